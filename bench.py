@@ -6,8 +6,8 @@
   IDs) + Lloyd assignment over K=256 centroids (cluster ID + exact-order fp64
   distance). Multi-GPU: contiguous row shards, one process per GPU, no
   data-path collective (hash and assign are per point) -> weak scaling.
-  The same line carries a "c5" object (unless --no-c5): configs[4]'s full
-  iteration on the same resident shard, below.
+  With --full the same line carries a "c5" object (unless --no-c5):
+  configs[4]'s full iteration on the same resident shard, below.
 --workload c5 (configs[4]: 80M x 128, K=1024 over 8 GPUs = 10M per GPU): one
   step = one full iteration, sharding.ShardedLloyd: lshkm_hash_assign (K=1024)
   + lshkm_kmeans_partial + all-reduce of the K x d sums and K counts over RCCL
@@ -18,7 +18,20 @@
   over RCCL point-to-point (sharding.recommend_sharded).
 Points are synthetic (include/lshkm_synth.h), generated in HBM before timing.
 
-python bench.py --gpus N --steps K --warmup W [--workload c5]
+python bench.py --gpus N --steps K --warmup W [--workload c5] [--dump-outputs DIR] [--full]
+  A plain run sets up, runs W untimed and K timed steps, writes its outputs if
+  --dump-outputs is given, and prints the result line (metric, value, unit,
+  ms_per_step, the exactness counters of the timed steps). --full adds
+  everything else to that line, each from runs of its own after the timed
+  steps: the fused pass's kernel time and roofline, the step with bit-exact
+  distances, the "c5" object, the normal_data leg, the C5 breakdown (sums +
+  exchange, recommend phases) and the CPU baselines (the --no-* options trim
+  a --full run).
+  --dump-outputs DIR: what the last timed step of the headline workload left in
+  the caller's arrays, as DIR/<name>.npy in float64 (at N > 1,
+  DIR/<name>.rank<r>.npy per rank): the per-row outputs on a fixed, seeded
+  sample of rows (rows.npy), small arrays whole. Same arguments, same inputs,
+  so two builds can be compared output for output.
   N > 1: started under torch.distributed.run (the driver does this), or, when
   no WORLD_SIZE is set, this script launches torch.distributed.run itself, as a
   child process, before anything touches the GPU. --dry-run: the same launch
@@ -162,6 +175,27 @@ def max_over_ranks(x, world, dev):
     return float(t.item())
 
 
+DUMP_ROWS, DUMP_SEED = 200_000, 0xD0E5    # 28 float64 per sampled row (C3): 45 MB, under the 64 MB a dump may take
+
+
+def dump_outputs(dirname, rank, world, per_row, whole):
+    """--dump-outputs: per_row arrays (device, one entry per resident row) on
+    the sampled rows, `whole` arrays as they are, each as float64 .npy (int32
+    IDs and counts are exact in it). The sample depends on the row count alone."""
+    os.makedirs(dirname, exist_ok=True)
+    n = next(iter(per_row.values())).shape[0]
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS,
+                                                                                                  replace=False))
+    dev = next(iter(per_row.values())).device
+    idx = torch.from_numpy(rows.astype(np.int64)).to(dev)
+    out = {"rows": rows}
+    out.update({name: t[idx].cpu().numpy() for name, t in per_row.items()})
+    out.update({name: t.cpu().numpy() for name, t in whole.items()})
+    suffix = "" if world == 1 else f".rank{rank}"
+    for name, a in out.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def timed(step, steps, warmup, world, dev):
     """W untimed steps, then exactly K steps bracketed by barrier + synchronize;
     returns the max over ranks of the elapsed seconds."""
@@ -211,7 +245,7 @@ def dry_run(args, world, rank):
                 "ms_per_step": elapsed / args.steps * 1e3, "allreduce_ok": ok,
                 "shards": [{"rank": r, "row0": a, "n": b} for r, a, b in gathered],
                 "backend": dist.get_backend()}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             attach_cpu_baseline(line, args, args.k or 256)
         print(json.dumps(line), flush=True)
     dist.destroy_process_group()
@@ -269,21 +303,27 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)   # untimed; the step time settles over the first few dozen calls
     ap.add_argument("--n", type=int, default=10_000_000, help="points per GPU")
     ap.add_argument("--workload", choices=["c3", "c5"], default="c3")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (kernel time and roofline, exact "
+                         "distances, the c5 object, the normal_data leg, the C5 breakdown, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64; per-row arrays on a fixed "
+                         "seeded sample of rows)")
     ap.add_argument("--k", type=int, default=None, help="centroids (default 256 for c3, 1024 for c5)")
-    ap.add_argument("--no-c5", action="store_true", help="c3: leave out the C5 iteration object")
+    ap.add_argument("--no-c5", action="store_true", help="c3 --full: leave out the C5 iteration object")
     ap.add_argument("--data", choices=["grid", "normal"], default="grid",
                     help="the rows: include/lshkm_synth.h's 2^-15 grid generator (default) or its full-mantissa "
                          "normal generator (SURVEY.md §8d)")
     ap.add_argument("--no-normal-leg", dest="normal_leg", action="store_false",
-                    help="c3 on grid data: leave out the normal_data object (C3 + C5 on full-mantissa rows)")
+                    help="c3 --full on grid data: leave out the normal_data object (C3 + C5 on full-mantissa rows)")
     ap.add_argument("--recom-users", type=int, default=1024,
                     help="C5: query users per iteration of the recommend step (0: no recommend step)")
     ap.add_argument("--no-exact-dist-line", dest="exact_dist_line", action="store_false",
-                    help="c3: leave out the timing with bit-exact (fp64 chain) distances")
+                    help="c3 --full: leave out the timing with bit-exact (fp64 chain) distances")
     ap.add_argument("--dry-run", action="store_true", help="gloo on CPU, no GPU work (tests the rank plumbing)")
     ap.add_argument("--cpu-port-hash-sample", type=int, default=400_000)
     ap.add_argument("--cpu-port-assign-sample", type=int, default=300_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baselines")
     ap.add_argument("--cpu-hash-sample", type=int, default=100_000)
     ap.add_argument("--cpu-assign-sample", type=int, default=12_000)
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"),
@@ -333,7 +373,7 @@ def main():
             Cc[i] = ctx.synth(SEED_DATA, 1, D, row0=int(row), kind=kind)[0].double()
         return Cc, sharding.local_src_rows(rows, rank * N, N)      # centroid override, shard-local
 
-    def c3_run(K, X=X, kind=args.data, steps=args.steps, warmup=args.warmup):
+    def c3_run(K, X=X, kind=args.data, steps=args.steps, warmup=args.warmup, dump=None):
         Cc, src = initial_centroids(K, kind)
         tuples = torch.empty((N, L_TABLES, K_FUNCS), dtype=torch.int32, device=dev)
         bucket = torch.empty((N, L_TABLES), dtype=torch.int32, device=dev)
@@ -347,10 +387,14 @@ def main():
                                          p(dist_)))
         ctx.reset_stats()
         elapsed = timed(step, steps, warmup, world, dev)
+        if dump:
+            dump_outputs(dump, rank, world, {"tuples": tuples, "bucket": bucket, "assign": assign, "dist": dist_}, {})
         ex = {"per_step": True, "assign_ambiguous_rows": ctx.stat(lk.STAT_ASSIGN_AMBIG) // (steps + warmup),
               "hash_fixup_rows": ctx.stat(lk.STAT_HASH_FIX) // (steps + warmup),
               "hash_exact_fallbacks": ctx.stat(lk.STAT_HASH_EXACT) // (steps + warmup),
               "refined_rows": ctx.stat(lk.STAT_REFINED) // (steps + warmup)}
+        if not args.full:
+            return elapsed, None, ex
         kms = fused_kernel_ms(lk, lib, ctx, step, max(3, steps))
         if args.exact_dist_line:
             # the same step with every distance from the reference-order fp64 chain
@@ -369,7 +413,7 @@ def main():
                                      "pow_fix_rows": pow_fix}
         return elapsed, kms, ex
 
-    def c5_run(K, X=X, kind=args.data, steps=args.steps, warmup=args.warmup):
+    def c5_run(K, X=X, kind=args.data, steps=args.steps, warmup=args.warmup, dump=None):
         # one full iteration: hash + assign, per-shard sums, RCCL all-reduce,
         # finalize, and the recommend step (get_top_N_recom over the whole
         # clusters of Q query users, the prediction sums carried rank to rank)
@@ -379,9 +423,17 @@ def main():
             it.enable_recommend(N_total, rank * N, Q=args.recom_users, n_top=5)
         ctx.reset_stats()
         elapsed = timed(it.step, steps, warmup, world, dev)
+        if dump:
+            whole = {"centers": it.C, "counts": it.last_counts}
+            if args.recom_users > 0:
+                whole["recommend"] = it.recom_out
+            dump_outputs(dump, rank, world, {"tuples": it.tuples, "bucket": it.bucket, "assign": it.assign,
+                                             "dist": it.dist}, whole)
         ex = {"per_step": True, "assign_ambiguous_rows": ctx.stat(lk.STAT_ASSIGN_AMBIG) // (steps + warmup),
               "hash_fixup_rows": ctx.stat(lk.STAT_HASH_FIX) // (steps + warmup),
               "refined_rows": ctx.stat(lk.STAT_REFINED) // (steps + warmup)}
+        if not args.full:
+            return elapsed, None, None, {"km_flagged_chains": it.flagged, "exactness": ex}
         it.timing = True
         kms = fused_kernel_ms(lk, lib, ctx, it.step, max(3, steps))
         it.timing = False
@@ -417,7 +469,7 @@ def main():
                 f"all-reduces of the |x| sums, bit positions and {K} counts; the chains the global never-rounds "
                 f"test flags carried rank to rank" if world > 1
                 else "none (N = 1: a single shard, no collective)")
-        return {
+        obj = {
             "metric": f"C5 LSH-assign + k-means recommend iterations: points/s (hash + assign K={K} + sums + "
                       f"{'RCCL exchange' if world > 1 else 'no collective at N = 1'} + finalize"
                       + (f" + recommend for {args.recom_users} users)" if args.recom_users > 0 else ")"),
@@ -431,14 +483,18 @@ def main():
             "km_flagged_chains": (rec or {}).pop("km_flagged_chains", None),
             "exactness": (rec or {}).pop("exactness", None),
             "recommend": rec or None,
-            "roofline": roofline(N, K, kms, traffic_for(args.traffic_json_c5, N, K, "c5"),
-                                 FUSED_WHAT + " (K = 1024: two 512-centroid passes)"),
         }
+        if args.full:
+            obj["roofline"] = roofline(N, K, kms, traffic_for(args.traffic_json_c5, N, K, "c5"),
+                                       FUSED_WHAT + " (K = 1024: two 512-centroid passes)")
+        else:                   # the breakdown takes runs of its own
+            del obj["km_sums_exchange_ms"], obj["recommend"]
+        return obj
 
     line = None
     if args.workload == "c5":
         K = args.k or 1024
-        el, kms, xms, rec = c5_run(K)
+        el, kms, xms, rec = c5_run(K, dump=args.dump_outputs)
         line = c5_object(K, el, kms, xms, rec)
         line.update({"metric": METRIC + " (C5 workload)", "unit": "point hash+assign ops/s", "steps": args.steps,
                      "warmup": args.warmup, "higher_is_better": True, "vs_baseline": None,
@@ -446,7 +502,7 @@ def main():
                      "data": DATA[args.data]})
     else:
         K = args.k or 256
-        el, kms, ex = c3_run(K)
+        el, kms, ex = c3_run(K, dump=args.dump_outputs)
         line = {
             "metric": METRIC, "value": N_total * args.steps / el, "unit": "point hash+assign ops/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3,
@@ -456,14 +512,15 @@ def main():
             "config": {"workload": f"C3 Lloyd K={K} + C2 LSH L=5 k=4 hashing, N={N} per GPU, d=128",
                        "N_per_gpu": N, "N_total": N_total, "d": D, "K": K, "L": L_TABLES, "k": K_FUNCS,
                        "w": W, "nb": nb, "parallelism": f"dp{world} (row shards)"},
-            "roofline": roofline(N, K, kms, traffic_for(args.traffic_json, N, K, "c3"), FUSED_WHAT),
             "exactness": ex,
         }
-        if not args.no_c5:
+        if args.full:
+            line["roofline"] = roofline(N, K, kms, traffic_for(args.traffic_json, N, K, "c3"), FUSED_WHAT)
+        if args.full and not args.no_c5:
             K5 = 1024
             el5, kms5, xms5, rec5 = c5_run(K5)
             line["c5"] = c5_object(K5, el5, kms5, xms5, rec5)
-        if args.data == "grid" and args.normal_leg:
+        if args.full and args.data == "grid" and args.normal_leg:
             # the same C3 step and C5 iteration on full-mantissa rows (SURVEY.md
             # §8d's N(0,1) data): the certificates' and exact chains' rates there
             Xn = ctx.synth(SEED_DATA, N, D, row0=rank * N, kind="normal")
@@ -482,7 +539,7 @@ def main():
     line["backend"] = backend
     if world > 1:
         torch.distributed.barrier()       # every rank's timed work is done before the CPU baseline runs
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # the reference's CPU path on this host, in the same run (rank 0 only; at
         # N > 1 after the final barrier, so no rank's timing overlaps it)
         attach_cpu_baseline(line, args, line["config"]["K"])
