@@ -16,7 +16,7 @@ import os
 
 import numpy as np
 
-from lshkm import LshkmError, kmeans_pp_rows, kmeans_update, lloyd_assign, load_config, read_vectors
+from lshkm import LshkmError, kmeans_pp_rows, kmeans_update, lloyd_assign, load_config, pam_update, read_vectors
 
 
 def device_rows(ctx, X_host):
@@ -28,16 +28,30 @@ def device_rows(ctx, X_host):
     return ctx.torch.from_numpy(X32 if exact else X64).to(ctx.dev)
 
 
-def cluster_vectors(ctx, X_host, K, max_iters, min_dist, seed, metric="cosine"):
-    """k-means++ + Lloyd + k-means (main.cpp:94-111).
-    Returns dict(rows, assign, dist, centers, iters, cont) (numpy)."""
+def cluster_vectors(ctx, X_host, K, max_iters, min_dist, seed, metric="cosine", update="kmeans"):
+    """k-means++ + Lloyd + k-means (main.cpp:94-111); update="pam": the update
+    step is pam_lloyds (update.hpp:89-142) instead, the loop running until no
+    medoid was swapped; every centroid then stays a dataset row (src_rows: the
+    override of lloyds_assignment applies in every iteration).
+    Returns dict(rows, assign, dist, centers, iters, cont) (numpy; with
+    update="pam" also medoid_rows)."""
     torch = ctx.torch
+    if update not in ("kmeans", "pam"):
+        raise LshkmError(f"unknown update step '{update}' (kmeans or pam)")
     X = device_rows(ctx, X_host)
     rows = kmeans_pp_rows(ctx, X, K, metric, seed)
     C = X[torch.from_numpy(rows.astype(np.int64)).to(ctx.dev)].double()
     src = rows            # initial centroids are dataset rows: the override applies (assignment.hpp:77-78)
     it, cont = 0, True
     assign = dist = None
+    while update == "pam" and cont and it < max_iters:
+        assign, dist = lloyd_assign(ctx, X, C, metric, src)
+        src, C, _, cont = pam_update(ctx, X, assign, K, metric, src, C)
+        it += 1
+    if update == "pam":
+        ctx.sync()
+        return dict(rows=rows, assign=assign.cpu().numpy(), dist=dist.cpu().numpy(), centers=C.cpu().numpy(),
+                    iters=it, cont=cont, medoid_rows=src)
     while cont and it < max_iters:
         assign, dist = lloyd_assign(ctx, X, C, metric, src)
         Cn, _, cont = kmeans_update(ctx, X, assign, C, metric, min_dist)

@@ -979,6 +979,143 @@ int lshkm_silhouette_f64(lshkm_ctx ctx, const double* X, int64_t N, int d, const
     return silhouette_impl(ctx, X, N, d, assign, C, K, metric, out_host, s_dev);
 }
 
+// ------------------------------------------------------------------ PAM update
+// Clusters of at least this many members take the MFMA screen (euclidean,
+// d <= PAM_SCREEN_DMAX); smaller ones go straight to the exact chain: the
+// smallest size at which the screened update measured below the exact-only one
+// (4096 equal clusters, d = 128, grid rows: 1.13 vs 1.43 ms at 64 members, 1.05
+// vs 0.97 ms at 48; full-mantissa rows cross at 16). Test
+// switch LSHKM_PAM_PATH=screen: every cluster of >= 2 members is screened;
+// =exact: none is.
+constexpr int64_t PAM_SCREEN_MIN = 64;
+
+static int pam_update_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const int32_t* assign, int K, int metric,
+                           const int32_t* prev_rows, const double* C_old, int32_t* medoid_rows, double* C_new,
+                           double* sums_host, int* swapped) {
+    LSHKM_CHECK(ctx && (X.p || N == 0) && (assign || N == 0) && medoid_rows && swapped && N >= 0 && N < (1ll << 31) &&
+                    d > 0 && K > 0,
+                LSHKM_ERR_ARG, "bad arguments");
+    LSHKM_CHECK(metric == LSHKM_METRIC_EUCLIDEAN || metric == LSHKM_METRIC_COSINE, LSHKM_ERR_ARG, "unknown metric");
+    LSHKM_CHECK((C_old == nullptr) == (C_new == nullptr), LSHKM_ERR_ARG, "C_old_dev and C_new_dev go together");
+    LSHKM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int rc;
+    const size_t Nn = (size_t)std::max<int64_t>(N, 1), Kk = (size_t)K;
+    if ((rc = reserve(ctx, WS_ROWS, Nn * 4)) || (rc = reserve(ctx, WS_CROW, (Kk + 1) * 8)) ||
+        (rc = reserve(ctx, WS_FLAG, 64)))
+        return rc;
+    // per cluster: cnt [K] i64, coff [K + 1] i64, csum [K] f64, cmax [K] u64, med / cbad / screen [K] i32
+    if ((rc = ctx->ws_pam[2].reserve((4 * Kk + 1) * 8 + 3 * Kk * 4)) || (rc = ctx->ws_pam[1].reserve(Nn * 8))) return rc;
+    int64_t* cnt = ctx->ws_pam[2].as<int64_t>();
+    int64_t* coff = cnt + K;
+    double* csum = reinterpret_cast<double*>(coff + K + 1);
+    unsigned long long* cmax = reinterpret_cast<unsigned long long*>(csum + K);
+    int32_t* med = reinterpret_cast<int32_t*>(cmax + K);
+    int* cbad = med + K;
+    int32_t* screen_d = cbad + K;
+    double* sums = ctx->ws_pam[1].as<double>();
+    int32_t* rows = slot<int32_t>(ctx, WS_ROWS);
+    int64_t* crow = slot<int64_t>(ctx, WS_CROW);
+    int* flag = slot<int>(ctx, WS_FLAG);
+
+    // assign values outside [0, K) are refused before the scatter reads them;
+    // rows on a grid of <= 26 bits (every difference squares exactly): x*x for
+    // pow(x, 2) without the per-square test (grid_exact_squares)
+    const bool eu = metric == LSHKM_METRIC_EUCLIDEAN;
+    if ((rc = launch_pam_check_assign(s, assign, N, K, flag + 4))) return rc;
+    if (eu && (rc = launch_grid_bits(s, X, N * d, flag))) return rc;
+    int qt[3] = {0, 0, 0}, bad = 0;
+    {
+        const D2H r[2] = {{&bad, flag + 4, sizeof bad}, {qt, flag, eu ? sizeof qt : 0}};
+        if ((rc = d2h_batch_impl(ctx, r, 2))) return rc;
+    }
+    LSHKM_CHECK(!bad, LSHKM_ERR_ARG, "assign holds a cluster ID outside [0, K)");
+    const bool exsq = eu && grid_exact_squares(qt);
+    // separate_clusters_from_input (utils.hpp:150-158): members in row order
+    if ((rc = build_csr(ctx, assign, 1, N, K, rows, crow))) return rc;
+    std::vector<int64_t> hcrow(Kk + 1);
+    if ((rc = d2h(ctx, hcrow.data(), crow, (Kk + 1) * 8))) return rc;
+
+    const bool can_screen = eu && d <= PAM_SCREEN_DMAX && !test_switch("LSHKM_PAM_PATH", "exact");
+    const int64_t smin = test_switch("LSHKM_PAM_PATH", "screen") ? 2 : PAM_SCREEN_MIN;
+    std::vector<int32_t> screen(Kk, 0);
+    std::vector<int2> items;
+    for (int c = 0; c < K && can_screen; c++) {
+        const int64_t n = hcrow[c + 1] - hcrow[c];
+        if (n < smin) continue;
+        screen[c] = 1;
+        for (int64_t j = 0; j < n; j += PAM_SCREEN_COLS) items.push_back(make_int2(c, (int)j));
+    }
+    const int32_t* cand = nullptr;
+    const int64_t* sel_off = crow;
+    const int64_t* m_dev = nullptr;
+    if (!items.empty()) {
+        // per member: n2, S~, E [N] f64, the fixed-point row parts of S~, E [N] u64, rho [N] f32,
+        // cand [N] i32, flag [N] u8
+        if ((rc = ctx->ws_pam[0].reserve(Nn * 49)) || (rc = ctx->ws_pam[3].reserve(items.size() * sizeof(int2))) ||
+            (rc = ctx->ws_pam[4].reserve(scan_ws_bytes(K))))
+            return rc;
+        double* n2 = ctx->ws_pam[0].as<double>();
+        double* St = n2 + Nn;
+        double* Et = St + Nn;
+        unsigned long long* Sfix = reinterpret_cast<unsigned long long*>(Et + Nn);
+        unsigned long long* Efix = Sfix + Nn;
+        float* rho = reinterpret_cast<float*>(Efix + Nn);
+        int32_t* cand_w = reinterpret_cast<int32_t*>(rho + Nn);
+        uint8_t* mflag = reinterpret_cast<uint8_t*>(cand_w + Nn);
+        int2* items_d = ctx->ws_pam[3].as<int2>();
+        LSHKM_HIP(hipMemsetAsync(cbad, 0, Kk * 4, s));
+        LSHKM_HIP(hipMemsetAsync(cmax, 0, Kk * 8, s));
+        LSHKM_HIP(hipMemsetAsync(Sfix, 0, Nn * 16, s));
+        const H2D up[2] = {{screen_d, screen.data(), Kk * 4}, {items_d, items.data(), items.size() * sizeof(int2)}};
+        if ((rc = h2d_batch_impl(ctx, up, 2))) return rc;
+        if ((rc = launch_pam_prep(s, X, d, rows, assign, N, n2, rho, cbad, cmax)) ||
+            (rc = launch_pam_screen(s, X, d, rows, crow, items_d, (int64_t)items.size(), n2, rho, St, Et, cmax, Sfix,
+                                    Efix)) ||
+            (rc = launch_pam_mark(s, crow, K, screen_d, cbad, St, Et, cmax, Sfix, Efix, mflag, cnt,
+                                  (unsigned long long*)ctx->stats.p)) ||
+            (rc = launch_scan_i64(s, cnt, K, coff, ctx->ws_pam[4].as<int64_t>())) ||
+            (rc = launch_pam_compact(s, crow, K, mflag, coff, cand_w)))
+            return rc;
+        cand = cand_w;
+        sel_off = coff;
+        m_dev = coff + K;
+    }
+    if ((rc = launch_pam_exact(s, X, d, metric, rows, crow, assign, cand, m_dev, N, sums, exsq)) ||
+        (rc = launch_pam_select(s, rows, cand, sel_off, K, sums, med, csum)))
+        return rc;
+    if (C_new && (rc = launch_pam_gather(s, X, d, med, K, C_old, C_new))) return rc;
+    std::vector<double> hsum(Kk);
+    std::vector<int32_t> hprev(Kk, -1);                 // medoid_rows may be prev_rows
+    if (prev_rows) std::memcpy(hprev.data(), prev_rows, Kk * 4);
+    {
+        const D2H r[2] = {{medoid_rows, med, Kk * 4}, {hsum.data(), csum, Kk * 8}};
+        if ((rc = d2h_batch_impl(ctx, r, 2))) return rc;
+    }
+    // update.hpp:131-135; an empty cluster keeps its previous centroid
+    int sw = 0;
+    for (int c = 0; c < K; c++) {
+        const int32_t prev = hprev[c];
+        if (hcrow[c + 1] == hcrow[c]) medoid_rows[c] = prev;
+        else if (prev < 0 || medoid_rows[c] != prev) sw = 1;
+    }
+    if (sums_host) std::memcpy(sums_host, hsum.data(), Kk * 8);
+    *swapped = sw;
+    return 0;
+}
+
+int lshkm_pam_update(lshkm_ctx ctx, const float* X, int64_t N, int d, const int32_t* assign, int K, int metric,
+                     const int32_t* prev_rows, const double* C_old, int32_t* medoid_rows, double* C_new,
+                     double* sums_host, int* swapped) {
+    return pam_update_impl(ctx, X, N, d, assign, K, metric, prev_rows, C_old, medoid_rows, C_new, sums_host, swapped);
+}
+
+int lshkm_pam_update_f64(lshkm_ctx ctx, const double* X, int64_t N, int d, const int32_t* assign, int K, int metric,
+                         const int32_t* prev_rows, const double* C_old, int32_t* medoid_rows, double* C_new,
+                         double* sums_host, int* swapped) {
+    return pam_update_impl(ctx, X, N, d, assign, K, metric, prev_rows, C_old, medoid_rows, C_new, sums_host, swapped);
+}
+
 }  // extern "C"
 
 namespace lshkm {

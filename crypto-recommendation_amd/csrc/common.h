@@ -81,7 +81,9 @@ enum Stat {
     STAT_REC_SOFT = 7,       // clustering-recommender similarities decided by the x87 chain (IpAcc declined)
     STAT_POW_FIX = 8,        // euclidean winner distances redone with glibc's pow(x, 2) (an inexact square)
     STAT_KM_SEQ = 9,         // k-means (cluster, dim) sums whose never-rounds test failed (sequential / segment chain)
-    STAT_COUNT = 10
+    STAT_PAM_SCREENED = 10,  // PAM update: clusters whose argmin went through the MFMA screen
+    STAT_PAM_EXACT = 11,     // ... and the members the screen left to the exact chain
+    STAT_COUNT = 12
 };
 
 constexpr int WAVE = 64;

@@ -74,6 +74,7 @@ struct lshkm_ctx_s {
     lshkm::Buf ws_long;          // the recommender's chains of huge clusters (RcLong)
     lshkm::Buf ws_km_seg;        // k-means: the segment records of the chains the never-rounds test flags (fp32 rows)
     lshkm::Buf ws_scan;          // multi-block scans of large query size arrays
+    lshkm::Buf ws_pam[5];        // PAM update (lshkm_pam_update): per-member, per-candidate, per-cluster, items, scan
     // workspaces of the entry points that synchronise their stream before
     // returning (kmeans_pp, p_closest, top_n_recom): reused across calls
     lshkm::Buf ws_call[10];

@@ -437,6 +437,46 @@ int launch_sil_points(hipStream_t s, Pts X, int d, int metric, const int32_t* ro
 int launch_sil_sum(hipStream_t s, const double* sv, const int32_t* rows, const int64_t* crow, int K, int64_t N,
                    double* raw, double* out);
 
+// PAM medoid update (pam.hip). Positions q index the cluster CSR (rows[q]).
+// bad [1]: set when an assign value lies outside [0, K).
+int launch_pam_check_assign(hipStream_t s, const int32_t* assign, int64_t N, int K, int* bad);
+// The screen (euclidean, d <= PAM_SCREEN_DMAX): per position the f32-rounded
+// row's |x|^2 (n2) and |x - f32(x)| rounded up (rho); cbad[c] != 0 when cluster
+// c holds a row outside the range the bound assumes (non-finite, |x| >= 2^50);
+// cmax[c] (zeroed by the caller): the bits of the cluster's largest n2.
+constexpr int PAM_SCREEN_DMAX = 128;
+constexpr int PAM_SCREEN_COLS = 128;     // members owned by one block of the screen
+int launch_pam_prep(hipStream_t s, Pts X, int d, const int32_t* rows, const int32_t* assign, int64_t N, double* n2,
+                    float* rho, int* cbad, unsigned long long* cmax);
+// items [nitems]: (cluster, first owned member) of every block; per member of
+// a screened cluster the approximate dist_sum and its bound in two parts:
+// St / Et [N] from the tiles it owned a column of, Sfix / Efix [N] (zeroed by
+// the caller; fixed point) from the tiles it was a row of.
+int launch_pam_screen(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, const int2* items,
+                      int64_t nitems, const double* n2, const float* rho, double* St, double* Et,
+                      const unsigned long long* cmax, unsigned long long* Sfix, unsigned long long* Efix);
+// screen [K] (host's choice per cluster) + cbad -> flag [N] (1 = the member goes
+// to the exact chain), cnt [K]; stats: the context's counters.
+int launch_pam_mark(hipStream_t s, const int64_t* crow, int K, const int32_t* screen, const int* cbad,
+                    const double* St, const double* Et, const unsigned long long* cmax,
+                    const unsigned long long* Sfix, const unsigned long long* Efix, uint8_t* flag, int64_t* cnt,
+                    unsigned long long* stats);
+// coff [K + 1] = scan of cnt: cand [coff[K]] = the flagged positions in order.
+int launch_pam_compact(hipStream_t s, const int64_t* crow, int K, const uint8_t* flag, const int64_t* coff,
+                       int32_t* cand);
+// sums[i] = dist_sum of candidate i (position cand[i], or i when cand is NULL;
+// m_dev: the candidate count on the device, NULL = N), in exact.h's order.
+int launch_pam_exact(hipStream_t s, Pts X, int d, int metric, const int32_t* rows, const int64_t* crow,
+                     const int32_t* assign, const int32_t* cand, const int64_t* m_dev, int64_t N, double* sums,
+                     bool exsq);
+// The reference's selection over each cluster's candidates [coff[c], coff[c+1])
+// (coff = crow when cand is NULL): med [K] = the medoid's row (-1: empty
+// cluster), csum [K] its dist_sum (-1.0: empty).
+int launch_pam_select(hipStream_t s, const int32_t* rows, const int32_t* cand, const int64_t* coff, int K,
+                      const double* sums, int32_t* med, double* csum);
+// C_new[c] = row med[c] widened to fp64, or C_old[c] for an empty cluster.
+int launch_pam_gather(hipStream_t s, Pts X, int d, const int32_t* med, int K, const double* C_old, double* C_new);
+
 // Synthetic data.
 int launch_synth(hipStream_t s, uint64_t seed, int64_t row0, int64_t rows, int d, float* X, int kind = 0);
 

@@ -23,6 +23,7 @@ EUCLIDEAN, COSINE = 0, 1
 STAT_HASH_EXACT, STAT_ASSIGN_AMBIG, STAT_COS_FIX, STAT_REFINED, STAT_HASH_FIX, STAT_REC_SOFT = 0, 1, 4, 5, 6, 7
 STAT_POW_FIX = 8
 STAT_KM_SEQ = 9
+STAT_PAM_SCREENED, STAT_PAM_EXACT = 10, 11
 _METRIC = {"euclidean": EUCLIDEAN, "cosine": COSINE, EUCLIDEAN: EUCLIDEAN, COSINE: COSINE}
 DIST_CERTIFIED, DIST_EXACT = 0, 1
 _DIST = {"certified": DIST_CERTIFIED, "default": DIST_CERTIFIED, "exact": DIST_EXACT,
@@ -139,6 +140,7 @@ def lib():
             "lshkm_synth": (i32, [vp, u64, i64, i64, i32, vp]),
             "lshkm_synth_normal": (i32, [vp, u64, i64, i64, i32, vp]),
             "lshkm_clusters": (i32, [vp, vp, i64, i32, vp, vp]),
+            "lshkm_pam_update": (i32, [vp, vp, i64, i32, vp, i32, i32, vp, vp, vp, vp, vp, C.POINTER(i32)]),
         }
         for name, (res, args) in sigs.items():
             for nm in (name, name + "_f64"):     # fp64-row twins share the signature
@@ -546,6 +548,26 @@ def kmeans_update(ctx, X, assign, C_old, metric="euclidean", min_dist=0.0):
     _ck(_fn("lshkm_kmeans_update", X)(ctx.h, _t_ptr(X), N, d, _t_ptr(assign), _t_ptr(C_old), K, _METRIC[metric],
                                   float(min_dist), _t_ptr(Cn), _t_ptr(cnt), C.byref(cont)))
     return Cn, cnt, bool(cont.value)
+
+
+def pam_update(ctx, X, assign, K, metric="euclidean", prev_rows=None, C_old=None):
+    """pam_lloyds (update.hpp:89-142). prev_rows [K]: the rows the previous
+    centroids are (-1: not a data row; None: all -1); C_old [K][d] (or None):
+    the previous centroids, kept by empty clusters. Returns (medoid_rows [K]
+    numpy int32, C_new [K][d] tensor or None without C_old, sums [K] numpy,
+    swapped)."""
+    torch = ctx.torch
+    N, d = X.shape
+    pr = None if prev_rows is None else np.ascontiguousarray(prev_rows, np.int32)
+    if pr is not None and pr.shape != (K,):
+        raise LshkmError(f"pam_update: prev_rows must hold K = {K} rows")
+    med = np.empty(K, np.int32)
+    sums = np.empty(K, np.float64)
+    Cn = None if C_old is None else ctx.empty((K, d), torch.float64)
+    sw = C.c_int()
+    _ck(_fn("lshkm_pam_update", X)(ctx.h, _t_ptr(X), N, d, _t_ptr(assign), K, _METRIC[metric], _np_ptr(pr),
+                                   _t_ptr(C_old), _np_ptr(med), _t_ptr(Cn), _np_ptr(sums), C.byref(sw)))
+    return med, Cn, sums, bool(sw.value)
 
 
 def kmeans_partial(ctx, X, assign, K, sums=None, counts=None, csr=None):

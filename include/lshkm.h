@@ -129,7 +129,9 @@ int lshkm_memcpy_d2h(lshkm_ctx ctx, void* dst_host, const void* src_dev, int64_t
  * 8 = euclidean winner distances (LSHKM_DIST_EXACT, hi-only pass) whose chain met an
  *     inexact square and were redone with glibc's pow(x, 2) (gpow2.h),
  * 9 = k-means (cluster, dim) sums of fp32 rows whose never-rounds test failed,
- *     i.e. that took a rounding-aware chain instead of plain fp64 adds. */
+ *     i.e. that took a rounding-aware chain instead of plain fp64 adds,
+ * 10 = PAM update: clusters whose argmin went through the MFMA screen,
+ * 11 = PAM update: members of those clusters the screen left to the exact chain. */
 int lshkm_get_stat(lshkm_ctx ctx, int which, int64_t* value_host);
 int lshkm_reset_stats(lshkm_ctx ctx);
 /* HIP-event timing of the dominant kernel launch (the fused hash+assign kernel)
@@ -382,6 +384,37 @@ int lshkm_kmeans_finalize(lshkm_ctx ctx, const double* sums_dev, const int64_t* 
  * rows_dev [N]. */
 int lshkm_clusters(lshkm_ctx ctx, const int32_t* assign_dev, int64_t N, int K, int64_t* crow_dev,
                    int32_t* rows_dev);
+
+/* ------------------------------------------------------------- PAM update
+ * pam_lloyds (update.hpp:89-142): per cluster (members in row order) the
+ * member p with the smallest dist_sum(p) = sum_j dist(x_p, x_j) over all
+ * members j in member order (j = p included), sequential fp64 adds from 0.0,
+ * every distance the reference's exact one; selection by
+ * `if (min == -1 || s < min)` in member order (the first of equal sums; the
+ * first member whatever its sum; a NaN min is never replaced). The reference's
+ * "<id>to<id>" cache needs no model: d is bitwise symmetric for unique IDs.
+ * prev_rows_host[c]: the row the previous centroid of c is (-1: not a data
+ * row, e.g. a "k_means_center"; NULL: all -1). medoid_rows_host [K]: the chosen
+ * rows (may be the prev_rows_host buffer); C_new_dev [K][d] (with C_old_dev; both
+ * NULL or neither): those rows widened to fp64; sums_host [K] (may be NULL):
+ * the winning dist_sum, NaN bits as x86 produces them; *swapped_host = 1 iff
+ * some cluster's medoid_rows[c] != prev_rows[c] (-1 always counts), the
+ * reference's return value.
+ * The one departure: an empty cluster (the reference indexes an empty vector,
+ * undefined) keeps its previous centroid: medoid_rows[c] = prev_rows[c],
+ * C_new[c] = C_old[c], sums[c] = -1.0 (the untouched sentinel), not a swap.
+ * assign values outside [0, K) are LSHKM_ERR_ARG. N < 2^31. Workspace is
+ * O(N + K): no cluster's distance matrix is stored. Euclidean clusters of
+ * enough members (d <= 128, finite rows with |x| < 2^50) first pass a screen
+ * on the matrix cores that bounds every member's dist_sum rigorously; only the
+ * members that can still hold the minimum take the exact chain, so the result
+ * is the same bit for bit (counters 10, 11). */
+int lshkm_pam_update(lshkm_ctx ctx, const float* X_dev, int64_t N, int d, const int32_t* assign_dev, int K,
+                     int metric, const int32_t* prev_rows_host, const double* C_old_dev,
+                     int32_t* medoid_rows_host, double* C_new_dev, double* sums_host, int* swapped_host);
+int lshkm_pam_update_f64(lshkm_ctx ctx, const double* X_dev, int64_t N, int d, const int32_t* assign_dev, int K,
+                         int metric, const int32_t* prev_rows_host, const double* C_old_dev,
+                         int32_t* medoid_rows_host, double* C_new_dev, double* sums_host, int* swapped_host);
 
 /* --------------------------------------------------------- range assignment
  * lsh_range_assignment / cube_range_assignment (assignment.hpp:108-145):

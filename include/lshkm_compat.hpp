@@ -16,6 +16,7 @@
  *   create_hypercube        lib/lsh_cube.hpp:108-136
  *   lloyds_assignment       lib/clustering_phases/assignment.hpp:54-80
  *   k_means                 lib/clustering_phases/update.hpp:37-86
+ *   pam_lloyds              lib/clustering_phases/update.hpp:89-142
  *   k_means_pp              lib/clustering_phases/initialization.hpp:71-156
  *   rand_selection          lib/clustering_phases/initialization.hpp:39-69
  *   get_P_closest           lib/crypto_rec.hpp:213-231
@@ -502,6 +503,38 @@ bool k_means(std::vector<CustVector<T>>& input_vectors, std::vector<CustVector<T
         centers[c] = new CustVector<T>("k_means_center", dims);
     }
     return true;
+}
+
+// pam_lloyds (update.hpp:89-142): per cluster the member with the smallest sum
+// of distances to all members becomes the centroid: centroids[c] is set to the
+// address of that input vector (nothing is deleted, as in the reference) where
+// it is not the vector centroids[c] already points to; returns whether any
+// centroid changed. The reference compares IDs; rows stand for them here (unique
+// IDs), and a centroid outside input_vectors (a "k_means_center") always counts
+// as changed. An empty cluster (undefined in the reference) keeps its centroid.
+template <typename T>
+bool pam_lloyds(std::vector<CustVector<T>>& input_vectors, std::vector<CustVector<T>*>& centroids,
+                std::string metric_type) {
+    const int metric = metric_of(metric_type);
+    if (input_vectors.empty() || centroids.empty()) return false;
+    const size_t N = input_vectors.size(), K = centroids.size(), d = input_vectors[0].getDimensions()->size();
+    const DevRows Xd = upload_rows(input_vectors, d);
+    std::vector<int32_t> a(N), prev(K), med(K);
+    for (size_t i = 0; i < N; i++) {
+        a[i] = input_vectors[i].getCluster();
+        if (a[i] < 0 || (size_t)a[i] >= K)
+            throw std::out_of_range("lshkm_compat: vector '" + input_vectors[i].getId() + "' has no cluster in [0, K)");
+    }
+    for (size_t c = 0; c < K; c++) prev[c] = (int32_t)row_of<T>(centroids[c], input_vectors.data(), (int64_t)N);
+    DevMem ad = upload(a.data(), N);
+    int swapped = 0;
+    check(Xd.f64 ? lshkm_pam_update_f64(context(), Xd.d(), (int64_t)N, (int)d, ad.as<int32_t>(), (int)K, metric,
+                                        prev.data(), nullptr, med.data(), nullptr, nullptr, &swapped)
+                 : lshkm_pam_update(context(), Xd.f(), (int64_t)N, (int)d, ad.as<int32_t>(), (int)K, metric, prev.data(),
+                                    nullptr, med.data(), nullptr, nullptr, &swapped));
+    for (size_t c = 0; c < K; c++)
+        if (med[c] >= 0 && med[c] != prev[c]) centroids[c] = &input_vectors[med[c]];
+    return swapped != 0;
 }
 
 // ------------------------------------------------------------ initialization

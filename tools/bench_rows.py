@@ -6,7 +6,7 @@ syncs (host launch and sync latency included) -- next to the CPU restatement (or
 thread, OMP_NUM_THREADS=1, kind "port") on a bounded sample of the same
 workload, scaled to the row's unit. Prints one JSON line per row.
 
-    python tools/bench_rows.py [--rows cosine,kpp,range,sil,update,lsh,cube,recom,csv,f64] [--no-cpu]
+    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64] [--no-cpu]
 """
 import argparse
 import json
@@ -88,8 +88,9 @@ def emit(row, unit, units, t_gpu, cpu=None, note="", bytes_per_unit=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", default="cosine,kpp,range,sil,update,lsh,cube,recom,csv,f64")
+    ap.add_argument("--rows", default="cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--pam-shapes", default="100000x16,1000000x256", help="NxK list of the pam row (d = 128)")
     a = ap.parse_args()
     rows = set(a.rows.split(","))
     ctx = lshkm.Context(0)
@@ -204,6 +205,38 @@ def main():
             c = (p2, cpu_time(lambda: oracle.silhouette(Xh, ah, C.cpu().numpy(), "euclidean")), f"{n} rows, K={K}")
         emit("silhouette_cluster", "distance pairs/s", pairs, t, c, "N=100k, d=128, K=16")
         del X
+
+    if "pam" in rows:        # pam_lloyds (update.hpp:89-142): the product library, then the test build
+        # with the exact chain forced and with the MFMA screen forced for every cluster
+        import amd
+        sw = amd.switched()
+        sctx = sw.Context(0)
+        shapes = [(int(s[0]), 128, int(s[1])) for s in (p.split("x") for p in a.pam_shapes.split(","))]
+        for N, d, K in shapes:
+            for kind in ("grid", "normal"):
+                X = ctx.synth(0x5EED + 3, N, d, kind=kind)
+                src = (np.arange(K) * (N // K)).astype(np.int64)
+                C = X[torch.from_numpy(src).to(ctx.dev)].double()
+                asg, _ = lshkm.lloyd_assign(ctx, X, C, "euclidean", src.astype(np.int32))
+                sizes = np.bincount(asg.cpu().numpy(), minlength=K).astype(np.float64)
+                pairs = float(np.sum(sizes ** 2))
+                reps = 2 if pairs > 2e9 else 3
+                t = gpu_time(ctx, lambda: lshkm.pam_update(ctx, X, asg, K, "euclidean"), reps=reps)
+                res, times, left = {}, {}, 0
+                for path in ("exact", "screen"):
+                    os.environ["LSHKM_PAM_PATH"] = path
+                    sctx.reset_stats()
+                    res[path] = sw.pam_update(sctx, X, asg, K, "euclidean")
+                    if path == "screen":
+                        left = sctx.stat(sw.STAT_PAM_EXACT)
+                    times[path] = gpu_time(sctx, lambda: sw.pam_update(sctx, X, asg, K, "euclidean"), reps=reps)
+                    del os.environ["LSHKM_PAM_PATH"]
+                same = all(np.array_equal(res["exact"][i], res["screen"][i]) for i in (0, 2))
+                emit("pam_lloyds", "distance pairs/s", pairs, t, None,
+                     f"N={N}, d={d}, K={K}, {kind} rows, clusters of {int(sizes.min())}..{int(sizes.max())}; exact-only "
+                     f"{times['exact'] * 1e3:.2f} ms, screen forced {times['screen'] * 1e3:.2f} ms with {left} of {N} "
+                     f"members ({left / N:.4%}) left to the exact chain; results equal: {same}")
+                del X
 
     if "lsh" in rows:        # create_LSH_hashtables + get_LSH_filtered_combined_buckets (C2)
         N, d, L, k = 1_000_000, 128, 5, 4
