@@ -482,8 +482,8 @@ int lshkm_lsh_hash_f64(lshkm_lsh lsh, const double* X, int64_t N, int32_t* tuple
 }  // extern "C"
 
 // Kernel path for assignment: d = 128 takes the split-f16 fused kernel
-// (persistent form, one launch per 256-centroid slice; cosine: normalised
-// centroids), else the f32-MFMA kernel (d <= 256), else the exact pass.
+// (hi-only passes over 512-centroid slices + the 3-product refinement of the
+// rows they list; cosine: normalised centroids), else the f32-MFMA kernel (d <= 256), else the exact pass.
 // LSHKM_ASSIGN_PATH = "f32" / "exact" forces a path (tests compare them).
 // fp64 rows and fp32 rows of d < 128 dims (d <= 128, K <= 512; either metric)
 // take the hi-only form too (path 3: zero-padded dims); other
@@ -495,7 +495,7 @@ static int assign_path(int metric, int d, int K, bool f64) {
     if (d == 128 && !f32 && !f64) {
         if (metric == LSHKM_METRIC_EUCLIDEAN || !test_switch("LSHKM_FUSED_FORM", "chunked")) return 0;
     }
-    if (!f32 && d <= 128 && K <= 512 && !test_switch("LSHKM_FUSED_HI", "0")) return 3;
+    if (!f32 && d <= 128 && K <= 512) return 3;
     return assign_dp(d) > 0 ? 1 : 2;
 }
 
@@ -561,10 +561,9 @@ static int assign_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const double* C, 
     // one pass for hashing + assignment: the euclidean index with euclidean
     // Lloyd (fused_ok: d = 128, L*k <= 32), or the cosine index with cosine Lloyd
     // on the hi-only form (k = 4)
-    const bool hi_form = !test_switch("LSHKM_FUSED_HI", "0");
     const bool fuse_hash = lsh && path == 0 && lsh->metric == metric &&
                            (metric == LSHKM_METRIC_EUCLIDEAN ? lsh->proj.fused_ok
-                                                             : (hi_form && lsh->proj.mfma_ok && lsh->proj.k == 4));
+                                                             : (lsh->proj.mfma_ok && lsh->proj.k == 4));
     int rc;
     if (lsh && !fuse_hash && (rc = hash_rows(ctx, lsh->metric == LSHKM_METRIC_EUCLIDEAN ? HM_LSH_EUCLID : HM_LSH_COSINE,
                                              X, N, lsh->proj, lsh->nb,
@@ -574,17 +573,15 @@ static int assign_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const double* C, 
         const int rows_kind = path == 3 ? (X.f64 ? 2 : 1) : 0;
         const int Kpad = (K + 63) / 64 * 64;
         const bool cosine = metric != LSHKM_METRIC_EUCLIDEAN;
-        // hi-only scoring + 3-product refinement; test switch LSHKM_FUSED_HI=0: the 3-product form alone
-        const bool hi = hi_form;
         // euclidean winner distances: the certified f32 form (default) or the
         // reference-order fp64 chain (LSHKM_DIST_EXACT)
         const bool fast = !cosine && rows_kind != 2 && !force_exact && fast_dist_on(ctx);
         // exact distances of the hi-only pass: rows whose chain met an inexact
         // square (glibc's pow(x, 2) may differ from x*x) are listed for the fix-up
-        const bool pwfix = !cosine && hi && !fast;
+        const bool pwfix = !cosine && !fast;
         // ws_hfix regions: [hash fix-ups] then, cosine: [declines of the hi-only
         // pass][declines of the refinement]; euclidean exact: [pow fix-ups]
-        const int nfix_regions = 1 + (cosine && hi ? 2 : 0) + (pwfix ? 1 : 0);
+        const int nfix_regions = 1 + (cosine ? 2 : 0) + (pwfix ? 1 : 0);
         const int64_t list_cap = N + FUSED_LIST_SLACK;
         const int64_t part_tiles = std::max<int64_t>((N + 31) / 32, (list_cap + 31) / 32 + FUSED_MAX_SEGS);
         if ((rc = ctx->ws_c32.reserve((size_t)Kpad * 128 * 2 * 2)) ||
@@ -592,10 +589,10 @@ static int assign_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const double* C, 
             (rc = ctx->ws_ambig.reserve((size_t)(N + FUSED_LIST_SLACK) * 4)) || (rc = ctx->ws_counter.reserve(64)) ||
             (rc = ctx->ws_seg.reserve((size_t)FUSED_MAX_SEGS * 2 * 4)) ||
             ((fuse_hash || cosine || pwfix) && (rc = ctx->ws_hfix.reserve((size_t)(N + FUSED_LIST_SLACK) * 8 * nfix_regions))) ||
-            (((cosine && hi) || pwfix) && (rc = ctx->ws_seg3.reserve((size_t)FUSED_MAX_SEGS * 2 * 4))) ||
+            ((cosine || pwfix) && (rc = ctx->ws_seg3.reserve((size_t)FUSED_MAX_SEGS * 2 * 4))) ||
             (Kpad > 256 && (rc = ctx->ws_part.reserve((size_t)part_tiles * 64 * 16))) ||
-            (hi && ((rc = ctx->ws_ambig2.reserve((size_t)list_cap * 4)) ||
-                    (rc = ctx->ws_seg2.reserve((size_t)FUSED_MAX_SEGS * 2 * 4)))) ||
+            (rc = ctx->ws_ambig2.reserve((size_t)list_cap * 4)) ||
+            (rc = ctx->ws_seg2.reserve((size_t)FUSED_MAX_SEGS * 2 * 4)) ||
             (fuse_hash && !cosine && !tuples && (rc = ctx->ws_tuples.reserve((size_t)std::max<int64_t>(N, 1) * lsh->proj.LK * 4))))
             return rc;
         unsigned long long* cnt = (unsigned long long*)ctx->ws_counter.p;
@@ -626,50 +623,46 @@ static int assign_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const double* C, 
         const bool xprep = exact_pruned(X, d, K, metric);
         if (xprep && (rc = exact_listed_prep(ctx, X, d, C, K, metric))) { LSHKM_LAUNCH_CHECK(); return rc; }
         FusedLaunch f;
-        f.C32 = C32; f.rn32 = rn32; f.fast_dist = fast ? 1 : 0;
-        f.rows = rows_kind; f.d = d; f.Cd = C;
-        f.X = X.f64 ? nullptr : X.f(); f.X64 = X.f64 ? X.d() : nullptr;
-        f.N = N; f.Ch = Ch; f.Cl = Cl; f.cnh = cnh; f.cbound = cbound; f.C64 = C64p ? C64p : C; f.Kpad = Kpad;
-        f.assign = assign; f.dist = dist; f.ambig = (int32_t*)ctx->ws_ambig.p; f.ambig_count = cnt;
-        f.stats = (unsigned long long*)ctx->stats.p;
+        FusedArgs& a = f.a;
+        a.C32 = C32; a.rn32 = rn32; a.fast_dist = fast ? 1 : 0;
+        f.rows = rows_kind; a.d = d; a.Cd = C;
+        a.X = X.f64 ? nullptr : X.f(); a.X64 = X.f64 ? X.d() : nullptr;
+        a.N = N; a.Ch = Ch; a.Cl = Cl; a.cnh = cnh; a.cbound = cbound; a.C64 = C64p ? C64p : C; a.Kpad = Kpad;
+        a.assign = assign; a.dist = dist; a.ambig = (int32_t*)ctx->ws_ambig.p; a.ambig_count = cnt;
+        a.stats = (unsigned long long*)ctx->stats.p;
         f.list_cap = N + FUSED_LIST_SLACK;
         f.seg_counts = (int32_t*)ctx->ws_seg.p;
         f.seg_cap = FUSED_MAX_SEGS;
         if (Kpad > 256) { f.part = ctx->ws_part.p; f.part_bytes = part_tiles * 64 * 16; }
-        if (hi) {
-            f.hi = true;
-            f.list2 = (int32_t*)ctx->ws_ambig2.p;
-            f.seg_counts2 = (int32_t*)ctx->ws_seg2.p;
-            f.refined = cnt + 2;
-        }
+        f.list2 = (int32_t*)ctx->ws_ambig2.p;
+        f.seg_counts2 = (int32_t*)ctx->ws_seg2.p;
+        f.refined = cnt + 2;
         if (pwfix) {
-            f.cfix = (unsigned long long*)ctx->ws_hfix.p + (N + FUSED_LIST_SLACK);
-            f.cfix_counts = (int32_t*)ctx->ws_seg3.p;
-            f.cfix_count = cnt + 3;
+            a.cfix = (unsigned long long*)ctx->ws_hfix.p + (N + FUSED_LIST_SLACK);
+            a.cfix_counts = (int32_t*)ctx->ws_seg3.p;
+            a.cfix_count = cnt + 3;
         }
         if (cosine && rows_kind == 2) {
             if ((rc = ctx->ws_xn2.reserve((size_t)std::max<int64_t>(N, 1) * 8))) return rc;
             if ((rc = launch_row_sumsq(s, X.d(), N, d, (double*)ctx->ws_xn2.p))) { LSHKM_LAUNCH_CHECK(); return rc; }
-            f.xn2 = (const double*)ctx->ws_xn2.p;
+            a.xn2 = (const double*)ctx->ws_xn2.p;
         }
         if (cosine) {
-            f.metric = 1; f.nbv = nbv;
-            f.hfix = (unsigned long long*)ctx->ws_hfix.p; f.hfix_count = hi ? cnt + 1 : cnt + 3;
-            if (hi) {
-                f.cfix = f.hfix + (N + FUSED_LIST_SLACK);
-                f.cfix_counts = (int32_t*)ctx->ws_seg3.p;
-                f.cfix_count = cnt + 3;
-                f.hfix2 = f.cfix + (N + FUSED_LIST_SLACK);
-            }
+            f.metric = 1; a.nbv = nbv;
+            a.hfix = (unsigned long long*)ctx->ws_hfix.p; a.hfix_count = cnt + 1;
+            a.cfix = a.hfix + (N + FUSED_LIST_SLACK);
+            a.cfix_counts = (int32_t*)ctx->ws_seg3.p;
+            a.cfix_count = cnt + 3;
+            f.hfix2 = a.cfix + (N + FUSED_LIST_SLACK);
         }
         if (fuse_hash) {
             const ProjTable& pj = lsh->proj;
-            f.Vh = pj.vh_d.as<_Float16>(); f.Vl = pj.vl_d.as<_Float16>(); f.PT = pj.PT_d.as<double>();
-            f.tv = pj.t_d.as<float>(); f.pnorm = pj.pn_d.as<double>(); f.v1 = pj.v1_d.as<double>();
-            f.rv = pj.r_d.as<int32_t>(); f.w = pj.w; f.L = pj.L; f.k = pj.k; f.LK = pj.LK; f.LKpad = pj.LKpad;
-            f.nb = lsh->nb; f.phi = phi; f.bucket = bucket;
-            f.tuples = cosine ? nullptr : tuples ? tuples : (int32_t*)ctx->ws_tuples.p;
-            f.hfix = (unsigned long long*)ctx->ws_hfix.p; f.hfix_count = cnt + 1;
+            a.Vh = pj.vh_d.as<_Float16>(); a.Vl = pj.vl_d.as<_Float16>(); a.PT = pj.PT_d.as<double>();
+            a.tv = pj.t_d.as<float>(); a.pnorm = pj.pn_d.as<double>(); a.v1 = pj.v1_d.as<double>();
+            a.rv = pj.r_d.as<int32_t>(); a.w = pj.w; a.L = pj.L; a.k = pj.k; a.LK = pj.LK; a.LKpad = pj.LKpad;
+            a.nb = lsh->nb; a.phi = phi; a.bucket = bucket;
+            a.tuples = cosine ? nullptr : tuples ? tuples : (int32_t*)ctx->ws_tuples.p;
+            a.hfix = (unsigned long long*)ctx->ws_hfix.p; a.hfix_count = cnt + 1;
         }
         if (fuse_hash && ctx->side_init() == 0) {
             f.side = ctx->side_stream; f.fork = ctx->fork_ev; f.join = ctx->join_ev;
@@ -691,7 +684,7 @@ static int assign_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const double* C, 
         if (ctx->timing) LSHKM_HIP(hipEventRecord(ctx->tev[1], s));
         if ((rc = exact_listed(ctx, X, d, C, K, metric, cnt, N, assign, dist, f.nseg ? f.final_counts : nullptr,
                                f.seg_rows, f.nseg, f.nseg ? f.final_list : nullptr, !fast, xprep,
-                               cosine ? f.xn2 : nullptr, cosine ? nbv : nullptr))) { LSHKM_LAUNCH_CHECK(); return rc; }
+                               cosine ? f.a.xn2 : nullptr, cosine ? nbv : nullptr))) { LSHKM_LAUNCH_CHECK(); return rc; }
         if (sj.pending) {
             LSHKM_HIP(hipStreamWaitEvent(s, f.join, 0));
             sj.pending = false;
@@ -699,14 +692,14 @@ static int assign_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const double* C, 
         {
             int di[3], n = 0;
             const unsigned long long* sp[3];
-            if (hi) { di[n] = STAT_REFINED; sp[n++] = cnt + 2; }
+            di[n] = STAT_REFINED; sp[n++] = cnt + 2;
             if (fuse_hash) { di[n] = STAT_HASH_FIX; sp[n++] = cnt + 1; }
             di[n] = STAT_ASSIGN_AMBIG; sp[n++] = cnt;
             if ((rc = launch_add_counters(s, (unsigned long long*)ctx->stats.p, n, di, sp))) { LSHKM_LAUNCH_CHECK(); return rc; }
         }
         if (cosine || pwfix) {
             if ((rc = launch_cos_fix_seg(s, X, d, C, f.ncos_lists, f.cos_list, f.cos_counts, f.seg_rows, f.nseg, assign,
-                                         dist, cosine ? 1 : 0, cosine ? f.xn2 : nullptr, cosine ? nbv : nullptr))) { LSHKM_LAUNCH_CHECK(); return rc; }
+                                         dist, cosine ? 1 : 0, cosine ? f.a.xn2 : nullptr, cosine ? nbv : nullptr))) { LSHKM_LAUNCH_CHECK(); return rc; }
             if ((rc = launch_add_counter(s, (unsigned long long*)ctx->stats.p + (cosine ? STAT_COS_FIX : STAT_POW_FIX), cnt + 3))) { LSHKM_LAUNCH_CHECK(); return rc; }
         }
     } else if (path == 1) {

@@ -1,5 +1,6 @@
 // fused_args.h — the argument block of the fused hash + assign kernels
-// (fused.hip: the persistent and hi-only forms).
+// (fused_hi.hip, fused_refine.hip, fused_chunked.hip and the fix-ups of
+// fused_small.hip; filled by the caller through FusedLaunch::a, kernels.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,7 +60,7 @@ struct FusedArgs {
     // crosses passes in part[tile * 64 + lane]
     float4* part;
     int t0, pass_first, pass_last;
-    // LIST form (refinement of the rows a hi-only pass left uncertified): block b
+    // refinement of the rows a hi-only pass left uncertified (fused_refine.hip): block b
     // takes the rows list_in[b * list_seg_rows ..][0 .. list_counts[2b])
     const int32_t* list_in;
     const int32_t* list_counts;

@@ -1,0 +1,918 @@
+// fused_hi.hip — the hi-only form of the fused pass (fused.hip).
+// Lloyd (+ hashing, euclidean) with ONE f16 MFMA per centroid product: the
+// score is t~ = acc(-|c|^2/2 + sum_j xh_j ch_j), the accumulator initialised
+// with the f32 -|c|^2/2 (no epilogue add), ch = f16(f32(c)), xh = f16(x);
+// cosine (MET = 1): the normalised centroid rows, no offset.
+// Bound (rigorous, |x_j| <= 2^15, c in range): with xr = x - xh (exact in f32)
+// and cr = c - ch,
+//   |t~ - t| <= |xh||cr| + |xr||c| + 2^-24|cn| + A (|cn| + |xh||ch|),
+//   A = 130 2^-23 (<= 129 round-toward-zero additions of partial sums bounded
+//   by |cn| + sum|xh_j ch_j|), plus the terms of the 3-product form for the
+//   reference's own fp64 roundings (2^-41 (|x|^2 + |c|^2)) and the packed tile
+//   index (2^-18 (|x||c| + |cn|)); |xr| is summed per row, the centroid
+//   maxima come from the prep (cbound[3..6]). A point is certified iff
+//   M2 < M1 - 2E; the others (~3% of N(0,1) rows at K = 256) are listed for the
+//   3-product form (fused_persistent_kernel, fused_refine.hip), which certifies
+//   all but ~1% of those and lists the rest for the exact pass.
+// One third of the MFMA work of the 3-product form, and only the hi image of
+// the centroids in LDS: up to 512 centroids per pass (K = 1024: 2 passes).
+#include "fused_impl.h"
+
+namespace lshkm {
+
+__host__ __device__ constexpr int fh_lds_bytes(int Kpad, bool hash) {
+    return 16 + Kpad * FU_RS * 2 + Kpad * 4 + (hash ? 2 * 32 * FU_RS * 2 + FP_HC_BYTES : 0);
+}
+static_assert(fh_lds_bytes(FH_KMAX, true) <= 160 * 1024, "hi-only LDS image exceeds 160 KiB");
+constexpr double FH_A = 130.0 * 0x1p-23;
+
+// Waves per block of the hi-only form (one block per CU), per instantiation:
+// 8 unless a third wave per SIMD fits without spills and pays (the 8- vs
+// 12-wave measurements: DESIGN.md, "tried and rejected").
+constexpr int FH_WAVES_MPFAST = 12;  // the last pass of the multi-pass form with the certified distance
+constexpr int FH_FAST_WAVES = 8;     // the single-pass FAST form (the headline kernel)
+template <bool HASH, bool MP, int MET, bool FAST = false>
+__host__ __device__ constexpr int fh_waves() {
+    return HASH && MP ? 12 : (MP && FAST ? FH_WAVES_MPFAST : (FAST && !MP ? FH_FAST_WAVES : 8));
+}
+
+// The upper half's finish of the cosine winner certificate (IpAcc, exact.h):
+// the halves' double-double sums joined by one TwoSum; sum_k |S_k| bound
+// rounded up (+ 2^-47 relative for the roundings of |A_k + B_end| and of the
+// sums here; the partial sums stand in for the exact ones: their TwoSum rests,
+// |sl| <= 64 2^-53 max|t| per half, and the offsets, <= 2^-38 max|t|, charged
+// absolutely -- a cancelling A_k + B_end must not hide them). max |t| of both
+// halves' running sums <= sum_j |p_j| <= (1 + 2^-53) |x| |c| (Cauchy-Schwarz):
+// mb = 2 sqrt(xa nbv) (1 + 2^-40) bounds the pair of them without a per-term
+// max; sum |S_k| >= 2^-790 stands in for quot_status's lower range check on
+// the partial sums themselves (max |S_k| >= that / 128).
+__device__ inline int cosine_halves_finish(double sh0, double sl0, double ts0, double sh, double sl, double ts,
+                                           double xa, double nbv, double& v) {
+    const double mb = 2.0 * sqrt(__dmul_rn(xa, nbv)) * (1.0 + 0x1p-40);
+    const double tsum = __dadd_rn(ts0, ts);
+    if (!(tsum >= 0x1p-790)) return 2;
+    IpAcc ip;
+    const double t = __dadd_rn(sh0, sh);
+    const double bb = __dsub_rn(t, sh0);
+    const double e = __dadd_rn(__dsub_rn(sh0, __dsub_rn(t, bb)), __dsub_rn(sh, bb));
+    ip.sh = t;
+    ip.sl = __dadd_rn(__dadd_rn(sl0, sl), e);
+    ip.ts = __dadd_rn(tsum * (1.0 + 0x1p-47), 0x1p-37 * mb);
+    ip.mx = mb;
+    double q, qr;
+    const int st = ip.quot_status(__dmul_rn(sqrt(xa), sqrt(nbv)), q, qr);
+    if (st == 0) v = __dsub_rn(1.0, q);
+    return st;
+}
+
+// MET = 1: cosine (the prep's normalised centroid rows, score x.c^ with no
+// offset; the winner's distance from the row in registers, declines to the
+// cfix list). HASH with MET = 1: CosineHGen signs of the L*k projections
+// (k = 4: table l = 2g + h in D registers 4g..4g+3), certified as in
+// hash_mfma.hip, g = phi = bucket; uncertified signs to the hfix list.
+// Cosine winner distance from the row in registers, both lane halves busy.
+// Lane half h owns dims 16s + 8h..+7 (s = 0..7). Each half accumulates the
+// double products of ITS dims with IpAcc's double-double (exact.h), in its own
+// order; the reference's x87 chain runs over all 128 in order (block 2s = half
+// 0's step s, block 2s + 1 = half 1's), so its partial sums are S_k = A_k +
+// B_end(s-1) in half 0's block s and S_k = B_k + A_end(s) in half 1's. The
+// halves trade their running sums after every step: half 0 adds |A_k + B_end(s-1)|
+// exactly as the reference's partial sum, half 1 |B_k + A_end(s-1)| plus
+// 8 |A_end(s) - A_end(s-1)| (the block it runs one step behind) -- the round-4
+// bound 8 (sum |A_end| + sum |B_end|) roughly doubled sum_k |S_k| and declined
+// 9.3 % of the C3 winners. max |S_k| from the norms (cosine_halves_finish;
+// exact.h quot_status decides). |x|^2 is the reference's sequential chain, the
+// halves taking turns (the euclidean winner's pattern).
+// Returns 0 (certified, v = 1 - q), 1 / 2 (declined: soft-x87 fix-up).
+__device__ inline int cosine_winner_halves(const float (&xf)[64], const double* __restrict__ crow_h, double nbv, int h,
+                                           double& v) {
+    // |x|^2: the reference's sequential fp64 chain (cust_vector.hpp:139-155), halves alternating
+    double xa = 0.0;
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        if (h == 0) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const double xj = (double)xf[8 * s + j];
+                xa = __dadd_rn(xa, __dmul_rn(xj, xj));
+            }
+        }
+        xa = take_from_lower(xa);
+        if (h == 1) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const double xj = (double)xf[8 * s + j];
+                xa = __dadd_rn(xa, __dmul_rn(xj, xj));
+            }
+        }
+        xa = take_from_upper(xa);
+    }
+    // the inner product, each half over its own dims
+    double sh = 0.0, sl = 0.0, ts = 0.0;
+    double off = 0.0;                     // half 0: B_end(s-1); half 1: A_end(s-1)
+    double2 cb[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) cb[j] = *reinterpret_cast<const double2*>(crow_h + 2 * j);
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        double cv[8];
+#pragma unroll
+        for (int j = 0; j < 4; j++) { cv[2 * j] = cb[j].x; cv[2 * j + 1] = cb[j].y; }
+        if (s + 1 < 8) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) cb[j] = *reinterpret_cast<const double2*>(crow_h + 16 * (s + 1) + 2 * j);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const double pj = __dmul_rn((double)xf[8 * s + j], cv[j]);
+            const double t = __dadd_rn(sh, pj);
+            const double bb = __dsub_rn(t, sh);
+            const double e = __dadd_rn(__dsub_rn(sh, __dsub_rn(t, bb)), __dsub_rn(pj, bb));   // TwoSum
+            sh = t;
+            sl = __dadd_rn(sl, e);
+            ts = __dadd_rn(ts, fabs(__dadd_rn(t, off)));
+        }
+        // trade the running sums: half 0 takes B_end(s), half 1 A_end(s) (and
+        // charges the block it ran behind: 8 |A_end(s) - A_end(s-1)|)
+        const double other = swap_halves(sh, h);
+        if (h == 1) ts = __dadd_rn(ts, 8.0 * fabs(__dsub_rn(other, off)));
+        off = other;
+    }
+    // the lower half's accumulator to the upper lanes
+    const double sh0 = swap_halves(sh, h), sl0 = swap_halves(sl, h), ts0 = swap_halves(ts, h);
+    if (h == 0) return 2;                 // the upper lanes finish
+    return cosine_halves_finish(sh0, sl0, ts0, sh, sl, ts, xa, nbv, v);
+}
+
+// The same for fp64 rows (ROWS = 2): the exact x values re-read from the row
+// (L2) two 16-dim steps ahead (a rolled loop: unrolled, the loads of all steps
+// were hoisted and spilled) for the halves' inner products. Dims past d are
+// zero in the row (load_x64_step) and in the padded centroid copy: exact zero
+// terms. |x|^2 of a general double row needs glibc's pow(x, 2) per term
+// (gpow2.h): the row's sequential sum comes precomputed (a.xn2, row_sumsq).
+__device__ inline int cosine_winner_halves_x64(const FusedArgs& a, int64_t rowc, const double* __restrict__ crow_h,
+                                               double nbv, int h, double& v) {
+    double2 xn[4], xnn[4];
+    load_x64_step(a, rowc, 0, h, xn);
+    load_x64_step(a, rowc, 1, h, xnn);
+    double sh = 0.0, sl = 0.0, ts = 0.0;
+    double off = 0.0;                     // as cosine_winner_halves
+    double2 cb[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) cb[j] = *reinterpret_cast<const double2*>(crow_h + 2 * j);
+#pragma unroll 1
+    for (int s = 0; s < 8; s++) {
+        double xv[8], cv[8];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            xv[2 * j] = xn[j].x; xv[2 * j + 1] = xn[j].y;
+            cv[2 * j] = cb[j].x; cv[2 * j + 1] = cb[j].y;
+            xn[j] = xnn[j];
+        }
+        if (s + 2 < 8) load_x64_step(a, rowc, s + 2, h, xnn);
+        if (s + 1 < 8) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) cb[j] = *reinterpret_cast<const double2*>(crow_h + 16 * (s + 1) + 2 * j);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const double pj = __dmul_rn(xv[j], cv[j]);
+            const double t = __dadd_rn(sh, pj);
+            const double bb = __dsub_rn(t, sh);
+            const double e = __dadd_rn(__dsub_rn(sh, __dsub_rn(t, bb)), __dsub_rn(pj, bb));   // TwoSum
+            sh = t;
+            sl = __dadd_rn(sl, e);
+            ts = __dadd_rn(ts, fabs(__dadd_rn(t, off)));
+        }
+        const double other = swap_halves(sh, h);
+        if (h == 1) ts = __dadd_rn(ts, 8.0 * fabs(__dsub_rn(other, off)));
+        off = other;
+    }
+    const double sh0 = swap_halves(sh, h), sl0 = swap_halves(sl, h), ts0 = swap_halves(ts, h);
+    if (h == 0) return 2;
+    return cosine_halves_finish(sh0, sl0, ts0, sh, sl, ts, a.xn2[rowc], nbv, v);
+}
+
+// NIMG = 2 (512 < K <= 1024, euclidean): ONE launch for all centroids. The
+// LDS holds one 512-centroid image at a time; the block's waves each score
+// their tile against the image in LDS, the block swaps in the other image
+// (two barriers, 128 KB from L2), and the waves finish the same tile against
+// it with the row still in registers -- no second read of X and no carried
+// pass state. Images alternate A,B / B,A between rounds (one swap per round);
+// every wave runs the block's round count (tiles past the end: no valid rows).
+// GATH (euclidean, one pass, Kpad <= FH_GATH_KMAX): the winner rows of the
+// distance chain are gathered into a per-wave LDS ring by LDS-DMA, 8 lanes per
+// 128-B row segment (coalesced), instead of 16-B register loads from 32
+// different rows per instruction -- the vector-memory path (TA/TD/TCP) was the
+// busiest unit of the pass (TD 97 %, TA 88 % busy; 63 % of the L1 accesses
+// were these loads). Ring of two 4-KiB steps (16 dims x 32 points x 8 B).
+constexpr int FH_GATH_STEP = 32 * 16 * 8;
+constexpr int FH_GATH_WAVE = 2 * FH_GATH_STEP;
+__host__ __device__ constexpr int fh_gath_off(int Kpad, bool hash) { return (fh_lds_bytes(Kpad, hash) + 255) & ~255; }
+static_assert(fh_gath_off(FH_GATH_KMAX, true) + 8 * FH_GATH_WAVE <= 160 * 1024, "gather ring exceeds 160 KiB");
+
+// One LDS-DMA piece: each lane's 16 B at gsrc land at lds_dst + 16 * lane
+// (M0 written and restored in the same statement; the load is invisible to the
+// compiler's wait counting: the chain waits for it with an explicit vmcnt).
+__device__ inline void glds16(const void* gsrc, uint32_t lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+
+// ROWS = 0: fp32 rows of 128 dims (X); 1: fp32 rows of d <= 128 dims; 2: fp64
+// rows of d <= 128 dims (X64) -- euclidean Lloyd without hashing, one pass.
+// Dims d..127 are zero in the row and in the centroid images (the prep pads
+// them). fp64 rows: the scores use xh = f16(f32(x)); |x - f32(x)| <= 2^-24 |x|
+// joins |xr| in the bound; the winner chain re-reads the fp64 row (the
+// register copy is f32).
+// FAST (euclidean, fp32 rows; the last pass when K > 512): the certified f32 winner distance
+// compiled in (no fp64 chain state). Its f32 centroid rows are register loads:
+// through the gather ring (GATH) each 16-dim step waits on its DMA, and the
+// short f32 sum cannot hide that (fused pass 2.21 vs 2.14 ms at C3).
+template <bool HASH, bool MP = false, int MET = 0, int NIMG = 1, bool GATH = false, int ROWS = 0, bool FAST = false>
+__global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fused_hi_kernel(FusedArgs a) {
+    constexpr int FH_WAVES = fh_waves<HASH, MP, MET, FAST>();
+    constexpr int FH_THREADS = 64 * FH_WAVES;
+    static_assert(NIMG == 1 || (!MP && MET == 0), "two-image form: euclidean, single launch");
+    static_assert(!GATH || (!MP && MET == 0 && NIMG == 1 && FH_WAVES == 8), "gather ring: euclidean single pass");
+    static_assert(ROWS == 0 || (!HASH && !MP && NIMG == 1), "general rows: Lloyd without hashing, one pass");
+    // the gather's explicit vmcnt waits assume no other vector loads in the chain
+    static_assert(!(GATH && ROWS == 2), "fp64 rows re-read x in the chain: register loads of the winner rows");
+    static_assert(!FAST || (MET == 0 && ROWS != 2 && NIMG == 1 && !GATH), "fast distance: euclidean, fp32 rows");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int Kpad = a.Kpad;
+    const bool fastd = FAST || a.fast_dist != 0;
+    const int KI = NIMG == 2 ? FH_KMAX : Kpad;           // centroid rows the LDS image holds
+    int* lcount = reinterpret_cast<int*>(smem);          // [0] uncertified rows, [1] hash fix-up rows, [2] cosine declines
+    _Float16* lch = reinterpret_cast<_Float16*>(smem + 16);
+    float* lcn = reinterpret_cast<float*>(lch + KI * FU_RS);
+    _Float16* lvh = reinterpret_cast<_Float16*>(lcn + KI);
+    _Float16* lvl = lvh + 32 * FU_RS;
+    float* lpn0 = reinterpret_cast<float*>(lvl + 32 * FU_RS);
+    float* lv10 = lpn0 + 32;
+    float* lt0 = lv10 + 32;
+    int32_t* lr0 = reinterpret_cast<int32_t*>(lt0 + 32);
+
+    // image img: centroid rows [img * KI, img * KI + rows) into LDS rows 0..
+    auto load_image = [&](int img) {
+        const int r0 = img * KI, nr = NIMG == 2 && img == 1 ? Kpad - FH_KMAX : KI;
+        // FH_CU granules per thread in flight at once (a plain copy loop waited on every load)
+        constexpr int FH_CU = 8;
+        for (int e0 = 0; e0 < nr * 16; e0 += FH_THREADS * FH_CU) {
+            float4 v[FH_CU];
+#pragma unroll
+            for (int u = 0; u < FH_CU; u++) {
+                // past the end: granule 0 again (the same bytes rewritten), so neither
+                // the loads nor the stores carry a branch and the loads issue together
+                const int e = e0 + u * FH_THREADS + (int)threadIdx.x < nr * 16 ? e0 + u * FH_THREADS + (int)threadIdx.x : 0;
+                v[u] = *reinterpret_cast<const float4*>(a.Ch + (size_t)(r0 + (e >> 4)) * FU_D + (e & 15) * 8);
+            }
+#pragma unroll
+            for (int u = 0; u < FH_CU; u++) {
+                const int e = e0 + u * FH_THREADS + (int)threadIdx.x < nr * 16 ? e0 + u * FH_THREADS + (int)threadIdx.x : 0;
+                *reinterpret_cast<float4*>(lch + (e >> 4) * FU_RS + (e & 15) * 8) = v[u];
+            }
+        }
+        for (int e = threadIdx.x; e < nr; e += FH_THREADS) lcn[e] = a.cnh[r0 + e];
+    };
+    load_image(0);
+    if (threadIdx.x < 3) lcount[threadIdx.x] = 0;
+    int32_t* ambig_seg = a.ambig + (int64_t)blockIdx.x * a.seg_rows;
+    unsigned long long* hfix_seg = a.hfix + (int64_t)blockIdx.x * a.seg_rows;
+    unsigned long long* cfix_seg = a.cfix ? a.cfix + (int64_t)blockIdx.x * a.seg_rows : nullptr;
+    if (HASH) {
+        for (int e = threadIdx.x; e < 32 * 16; e += FH_THREADS) {
+            const int r = e >> 4, g = e & 15;
+            *reinterpret_cast<float4*>(lvh + r * FU_RS + g * 8) = *reinterpret_cast<const float4*>(a.Vh + r * FU_D + g * 8);
+            *reinterpret_cast<float4*>(lvl + r * FU_RS + g * 8) = *reinterpret_cast<const float4*>(a.Vl + r * FU_D + g * 8);
+        }
+        if (threadIdx.x < 32) {
+            const int f = threadIdx.x;
+            const bool on = f < a.LK;
+            // euclidean: the window in units of y = (acc + t) / w; cosine: of the
+            // inner product itself (hash_mfma.hip)
+            const double iwu = MET == 1 ? 1.0 : (double)(1.0f / a.w) * (1.0 + 0x1p-20);
+            const double tf = MET == 1 || !on ? 0.0 : fabs((double)a.tv[f]);
+            lpn0[f] = on ? (float)((FU_A1H * a.pnorm[f] * (1.0 + 0x1p-20) + FU_A2 * FU_SQRT_D) * iwu * (1.0 + 0x1p-18)) : 0.f;
+            lv10[f] = on ? (float)((FU_A2 * a.v1[f] * (1.0 + 0x1p-20) + (0x1p-40 + 0x1p-23) * tf) * iwu * (1.0 + 0x1p-18) +
+                                   0x1p-126) : 0.f;
+            lt0[f] = on && MET == 0 ? a.tv[f] : 0.f;
+            lr0[f] = on && MET == 0 ? a.rv[f] : 0;
+        }
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane & 31, h = lane >> 5;
+    const float cmaxf = a.cbound[3], crf = a.cbound[4], chf = a.cbound[5], cnf = a.cbound[6];
+    const bool c_ok = __float_as_uint(a.cbound[2]) == 0u;
+    const _Float16* my_h = lch + col * FU_RS + 8 * h;
+    const int ntile32 = Kpad >> 5;
+    const int64_t ntiles = (a.N + 31) >> 5;
+    // point-independent part of the bound
+    const double Ec = (0x1p-24 + FH_A) * (double)cnf + 0x1p-41 * (double)cmaxf * (double)cmaxf + 0x1p-18 * (double)cnf;
+
+    const int64_t tstride = (int64_t)gridDim.x * FH_WAVES, tfirst = (int64_t)blockIdx.x * FH_WAVES;
+    const int64_t nround = NIMG == 2 && ntiles > tfirst ? (ntiles - tfirst + tstride - 1) / tstride : 0;
+    int64_t rd = 0;
+    // profiling build: [0] row load + split + hash tile, [1] centroid tiles, [2] certificate + winner chain + stores
+    // this lane's 64 values of row (tile, col) in the B-operand layout (rows past
+    // the end read row N-1: their results are never stored)
+    auto load_row = [&](int64_t tl, float (&dst)[64]) {
+        if constexpr (ROWS != 0) {
+            const int64_t rr = tl * 32 + col;
+            load_row_gen<ROWS>(a, rr < a.N ? rr : a.N - 1, h, dst);
+            return;
+        }
+        const int64_t rr = tl * 32 + col;
+        const float* xr = a.X + (rr < a.N ? rr : a.N - 1) * FU_D + 8 * h;
+#pragma unroll
+        for (int s = 0; s < 8; s++) {
+            const float4 p0 = *reinterpret_cast<const float4*>(xr + 16 * s);
+            const float4 p1 = *reinterpret_cast<const float4*>(xr + 16 * s + 4);
+            dst[8 * s + 0] = p0.x; dst[8 * s + 1] = p0.y; dst[8 * s + 2] = p0.z; dst[8 * s + 3] = p0.w;
+            dst[8 * s + 4] = p1.x; dst[8 * s + 5] = p1.y; dst[8 * s + 6] = p1.z; dst[8 * s + 7] = p1.w;
+        }
+    };
+    PT_DECL
+    for (int64_t tile = tfirst + wave; NIMG == 2 ? rd < nround : tile < ntiles; tile += tstride, rd++) {
+        const int64_t row = tile * 32 + col;
+        const bool valid = row < a.N;
+        float xf[64];
+        load_row(tile, xf);
+        half8 bh[8];
+        float2v n2a = {0.f, 0.f}, n2b = {0.f, 0.f}, r2 = {0.f, 0.f};
+        // hi part of 8 values (LO: and the lo part), |x|^2 and |x - xh|^2 partial sums
+        auto split_step = [&](int s, half8& lo, auto lo_tag) {
+            split8_hi<decltype(lo_tag)::value>(xf + 8 * s, bh[s], lo, r2);
+#pragma unroll
+            for (int j = 0; j < 8; j += 4) {
+                const float2v u = {xf[8 * s + j], xf[8 * s + j + 1]}, v = {xf[8 * s + j + 2], xf[8 * s + j + 3]};
+                n2a = __builtin_elementwise_fma(u, u, n2a);
+                n2b = __builtin_elementwise_fma(v, v, n2b);
+            }
+        };
+        double xn2, nx, nxr, nxh;
+        bool x_ok;
+        auto finish_norms = [&]() {
+            float xn2f = (n2a.x + n2a.y) + (n2b.x + n2b.y);
+            float xr2f = r2.x + r2.y;
+            xn2f += __shfl_xor(xn2f, 32);
+            xr2f += __shfl_xor(xr2f, 32);
+            // f32 sums of squares inflated by 2^-16 (> d 2^-24): upper bounds
+            xn2 = (double)xn2f * (1.0 + 0x1p-16);
+            nx = sqrt(xn2);
+            nxr = sqrt((double)xr2f * (1.0 + 0x1p-16)) + 0x1p-100;
+            if (ROWS == 2) nxr += 0x1p-24 * nx * (1.0 + 0x1p-20);   // |x - f32(x)| (fp64 rows)
+            nxh = nx + nxr;                                     // |xh| <= |x| + |xr|
+            x_ok = xn2f <= FU_RANGE * FU_RANGE;
+        };
+        const bool hash_here = HASH;          // <HASH, MP>: the first pass only
+        if (!hash_here) {
+#pragma unroll
+            for (int s = 0; s < 8; s++) {
+                half8 unused;
+                split_step(s, unused, std::false_type{});
+            }
+            finish_norms();
+        }
+
+        if (hash_here) {
+            uint32_t fmask = 0;
+            float acc_hi[16];
+            {
+                const _Float16* vh_row = lvh + col * FU_RS + 8 * h;
+                const _Float16* vl_row = lvl + col * FU_RS + 8 * h;
+                // per 16-dim step: the lo products first, then the hi products into
+                // the same accumulator (16 roundings relative to the step's sum of
+                // |terms|, the lo parts' own roundings ~2^-11 smaller), steps added
+                // in f32 (+7): 23 -> 24 roundings, still inside FU_A1H; one
+                // accumulator fewer than the separate lo chain (fits 168 VGPRs)
+                floatx16 tot;
+#pragma unroll
+                for (int s = 0; s < 8; s++) {
+                    half8 bls;
+                    split_step(s, bls, std::true_type{});
+                    const half8 ah = *reinterpret_cast<const half8*>(vh_row + 16 * s);
+                    const half8 al = *reinterpret_cast<const half8*>(vl_row + 16 * s);
+                    const floatx16 z = {};
+                    floatx16 acc_s = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[s], z, 0, 0, 0);
+                    acc_s = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bls, acc_s, 0, 0, 0);
+                    acc_s = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[s], acc_s, 0, 0, 0);
+                    if (s == 0) {
+                        tot = acc_s;
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 16; r += 2) {
+                            const float2v t2 = {tot[r], tot[r + 1]}, a2 = {acc_s[r], acc_s[r + 1]};
+                            const float2v u2 = t2 + a2;
+                            tot[r] = u2.x;
+                            tot[r + 1] = u2.y;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; r++) acc_hi[r] = tot[r];
+            }
+            finish_norms();
+            // Certification in f32 (the floor only needs y to ~2^-20): with
+            // u = f32(dot~ + t), y = f32(u * f32(1/w)),
+            //   |y - (x.v + t)/w| <= (Ed + 2^-23 |u| + 2^-40 |t|) / w + 2^-21 |y|,
+            // Ed = A1 |v||x| + A2 (|v|_1 + |x|_1) + 2^-23 |dot~| (the split bound and
+            // the final hi + lo add; the reference's x87 / double-product roundings
+            // are below 2^-50 (|v||x| + |t|)). With |x|_1 <= sqrt(d) |x|, |dot~| <=
+            // |u| + |t| and |u| / w <= |y| (1 + 2^-19), that is at most
+            //   B = |y| G + |x| P_f + Q_f,   G = (2^-22 + 2^-20)(1 + 2^-18),
+            //   P_f = (A1 |v| + A2 sqrt(d)) / w,  Q_f = (A2 |v|_1 + (2^-23 + 2^-40)|t|) / w
+            // (prologue; the 1 + 2^-18 factors cover the f32 roundings of B, y - B,
+            // y + B): floor(y - B) == floor(y + B) certifies the reference's floorl.
+            // hc is an opaque zero: it keeps the per-function constants as LDS
+            // reads inside the loop instead of hoisted VGPRs.
+            const float iw = MET == 1 ? 1.f : 1.0f / a.w;
+            const float nxf = (float)nx * (1.f + 0x1p-20f);
+            constexpr float G = (0x1p-22f + 0x1p-20f) * (1.f + 0x1p-18f);
+            int hc = 0;
+            asm volatile("" : "+v"(hc));
+            const float* lt = lt0 + hc;
+            const float* lP = lpn0 + hc;
+            const float* lQ = lv10 + hc;
+            const int32_t* lr = lr0 + hc;
+            if (!x_ok && valid) fmask = (a.LK >= 32 ? 0xFFFFFFFFu : (1u << a.LK) - 1u);
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int l = 2 * g + h;
+                if (l >= a.L || !valid) continue;
+                const int64_t o = row * a.L + l;
+                if constexpr (MET == 1) {
+                    // CosineHGen: ip >= 0, certified when |acc~| exceeds the window;
+                    // CosineGGen: g = bits MSB first
+                    int gv = 0;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const int f = 4 * l + q;
+                        const float u = acc_hi[4 * g + q];
+                        const float B = fmaf(nxf, lP[f], lQ[f]);
+                        gv = (gv << 1) | (u >= 0.f ? 1 : 0);
+                        if (!(fabsf(u) > B)) fmask |= 1u << f;
+                    }
+                    if (a.phi) a.phi[o] = gv;
+                    if (a.bucket) a.bucket[o] = gv;
+                    continue;
+                }
+                int32_t hv[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int f = 4 * l + q;
+                    const float u = acc_hi[4 * g + q] + lt[f];
+                    const float y = u * iw;
+                    const float B = fmaf(fabsf(y), G, fmaf(nxf, lP[f], lQ[f]));
+                    const float lo = floorf(y - B), hi = floorf(y + B);
+                    hv[q] = (int32_t)lo;
+                    if (lo != hi) fmask |= 1u << f;
+                }
+                if (a.tuples) *reinterpret_cast<int4*>(a.tuples + o * 4) = make_int4(hv[0], hv[1], hv[2], hv[3]);
+                uint32_t hn = 0;
+#pragma unroll
+                for (int q = 0; q < 4; q++) hn += phi_term_small(hv[q], lr[4 * l + q]);
+                const uint32_t ph = phi_final(hn);
+                if (a.phi) a.phi[o] = (int32_t)ph;
+                if (a.bucket) a.bucket[o] = bucket_fast(ph, a.bdiv);
+            }
+            fmask |= __shfl_xor(fmask, 32);
+            const unsigned long long fb = __ballot(fmask != 0u && h == 1);
+            if (fb) {
+                const int leader = __builtin_ctzll(fb);
+                int base = 0;
+                if (lane == leader) base = atomicAdd(lcount + 1, __popcll(fb));
+                base = __shfl(base, leader);
+                if (fmask != 0u && h == 1)
+                    hfix_seg[base + __popcll(fb & ((1ull << lane) - 1ull))] = ((unsigned long long)row << 32) | fmask;
+            }
+        }
+
+        PT_MARK(0)
+        // the certificate's bound E depends on the row only: formed before the
+        // centroid tiles (its fp64 ops overlap the MFMAs). cosine: + 2^-43 |x| for the normalisation and the reference's own q
+        // (fused_persistent_kernel's cosine bound)
+        const double E = (nxh * (double)crf + nxr * (double)cmaxf + FH_A * nxh * (double)chf + 0x1p-41 * xn2 +
+                          0x1p-18 * nx * (double)cmaxf + (MET == 1 ? 0x1p-43 * nx : 0.0) + Ec) * (1.0 + 0x1p-20) +
+                         1e-30;
+        // ---- centroid tiles: 8 MFMAs each, accumulator initialised with -|c|^2/2
+        float m1 = -__builtin_inff(), m2 = -__builtin_inff();
+        int t1 = 0;
+        if (MP && !HASH && !a.pass_first) {
+            const float4 st = a.part[tile * 64 + lane];
+            m1 = st.x; m2 = st.y; t1 = __float_as_int(st.z);
+        }
+        const int tg0 = MP ? a.t0 : 0;
+        __builtin_amdgcn_s_setprio(MFMA_PRIO);
+        const int ntile_run = ntile32;
+        auto run_tiles = [&](int ntl, int tgo) {
+#pragma unroll 1
+            for (int t = 0; t < ntl; t++) {
+                const float m1_prev = m1;
+                floatx16 acc;
+                const float* cn_t = lcn + t * 32 + 4 * h;     // D rows 8g + 4h + q of registers 4g + q
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const float4 cn = *reinterpret_cast<const float4*>(cn_t + 8 * g);
+                    acc[4 * g] = cn.x; acc[4 * g + 1] = cn.y; acc[4 * g + 2] = cn.z; acc[4 * g + 3] = cn.w;
+                }
+                const _Float16* arow = my_h + t * 32 * FU_RS;
+#pragma unroll
+                for (int s = 0; s < 8; s++) {
+                    const half8 ah = *reinterpret_cast<const half8*>(arow + 16 * s);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[s], acc, 0, 0, 0);
+                }
+                float sv[16];
+#pragma unroll
+                for (int r = 0; r < 16; r++) sv[r] = acc[r];
+                tile_epilogue(sv, m1, m2);
+                t1 = m1 != m1_prev ? t + tgo : t1;
+            }
+        };
+        if (NIMG == 1) {
+            run_tiles(ntile_run, tg0);
+        } else {
+            // the image in LDS at this round's start, then the other one
+            const int i0 = (int)(rd & 1);
+            const int nA = FH_KMAX / 32, nB = (Kpad - FH_KMAX) / 32;
+            run_tiles(i0 == 0 ? nA : nB, i0 * nA);
+            __syncthreads();
+            load_image(1 - i0);
+            __syncthreads();
+            run_tiles(i0 == 0 ? nB : nA, (1 - i0) * nA);
+        }
+        __builtin_amdgcn_s_setprio(0);
+        PT_MARK(1)
+        // <HASH, MP> launches only the first of several passes (never the last)
+        if (MP && (HASH || !a.pass_last)) {
+            a.part[tile * 64 + lane] = make_float4(m1, m2, __int_as_float(t1), 0.f);
+            continue;
+        }
+        const uint32_t l1 = __float_as_uint(m1) & 0xFu;
+        const int i1 = t1 * 32 + 8 * (int)(l1 >> 2) + 4 * h + (int)(l1 & 3u);
+        const float om1 = __shfl_xor(m1, 32), om2 = __shfl_xor(m2, 32);
+        const int oi1 = __shfl_xor(i1, 32);
+        const float M2 = fmaxf(fmaxf(m2, om2), fminf(m1, om1));
+        const int I1 = (om1 > m1 || (om1 == m1 && oi1 < i1)) ? oi1 : i1;
+        const float M1 = fmaxf(m1, om1);
+        // the winner's fp64 row: the first loads go out before the certificate
+        // and the list append
+        const double* crow = a.C64 + (size_t)I1 * FU_D + 8 * h;
+        // GATH: piece u of a step holds points 8u..8u+7, lane L the 16-B chunk
+        // (L & 7) ^ swz(p) of point p = 8u + (L >> 3) (swz(p) = (p >> 1) & 7: the
+        // lanes of each ds_read_b128 group hit 16 distinct 4-bank groups).
+        // g32 (every centroid value is an f32, e.g. dataset rows: the prep's
+        // cbound[7] == 0): the f32 image C32 instead, exact as doubles -- half the
+        // bytes and two pieces per step: piece u holds points 16u..16u+15, lane L
+        // the 16-B chunk (L & 3) ^ swz32(p) of point p = 16u + (L >> 2), swz32(p) =
+        // (p >> 2) & 3 (the 16 lanes of a ds_read_b128 group on distinct banks).
+        const char* gsrc[4];
+        uint32_t gbase = 0;
+        const bool g32 = GATH && a.C32 != nullptr && (__float_as_uint(a.cbound[7]) & 1u) == 0u;
+        const int gstep = g32 ? 64 : 128;                // bytes of one 16-dim step of a row
+        if (GATH && !fastd) {
+            gbase = (uint32_t)__builtin_amdgcn_readfirstlane(
+                (int)((uint32_t)(uintptr_t)(smem + fh_gath_off(Kpad, HASH)) + (uint32_t)wave * FH_GATH_WAVE));
+            if (g32) {
+#pragma unroll
+                for (int u = 0; u < 2; u++) {
+                    const int p = 16 * u + (lane >> 2);
+                    const int Ip = __shfl(I1, p);
+                    gsrc[u] = reinterpret_cast<const char*>(a.C32 + (size_t)Ip * FU_D + 4 * ((lane & 3) ^ ((p >> 2) & 3)));
+                }
+                gsrc[2] = gsrc[3] = gsrc[0];
+#pragma unroll
+                for (int s0 = 0; s0 < 2; s0++)
+#pragma unroll
+                    for (int u = 0; u < 2; u++) glds16(gsrc[u] + gstep * s0, gbase + s0 * FH_GATH_STEP + u * 1024);
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int p = 8 * u + (lane >> 3);
+                    const int Ip = __shfl(I1, p);
+                    gsrc[u] = reinterpret_cast<const char*>(a.C64 + (size_t)Ip * FU_D + 2 * ((lane & 7) ^ ((p >> 1) & 7)));
+                }
+#pragma unroll
+                for (int s0 = 0; s0 < 2; s0++)
+#pragma unroll
+                    for (int u = 0; u < 4; u++) glds16(gsrc[u] + gstep * s0, gbase + s0 * FH_GATH_STEP + u * 1024);
+            }
+        }
+        // GATH: a step's values come from the ring one step early (the LDS read
+        // overlaps the previous step's chain), the ring slot is refilled two
+        // steps ahead as soon as it is read
+        double2 gnext[4];
+        float4 gnext32[2];                    // g32: raw f32 chunks, widened when used
+        auto gread = [&](int st) {
+            const char* ring = smem + fh_gath_off(Kpad, HASH) + wave * FH_GATH_WAVE + (st & 1) * FH_GATH_STEP;
+            if (g32) {
+#pragma unroll
+                for (int j = 0; j < 2; j++)
+                    gnext32[j] = *reinterpret_cast<const float4*>(ring + (col >> 4) * 1024 + (col & 15) * 64 +
+                                                                  16 * ((2 * h + j) ^ ((col >> 2) & 3)));
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    gnext[j] = *reinterpret_cast<const double2*>(ring + col * 128 + 16 * ((4 * h + j) ^ ((col >> 1) & 7)));
+            }
+        };
+        // vmcnt(n): all but the wave's n youngest vector-memory operations done
+        // (one step's pieces: 2 for g32, else 4)
+        auto wait_step = [&]() {
+            if (g32) __builtin_amdgcn_s_waitcnt(0x0F72);                   // vmcnt(2)
+            else __builtin_amdgcn_s_waitcnt(0x0F74);                       // vmcnt(4)
+        };
+        // ring step s consumed: slot s & 1 refilled with step s + 2, step s + 1 read
+        auto ring_advance = [&](int s) {
+            if (s + 2 < 8) {
+                __builtin_amdgcn_s_waitcnt(0xC07F);                        // lgkmcnt(0): slot s & 1 is read
+                asm volatile("" ::: "memory");
+                if (g32) {
+#pragma unroll
+                    for (int u = 0; u < 2; u++) glds16(gsrc[u] + gstep * (s + 2), gbase + (s & 1) * FH_GATH_STEP + u * 1024);
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 4; u++) glds16(gsrc[u] + gstep * (s + 2), gbase + (s & 1) * FH_GATH_STEP + u * 1024);
+                }
+            }
+            if (s + 1 < 8) {
+                if (s + 2 < 8) wait_step();                                // step s + 1 landed
+                else __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0)
+                asm volatile("" ::: "memory");
+                gread(s + 1);
+            }
+        };
+        // fp64 rows: the chain's x values re-read (mostly L2) four 16-dim steps
+        // ahead (one step ahead left the chain waiting ~8 round trips per tile)
+        constexpr int XD = 4;
+        double2 xring[XD][4];
+        const int64_t rowc = row < a.N ? row : a.N - 1;
+        if constexpr (ROWS == 2 && MET == 0) {
+#pragma unroll
+            for (int st = 0; st < XD; st++) load_x64_step(a, rowc, st, h, xring[st]);
+        }
+        // the winner's fp64 row, one 16-dim step ahead of the chain (deeper
+        // prefetch measured slower: DESIGN.md)
+        double2 cbuf[4];
+        if (MET == 0 && !GATH && !fastd) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) cbuf[j] = *reinterpret_cast<const double2*>(crow + 2 * j);
+        }
+        const bool cert = x_ok && c_ok && ((double)M2 < (double)M1 - 2.0 * E);
+
+        // euclidean fast distance (fastd): the winner's distance from f32(c)
+        // in f32 with every lane busy, certified to 2^-20 relative (DESIGN.md §5:
+        // 8 accumulators per lane, <= 12 roundings per sum, plus the f32(c)
+        // residual |c - f32(c)| of the centroid); a row whose bound fails is
+        // refined like an uncertified argmin (the exact chain of the refinement)
+        bool dok = true;
+        double fdist = 0.0;
+        if constexpr (MET == 0) {
+            if (fastd) {
+                const float* c32 = a.C32 + (size_t)I1 * FU_D + 8 * h;
+                float2v q[4] = {};
+#pragma unroll
+                for (int s = 0; s < 8; s++) {
+                    const float4 c0 = *reinterpret_cast<const float4*>(c32 + 16 * s);
+                    const float4 c1 = *reinterpret_cast<const float4*>(c32 + 16 * s + 4);
+                    const float2v cv[4] = {{c0.x, c0.y}, {c0.z, c0.w}, {c1.x, c1.y}, {c1.z, c1.w}};
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const float2v xv = {xf[8 * s + 2 * j], xf[8 * s + 2 * j + 1]};
+                        const float2v dv = xv - cv[j];
+                        q[j] = __builtin_elementwise_fma(dv, dv, q[j]);
+                    }
+                }
+                float t = ((q[0].x + q[0].y) + (q[1].x + q[1].y)) + ((q[2].x + q[2].y) + (q[3].x + q[3].y));
+                t = t + swap_halves_f(t, h);
+                const double S = (double)t, R = (double)a.rn32[I1];
+                const double B = 14.2 * 0x1p-24 * S + 2.02 * R * sqrt(S) + 2.02 * R * R + 0x1p-100;
+                dok = B <= 0x1p-19 * S;                   // false for inf / nan
+                fdist = sqrt(S);
+            }
+        }
+        const bool amb = valid && !(cert && dok);
+        const unsigned long long amask = __ballot(amb && h == 1);
+        if (amb && h == 1) {
+            int base = 0;
+            const int leader = __builtin_ctzll(amask);
+            if (lane == leader) base = atomicAdd(lcount, __popcll(amask));
+            base = __shfl(base, leader);
+            ambig_seg[base + __popcll(amask & ((1ull << lane) - 1ull))] = (int32_t)row;
+        }
+        if constexpr (MET == 1) {
+            // cosine winner from the row in registers, both lane halves busy;
+            // declined certificates -> the fix-up list
+            bool fix = false;
+            if (valid && cert) {                          // the same on both halves of a point
+                double v = 0.0;
+                int st;
+                // fp32 rows (ROWS = 0 / 1): the values in registers are exact (zero
+                // past d, as the padded centroid copy); fp64 rows re-read
+                if constexpr (ROWS == 2) st = cosine_winner_halves_x64(a, row, a.C64 + (size_t)I1 * FU_D + 8 * h, a.nbv[I1], h, v);
+                else st = cosine_winner_halves(xf, a.C64 + (size_t)I1 * FU_D + 8 * h, a.nbv[I1], h, v);
+                if (h == 1) {
+                    a.assign[row] = I1;
+                    if (st == 0) a.dist[row] = v;
+                    else fix = true;
+                }
+            }
+            const unsigned long long fb = __ballot(fix);
+            if (fb) {
+                const int leader = __builtin_ctzll(fb);
+                int base = 0;
+                if (lane == leader) base = atomicAdd(lcount + 2, __popcll(fb));
+                base = __shfl(base, leader);
+                if (fix) cfix_seg[base + __popcll(fb & ((1ull << lane) - 1ull))] = (unsigned long long)row;
+            }
+        } else if (fastd) {
+            if (h == 1 && valid && cert && dok) {
+                a.assign[row] = I1;
+                a.dist[row] = fdist;
+            }
+        } else {
+            // winner distance in reference order from the row kept in registers:
+            // the lane halves take turns on the chain, 8 dims each
+            __builtin_amdgcn_s_setprio(CHAIN_PRIO);
+            double acc = 0.0;
+            PwAcc pw;
+            // fp64 rows: glibc's pow in the chain itself when the launch gave the
+            // LDS for it (gp_sq_wave; every difference of general doubles has
+            // more than 26 bits, so the PwAcc test would list every row)
+            double* pwl = nullptr;
+            if constexpr (ROWS == 2) {
+                if (a.pw_lds) pwl = reinterpret_cast<double*>(smem + a.pw_lds) + wave * 512;
+            }
+            if constexpr (GATH) {
+                wait_step();                                               // step 0 landed
+                asm volatile("" ::: "memory");
+                gread(0);
+            }
+#pragma unroll
+            for (int s = 0; s < 8; s++) {
+                double sq[8];
+                double2 cur[4];
+                if constexpr (GATH) {
+                    if (g32) {
+#pragma unroll
+                        for (int j = 0; j < 2; j++) {
+                            cur[2 * j] = make_double2((double)gnext32[j].x, (double)gnext32[j].y);
+                            cur[2 * j + 1] = make_double2((double)gnext32[j].z, (double)gnext32[j].w);
+                        }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; j++) cur[j] = gnext[j];
+                    }
+                    ring_advance(s);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) cur[j] = cbuf[j];
+                    if (s + 1 < 8) {
+#pragma unroll
+                        for (int j = 0; j < 4; j++) cbuf[j] = *reinterpret_cast<const double2*>(crow + 16 * (s + 1) + 2 * j);
+                    }
+                }
+                double2 xcur[4];
+                if constexpr (ROWS == 2) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) xcur[j] = xring[s % XD][j];
+                    if (s + XD < 8) load_x64_step(a, rowc, s + XD, h, xring[s % XD]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) xcur[j] = make_double2((double)xf[8 * s + 2 * j], (double)xf[8 * s + 2 * j + 1]);
+                }
+                double dv[8];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const double2 cc = cur[j];
+                    dv[2 * j] = __dsub_rn(xcur[j].x, cc.x);
+                    dv[2 * j + 1] = __dsub_rn(xcur[j].y, cc.y);
+                }
+                if (ROWS == 2 && pwl) {
+                    gp_sq_wave<8>(dv, sq, pwl);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        sq[j] = __dmul_rn(dv[j], dv[j]);
+                        // the reference squares with glibc pow: x*x is its value when
+                        // the square is exact; otherwise the row's distance is redone
+                        // by the fix-up (gpow2.h PwAcc: differences of <= 26 bits, and
+                        // for fp64 rows no tiny ones)
+                        pw.add<ROWS == 2>(dv[j]);
+                    }
+                }
+                if (h == 0) {
+#pragma unroll
+                    for (int j = 0; j < 8; j++) acc = __dadd_rn(acc, sq[j]);
+                }
+                acc = take_from_lower(acc);
+                if (h == 1) {
+#pragma unroll
+                    for (int j = 0; j < 8; j++) acc = __dadd_rn(acc, sq[j]);
+                }
+                acc = take_from_upper(acc);
+            }
+            // fp32 rows: a difference 0 < |x - c| < 2^-460 needs such a centroid
+            // value (x has >= 2^-149 magnitude or is zero), flagged by the prep
+            const bool pw_hard = pwl == nullptr && (pw.hard() || (ROWS != 2 && (__float_as_uint(a.cbound[7]) & 2u) != 0u));
+            // the shuffle outside the ||: evaluated only where pw_hard is false, it
+            // would read the other half's lane while that lane is masked off
+            const int pw_other = __shfl_xor((int)pw_hard, 32);
+            const bool hard = pw_hard || pw_other != 0;
+            if (h == 1 && valid && cert) {
+                a.assign[row] = I1;
+                if (!hard) a.dist[row] = sqrt(acc);
+            }
+            // the pow fix-up list (cfix, counts in slot 2): certified winners
+            // whose chain met an inexact square
+            const unsigned long long pb = __ballot(h == 1 && valid && cert && hard);
+            if (pb) {
+                const int leader = __builtin_ctzll(pb);
+                int base = 0;
+                if (lane == leader) base = atomicAdd(lcount + 2, __popcll(pb));
+                base = __shfl(base, leader);
+                if (h == 1 && valid && cert && hard) cfix_seg[base + __popcll(pb & ((1ull << lane) - 1ull))] = (unsigned long long)row;
+            }
+            __builtin_amdgcn_s_setprio(0);
+        }
+        PT_MARK(2)
+    }
+    PT_FLUSH
+    __syncthreads();
+    if (threadIdx.x < 2 && (!MP || (threadIdx.x == 0 ? (!HASH && a.pass_last != 0) : (HASH && a.pass_first)))) {
+        const int c = lcount[threadIdx.x];
+        a.seg_counts[2 * blockIdx.x + threadIdx.x] = c;
+        if (c) atomicAdd(threadIdx.x == 0 ? a.ambig_count : a.hfix_count, (unsigned long long)c);
+    }
+    // slot 2: cosine declines / euclidean pow fix-ups (exact distances)
+    if ((MET == 1 || !fastd) && threadIdx.x == 2 && (!MP || (!HASH && a.pass_last))) {
+        const int c = lcount[2];
+        a.cfix_counts[2 * blockIdx.x + 1] = c;
+        if (c) atomicAdd(a.cfix_count, (unsigned long long)c);
+    }
+}
+
+template <bool HASH, bool MP, int MET, int NIMG, bool GATH, int ROWS, bool FAST>
+static void hi_launch(hipStream_t s, unsigned nblk, size_t lds, const FusedArgs& a) {
+    hipLaunchKernelGGL((fused_hi_kernel<HASH, MP, MET, NIMG, GATH, ROWS, FAST>), dim3(nblk),
+                       dim3(64 * fh_waves<HASH, MP, MET, FAST>()), lds, s, a);
+}
+
+int launch_fused_hi_pass(hipStream_t s, unsigned nblk, const HiForm& f, FusedArgs a) {
+    // LDS: the image (+ the hash rows), then the gather ring or the fp64 chain's pow buffers
+    size_t lds = (size_t)fh_lds_bytes(f.two_image ? FH_KMAX : a.Kpad, f.hash);
+    a.pw_lds = 0;
+    if (f.gath) {
+        if (a.Kpad > FH_GATH_KMAX) {
+            set_error("launch_fused_hi_pass: the gather ring needs K <= 256");
+            return -1;
+        }
+        lds = (size_t)fh_gath_off(a.Kpad, f.hash) + 8 * FH_GATH_WAVE;
+    } else if (f.rows == 2 && f.metric == 0) {
+        // the chain's pow buffers after the image when they fit (Kpad <= 448)
+        constexpr int PW_BYTES = fh_waves<false, false, 0>() * 512 * 8;
+        const size_t off = (lds + 255) & ~(size_t)255;
+        if (off + PW_BYTES <= 160 * 1024) {
+            a.pw_lds = (int)off;
+            lds = off + PW_BYTES;
+        }
+    }
+    const int nimg = f.two_image ? 2 : 1;
+    // every instantiation the library builds, one line each
+#define HI_CASE(H, MP, MET, NIMG, GATH, ROWS, FAST)                                                         \
+    if (f.hash == (bool)H && f.mp == (bool)MP && f.metric == MET && nimg == NIMG && f.gath == (bool)GATH && \
+        f.rows == ROWS && f.fast == (bool)FAST) {                                                           \
+        hi_launch<H, MP, MET, NIMG, GATH, ROWS, FAST>(s, nblk, lds, a);                                     \
+        return 0;                                                                                           \
+    }
+    //      hash mp met nimg gath rows fast
+    HI_CASE(1, 0, 0, 1, 0, 0, 1)      // euclidean, fp32 d = 128, one pass: the certified f32 distance,
+    HI_CASE(0, 0, 0, 1, 0, 0, 1)
+    HI_CASE(1, 0, 0, 1, 1, 0, 0)      // the exact chain through the gather ring,
+    HI_CASE(0, 0, 0, 1, 1, 0, 0)
+    HI_CASE(1, 0, 0, 1, 0, 0, 0)      // or by register loads (K > 256; tests)
+    HI_CASE(0, 0, 0, 1, 0, 0, 0)
+    HI_CASE(1, 1, 0, 1, 0, 0, 0)      // K > 512: the first pass hashes,
+    HI_CASE(0, 1, 0, 1, 0, 0, 1)      // the last one may compile the f32 distance in
+    HI_CASE(0, 1, 0, 1, 0, 0, 0)
+    HI_CASE(1, 0, 0, 2, 0, 0, 0)      // two-image form (tests)
+    HI_CASE(0, 0, 0, 2, 0, 0, 0)
+    HI_CASE(1, 0, 1, 1, 0, 0, 0)      // cosine
+    HI_CASE(0, 0, 1, 1, 0, 0, 0)
+    HI_CASE(1, 1, 1, 1, 0, 0, 0)
+    HI_CASE(0, 1, 1, 1, 0, 0, 0)
+    HI_CASE(0, 0, 0, 1, 0, 1, 1)      // general rows: fp32 d <= 128
+    HI_CASE(0, 0, 0, 1, 1, 1, 0)
+    HI_CASE(0, 0, 0, 1, 0, 1, 0)
+    HI_CASE(0, 0, 1, 1, 0, 1, 0)
+    HI_CASE(0, 0, 0, 1, 0, 2, 0)      // general rows: fp64 d <= 128
+    HI_CASE(0, 0, 1, 1, 0, 2, 0)
+#undef HI_CASE
+    set_error("launch_fused_hi_pass: no kernel was built for this form");
+    return -1;
+}
+
+}  // namespace lshkm

@@ -1,0 +1,531 @@
+// fused_small.hip — the small kernels around the fused pass (fused.hip): the
+// centroid preparation, the hash fix-up, the winners' distance fix-up and the
+// fp64 rows' sums of squares, each with its launcher.
+#include "fused_impl.h"
+
+namespace lshkm {
+
+// Rows listed by the fused pass with an uncertified floor (euclidean) or sign
+// (cosine): fix-up pass. Four lanes per listed row, each holding 32 contiguous
+// dims and 8 of the row's tuples (or 2 of its g values); the next row of the
+// group is loaded while the current one is computed, and the projections and
+// per-function constants sit in LDS, so the only global latency per row is
+// the prefetched one. The fp64 products are summed per lane and then across the
+// 4 lanes: hash.hip's bound covers any summation order of the 128 products
+// (depth 34 < 130); the soft-x87 fallback keeps the reference order.
+constexpr int HF_WAVES = 4;
+constexpr int HF_SPLIT = 4;                           // blocks per list segment
+constexpr int HF_G = 4;                               // lanes per listed row
+constexpr int HF_SLOTS = 64 * HF_WAVES / HF_G;        // rows per block pass
+// LDS image of the projections (fp64): dim r at (r / 32) * HF_QS + (r % 32) *
+// HF_PS; the quarters skewed by 8 words so that the 4 lanes of a row, reading
+// dim 32q + j of the same function, hit different banks (LK <= 32)
+constexpr int HF_PS = 33;
+constexpr int HF_QS = 32 * HF_PS + 8;
+constexpr size_t HF_LDS = (size_t)4 * HF_QS * 8 + 32 * (8 + 8 + 4);
+__device__ inline int hf_pidx(int r) { return (r >> 5) * HF_QS + (r & 31) * HF_PS; }
+
+// lane ^ 1 / lane ^ 2 within each quad by DPP quad_perm (VALU moves)
+template <int CTRL>
+__device__ inline uint32_t quad_swap(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, false);
+}
+template <int CTRL>
+__device__ inline double quad_swap(double v) {
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    const uint64_t lo = quad_swap<CTRL>((uint32_t)b), hi = quad_swap<CTRL>((uint32_t)(b >> 32));
+    return __longlong_as_double((long long)((hi << 32) | lo));
+}
+constexpr int QP_X1 = 0xB1, QP_X2 = 0x4E;   // quad_perm [1,0,3,2], [2,3,0,1]
+// sum over the 4 lanes of a row group (a quad, all active together); every
+// lane gets the same value ((v0 + v1) + (v2 + v3) in any lane's operand order)
+__device__ inline double group4_sum(double v) {
+    v += quad_swap<QP_X1>(v);
+    v += quad_swap<QP_X2>(v);
+    return v;
+}
+__device__ inline uint32_t group4_sum(uint32_t v) {
+    v += quad_swap<QP_X1>(v);
+    v += quad_swap<QP_X2>(v);
+    return v;
+}
+
+// the rare sequential fallbacks, out of line (their registers would lower the
+// occupancy of the whole kernel)
+__device__ __noinline__ int32_t fixup_floor_x87(const float* xrow, const double* pts, int f, double tt, float w) {
+    sx80 sxs = sx_zero();
+    for (int j = 0; j < FU_D; j++) sxs = sx_add_double(sxs, __dmul_rn(pts[hf_pidx(j) + f], (double)xrow[j]));
+    sxs = sx_add_double(sxs, tt);
+    return (int32_t)sx_floor_i64(sx_div(sxs, sx_from_float(w)));
+}
+__device__ __noinline__ int fixup_sign_x87(const float* xrow, const double* pts, int f) {
+    SxSum sx;
+    sx.init();
+    for (int j = 0; j < FU_D; j++) sx.add(__dmul_rn(pts[hf_pidx(j) + f], (double)xrow[j]));
+    return sx_hash_sign(sx);
+}
+
+// One listed row as the group's lane q holds it.
+struct FixRow {
+    int64_t row;
+    uint32_t mask;
+    float x[32];       // dims [32q, 32q + 32)
+    int32_t v[8];      // euclidean: tuples [8q, 8q + 8); cosine: g of tables 2q, 2q + 1
+};
+
+template <bool COS>
+__device__ inline void fix_load(const FusedArgs& a, unsigned long long ent, int q, FixRow& r) {
+    r.row = (int64_t)(ent >> 32);
+    r.mask = (uint32_t)ent;
+    const float* xq = a.X + r.row * FU_D + 32 * q;
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+        const float4 v = *reinterpret_cast<const float4*>(xq + 4 * u);
+        r.x[4 * u] = v.x; r.x[4 * u + 1] = v.y; r.x[4 * u + 2] = v.z; r.x[4 * u + 3] = v.w;
+    }
+    // unconditional loads (clamped indices; the extra values are never used):
+    // a load under a branch makes the compiler wait for it at the merge
+    if (COS) {
+        const int32_t* g = (a.bucket ? a.bucket : a.phi) + r.row * a.L;
+#pragma unroll
+        for (int i = 0; i < 2; i++) r.v[i] = g[min(2 * q + i, a.L - 1)];
+    } else {
+        const int32_t* t = a.tuples + r.row * a.LK;
+#pragma unroll
+        for (int i = 0; i < 8; i++) r.v[i] = t[min(8 * q + i, a.LK - 1)];
+    }
+}
+
+template <bool COS>
+__device__ inline void fix_row(const FusedArgs& a, const double* pts, const double* cpn, const double* ctt,
+                               const int32_t* crv, int q, FixRow& r) {
+    // four independent accumulators per lane (the fp64 FMA chains of 32 left the
+    // waves issue-stalled on their dependencies, 39 % of their cycles): nx only
+    // bounds, and the dot product's bound covers any summation order (depth 12 here)
+    double xq[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < 32; j++) xq[j & 3] = fma((double)r.x[j], (double)r.x[j], xq[j & 3]);
+    const double nx = sqrt(group4_sum((xq[0] + xq[1]) + (xq[2] + xq[3])));
+    const float* xrow = a.X + r.row * FU_D;
+    const int k = a.k;
+    const double iwd = 1.0 / (double)a.w;
+    for (uint32_t m = r.mask; m; m &= m - 1) {
+        const int f = __builtin_ctz(m);
+        const double* pq = pts + q * HF_QS + f;
+        // keep the fp64 widening inside the loop (hoisted, it holds 64 VGPRs)
+#pragma unroll
+        for (int j = 0; j < 32; j++) asm volatile("" : "+v"(r.x[j]));
+        double aq[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < 32; j++) aq[j & 3] = fma(pq[j * HF_PS], (double)r.x[j], aq[j & 3]);
+        const double acc = group4_sum((aq[0] + aq[1]) + (aq[2] + aq[3]));
+        const double P = cpn[f] * nx * (1.0 + 0x1p-40);
+        if (COS) {
+            const double B = (double)(FU_D + 3) * 0x1p-52 * P + 0x1p-1000;
+            int bit;
+            if (acc > B && acc < 0x1p1000) bit = 1;
+            else if (acc < -B && acc > -0x1p1000) bit = 0;
+            else {                                   // the same decision in all 4 lanes
+                bit = fixup_sign_x87(xrow, pts, f);
+                if (q == 0) atomicAdd(a.stats + STAT_HASH_EXACT, 1ull);
+            }
+            // g = bits MSB first (CosineGGen): function l*k + i is bit k-1-i of table l
+            const int l = f / k, b = 1 << (k - 1 - (f - l * k));
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+                if (l == 2 * q + i) r.v[i] = bit ? (r.v[i] | b) : (r.v[i] & ~b);
+        } else {
+            // y by the reciprocal (iw = RN(1/w)): three roundings of 2^-53 each
+            // relative, inside the |y| 2^-50 term
+            const double tt = ctt[f], iw = iwd;
+            const double y = (acc + tt) * iw;
+            const double B = ((double)(FU_D + 2) * 0x1p-52 * (P + fabs(tt))) * (iw * (1.0 + 0x1p-50)) +
+                             fabs(y) * 0x1p-50;
+            const double lo = floor(y - B), hi = floor(y + B);
+            int32_t hv = (int32_t)lo;
+            if (lo != hi) {                          // the same decision in all 4 lanes
+                hv = fixup_floor_x87(xrow, pts, f, tt, a.w);
+                if (q == 0) atomicAdd(a.stats + STAT_HASH_EXACT, 1ull);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; i++) r.v[i] = f == 8 * q + i ? hv : r.v[i];
+            if ((f >> 3) == q) a.tuples[r.row * a.LK + f] = hv;
+        }
+    }
+    const uint32_t kmask = k >= 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
+    if (COS) {
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int l = 2 * q + i;
+            if (l < a.L && (r.mask & (kmask << (l * k)))) {
+                if (a.phi) a.phi[r.row * a.L + l] = r.v[i];
+                if (a.bucket) a.bucket[r.row * a.L + l] = r.v[i];
+            }
+        }
+        return;
+    }
+    // touched tables: phi from the lanes' partial sums of the phi terms (the
+    // uint32 sum wraps the same in any order)
+    uint32_t term[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) term[i] = 8 * q + i < a.LK ? phi_term(r.v[i], crv[8 * q + i]) : 0u;
+    for (int l = 0; l < a.L; l++) {
+        if (!(r.mask & (kmask << (l * k)))) continue;                // the same in all 4 lanes
+        uint32_t hn = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int f = 8 * q + i;
+            hn += f >= l * k && f < l * k + k ? term[i] : 0u;
+        }
+        hn = group4_sum(hn);
+        if (q == 0) {
+            const uint32_t ph = phi_final(hn);
+            if (a.phi) a.phi[r.row * a.L + l] = (int32_t)ph;
+            if (a.bucket) a.bucket[r.row * a.L + l] = bucket_fast(ph, a.bdiv);
+        }
+    }
+}
+
+template <bool COS>
+__global__ __launch_bounds__(64 * HF_WAVES) void hash_fixup_kernel(FusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* pts = reinterpret_cast<double*>(smem);   // skewed [128][32]
+    double* cpn = pts + 4 * HF_QS;                   // [32] |p_f| (rounded up)
+    double* ctt = cpn + 32;                          // [32] t_f
+    int32_t* crv = reinterpret_cast<int32_t*>(ctt + 32);   // [32] r_f
+    const int nseg = gridDim.x / HF_SPLIT;       // segments across XCDs (cos_fix_seg_kernel)
+    const int seg = blockIdx.x % nseg, part = blockIdx.x / nseg;
+    const int n = a.seg_counts[2 * seg + 1];
+    if (n == 0) return;                                                 // block-uniform
+    const unsigned long long* list = a.hfix + (int64_t)seg * a.seg_rows;
+    const int LK = a.LK, LKpad = a.LKpad;
+#pragma unroll
+    for (int e = threadIdx.x; e < FU_D * 32; e += 64 * HF_WAVES) {
+        const int r = e >> 5, f = e & 31;
+        pts[hf_pidx(r) + f] = f < LK ? a.PT[r * LKpad + f] : 0.0;
+    }
+    if (threadIdx.x < 32) {
+        const int f = threadIdx.x;
+        cpn[f] = f < LK ? a.pnorm[f] : 0.0;
+        ctt[f] = !COS && f < LK ? (double)a.tv[f] : 0.0;
+        crv[f] = !COS && f < LK ? a.rv[f] : 0;
+    }
+    __syncthreads();
+    const int q = threadIdx.x & (HF_G - 1), slot = threadIdx.x / HF_G;
+    constexpr int STRIDE = HF_SPLIT * HF_SLOTS;
+    int e = part * HF_SLOTS + slot;
+    if (e >= n) return;                                                 // whole groups
+    // software pipeline: the next row (and the list entry after it) load while
+    // the current one is computed; past the end the last entry is re-loaded
+    FixRow cur, nxt;
+    fix_load<COS>(a, list[e], q, cur);
+    unsigned long long ent2 = list[min(e + STRIDE, n - 1)];
+    for (; e < n; e += STRIDE) {
+        fix_load<COS>(a, ent2, q, nxt);
+        ent2 = list[min(e + 2 * STRIDE, n - 1)];
+        fix_row<COS>(a, pts, cpn, ctt, crv, q, cur);
+        cur = nxt;
+    }
+}
+
+void launch_hash_fixup(hipStream_t s, unsigned nseg, bool cosine, const FusedArgs& a) {
+    const dim3 grid(nseg * HF_SPLIT), block(64 * HF_WAVES);
+    if (cosine) hipLaunchKernelGGL(hash_fixup_kernel<true>, grid, block, HF_LDS, s, a);
+    else hipLaunchKernelGGL(hash_fixup_kernel<false>, grid, block, HF_LDS, s, a);
+}
+
+// ------------------------------------------------------------------ preparation
+// Centroids -> f16 hi/lo rows, -||c||^2/2, and the per-call bound maxima.
+constexpr int FP_PREP_WAVES = 8;     // centroids per prep block (Kpad % 64 == 0)
+// d < 128: the rows are zero-padded to 128 dims (C64p: the padded fp64 copy the
+// winner chains read; a zero dim adds (0 - 0)^2 = +0 to a non-negative chain).
+__global__ void fused_centroid_prep(const double* __restrict__ C, int K, int Kpad, _Float16* __restrict__ Ch,
+                                    _Float16* __restrict__ Cl, float* __restrict__ cnh, unsigned int* __restrict__ cb,
+                                    int metric, double* __restrict__ nbv, float* __restrict__ C32,
+                                    float* __restrict__ rn32, int d, double* __restrict__ C64p) {
+    const int c = blockIdx.x * FP_PREP_WAVES + (threadIdx.x >> 6);   // one wave per centroid row
+    const int lane = threadIdx.x & 63;
+    double s2 = 0.0, s1 = 0.0;
+    bool bad = false;
+    double scale = 1.0;                  // cosine: the row is normalised (score x.c/|c|)
+    if (metric == 1) {
+        double q = 0.0;
+        for (int j = lane; j < FU_D; j += 64) {
+            const double v = c < K && j < d ? C[(size_t)c * d + j] : 0.0;
+            q = fma(v, v, q);
+        }
+        for (int off = 32; off >= 1; off >>= 1) q += __shfl_xor(q, off);
+        // zero / extreme-norm centroids (the reference's NaN for a zero vector,
+        // assignment.hpp:66) leave the call uncertified: every row goes exact
+        if (c < K && !(q >= 1e-200 && q <= 1e200)) bad = true;
+        scale = (q >= 1e-200 && q <= 1e200) ? 1.0 / sqrt(q) : 0.0;
+        if (lane == 0 && c < K) {
+            double b = 0.0;
+            for (int j = 0; j < d; j++) {
+                const double cj = C[(size_t)c * d + j];
+                b = __dadd_rn(b, gp_sq(cj));
+            }
+            nbv[c] = b;
+        }
+    }
+    bool not32 = false;                  // some value of the row is not an f32 (cbound[7] bit 0)
+    bool tiny = false;                   // some 0 < |c_j| < 2^-460 (cbound[7] bit 1: PwAcc)
+    double rr = 0.0, hh = 0.0;           // |c - ch|^2, |ch|^2 (the hi-only scores' bound)
+    double r32 = 0.0;                    // |c - f32(c)|^2 (fast distances)
+    for (int j = lane; j < FU_D; j += 64) {
+        const double raw = c < K && j < d ? C[(size_t)c * d + j] : 0.0;
+        const double v = raw * scale;
+        if (C64p) C64p[(size_t)c * FU_D + j] = raw;
+        const float f = (float)v;
+        not32 |= c < K && (double)f != v;
+        tiny |= c < K && fabs(raw) < 0x1p-460 && raw != 0.0;
+        if (C32) {
+            C32[(size_t)c * FU_D + j] = f;
+            const double e = v - (double)f;       // exact (or inf / nan: never certified)
+            r32 = fma(e, e, r32);
+        }
+        const _Float16 hv = (_Float16)f;
+        Ch[(size_t)c * FU_D + j] = hv;
+        Cl[(size_t)c * FU_D + j] = (_Float16)(f - (float)hv);
+        s2 = fma(v, v, s2);
+        s1 += fabs(v);
+        const double r = v - (double)hv;     // exact in fp64 for |v| <= 2^15
+        rr = fma(r, r, rr);
+        hh = fma((double)hv, (double)hv, hh);
+        bad |= !(fabs(v) <= (double)FU_RANGE);
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        s2 += __shfl_xor(s2, off);
+        s1 += __shfl_xor(s1, off);
+        rr += __shfl_xor(rr, off);
+        hh += __shfl_xor(hh, off);
+        r32 += __shfl_xor(r32, off);
+    }
+    // sum of 128 non-negative fp64 values: <= 2^-46 relative rounding; rounded up
+    if (rn32 && lane == 0) rn32[c] = r32 == 0.0 ? 0.f : (float)(sqrt(r32) * (1.0 + 0x1p-40)) * (1.f + 0x1p-22f);
+    const unsigned long long anybad = __ballot(bad);
+    const unsigned long long any_not32 = __ballot(not32);
+    const unsigned long long any_tiny = __ballot(tiny);
+    // per wave (centroid) the bound maxima, then one atomic per word per block:
+    // single-word atomics from every centroid serialise (~12 ns each)
+    __shared__ unsigned int wmax[FP_PREP_WAVES][8];
+    if (lane == 0) {
+        unsigned int m[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        m[7] = (any_not32 ? 1u : 0u) | (any_tiny ? 2u : 0u);
+        if (c >= K) {
+            // padding rows: a finite score far below any real one (|x.c| < 2^38 under
+            // the range guard), so the packed-index trick never meets an inf/nan
+            cnh[c] = -0x1p100f;
+        } else {
+            cnh[c] = metric == 1 ? 0.f : (float)(-0.5 * s2);
+            const double up = 1.0 + 0x1p-18;
+            const double nc = sqrt(s2) * (1.0 + 0x1p-30);
+            // |t~ - t| <= (A1 + 2^-22)|x||c| + A2(|x|_1 + |c|_1) + 2^-23 |c|^2 + 2^-41 (|x|^2 + |c|^2)
+            // (cosine: no |c|^2 term in t, c = the normalised row)
+            m[0] = __float_as_uint((float)((FU_A1 + 0x1p-22) * nc * up));     // positive floats order like their bits
+            m[1] = __float_as_uint((float)((FU_A2 * s1 * (1.0 + 0x1p-20) + (metric == 1 ? 0.0 : 0x1p-23 * s2) +
+                                            0x1p-41 * s2) * up));
+            m[2] = anybad ? 1u : 0u;
+            m[3] = __float_as_uint((float)(nc * up));                        // max |c|, rounded up
+            // hi-only scores (fused_hi_kernel): max |c - ch|, max |ch|, max |cn|, rounded up
+            m[4] = __float_as_uint((float)(sqrt(rr) * (1.0 + 0x1p-30) * up));
+            m[5] = __float_as_uint((float)(sqrt(hh) * (1.0 + 0x1p-30) * up));
+            m[6] = __float_as_uint((float)(metric == 1 ? 0.0 : 0.5 * s2 * up));
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++) wmax[threadIdx.x >> 6][i] = m[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const int i = threadIdx.x;
+        unsigned int v = 0u;
+        for (int w = 0; w < FP_PREP_WAVES; w++) v = i == 2 || i == 7 ? (v | wmax[w][i]) : max(v, wmax[w][i]);
+        if (v) {
+            if (i == 2 || i == 7) atomicOr(cb + i, v);
+            else atomicMax(cb + i, v);
+        }
+    }
+}
+
+int launch_fused_prep(hipStream_t s, const double* C, int K, int Kpad, _Float16* Ch, _Float16* Cl, float* cnh,
+                      float* cbound, int metric, double* nbv, float* C32, float* rn32, int d, double* C64p) {
+    if (d < 1 || d > FU_D || (d != FU_D && metric == 0 && !C64p)) {
+        set_error("launch_fused_prep: d <= 128, and d < 128 needs the padded centroid copy");
+        return -1;
+    }
+    if (metric == 1 && !nbv) {
+        set_error("launch_fused_prep: cosine needs the norm array");
+        return -1;
+    }
+    if ((C32 == nullptr) != (rn32 == nullptr)) {
+        set_error("launch_fused_prep: the fast-distance image needs both arrays");
+        return -1;
+    }
+    (void)hipMemsetAsync(cbound, 0, 32, s);
+    if (Kpad % FP_PREP_WAVES) {
+        set_error("launch_fused_prep: Kpad must be a multiple of 8");
+        return -1;
+    }
+    hipLaunchKernelGGL(fused_centroid_prep, dim3((unsigned)(Kpad / FP_PREP_WAVES)), dim3(64 * FP_PREP_WAVES), 0, s, C, K, Kpad, Ch, Cl, cnh,
+                       reinterpret_cast<unsigned int*>(cbound), metric, nbv, C32, rn32, d, C64p);
+    return kstatus("fused_centroid_prep");
+}
+
+// Winners listed by the fused kernels for their distance alone: lane per row.
+// Cosine (MET = 1): the certificate declined, the x87 chain decides
+// (exact_cosine_x87_wave). Euclidean (MET = 0, exact distances): a square of
+// the chain was inexact, so glibc's pow(x, 2) may differ from x*x -- the chain
+// again with glibc's pow (exact_euclid_wave). CF_SPLIT blocks per list segment; both
+// lists of a call (the hi-only pass's and the refinement's) in ONE launch, so
+// the short list's lone chains (~40 us of latency) overlap the long one.
+constexpr int CF_SPLIT = 8;
+struct CosLists {
+    const unsigned long long* list[2];
+    const int32_t* counts[2];
+};
+template <typename TX, int MET>
+__global__ __launch_bounds__(256) void cos_fix_seg_kernel(const TX* __restrict__ X, int d, const double* __restrict__ C,
+                                                          CosLists cl, int nseg, int64_t seg_rows,
+                                                          const int32_t* __restrict__ assign, double* __restrict__ dist,
+                                                          const double* __restrict__ xn2, const double* __restrict__ nbv) {
+    // consecutive blocks take different segments: blocks are dealt round-robin to
+    // the 8 XCDs, and a short list fills only its segment's first part (with
+    // seg = blockIdx / CF_SPLIT every busy block sat on one XCD: 4x slower)
+    const int per_list = nseg * CF_SPLIT;
+    const int li = blockIdx.x / per_list, b = blockIdx.x % per_list;
+    const int seg = b % nseg, part = b / nseg;
+    const int n = cl.counts[li][2 * seg + 1];
+    const unsigned long long* l = cl.list[li] + (int64_t)seg * seg_rows;
+    const bool vec = sizeof(TX) == 4 && d % 8 == 0 && ((uintptr_t)X & 15) == 0 && ((uintptr_t)C & 15) == 0;
+    __shared__ double sqs[4][64 * 16];                   // gp_sq_wave: 64 * NV per wave
+    double* sq = sqs[threadIdx.x >> 6];
+    const int lane = threadIdx.x & 63;
+    // wave-uniform trip count (the chains run the whole wave in step); a lane
+    // past the list end repeats the wave's first row and writes nothing
+    for (int i0 = part * 256 + (threadIdx.x & ~63); i0 < n; i0 += CF_SPLIT * 256) {
+        const int i = i0 + lane;
+        const bool live = i < n;
+        const int64_t row = (int64_t)l[live ? i : i0];
+        const TX* xr = X + row * d;
+        const double* cr = C + (size_t)assign[row] * d;
+        double v;
+        if constexpr (MET == 1) {
+            // the sums of squares precomputed (the prep's nbv; fp64 rows: row_sumsq)
+            // when the launch has them: no squares left in the chain
+            if (nbv && (sizeof(TX) == 4 || xn2)) {
+                const double xa = sizeof(TX) == 4 ? -1.0 : xn2[row], cb = nbv[assign[row]];
+                if (vec) v = exact_cosine_x87_pf<sizeof(TX) == 4>(xr, cr, d, xa, cb);
+                else v = exact_cosine_x87_pf<false>(xr, cr, d, xa, cb);
+            } else if (vec) {
+                v = exact_cosine_x87_wave<sizeof(TX) == 4>(xr, cr, d, sq);
+            } else {
+                v = exact_cosine_x87_wave<false>(xr, cr, d, sq);
+            }
+        } else {
+            if (vec) v = exact_euclid_wave<sizeof(TX) == 4>(xr, cr, d, sq);
+            else v = exact_euclid_wave<false>(xr, cr, d, sq);
+        }
+        if (live) dist[row] = v;
+    }
+}
+
+// out[i] = the reference's sum_j pow(x_ij, 2), j ascending (the |x|^2 of
+// cosineDistance, cust_vector.hpp:148-151) for fp64 rows, lane per row. A wave
+// takes 64 rows; VEC (d even, rows 16-B aligned): each 8-dim step of the 64
+// rows is loaded as 16-B pieces, four lanes per row's 64 contiguous bytes, and
+// transposed through LDS (a lane-per-row load touches 64 lines per instruction).
+constexpr int RSQ_S = 10;                                // LDS row stride (doubles)
+template <bool VEC>
+__global__ __launch_bounds__(256) void row_sumsq_kernel(const double* __restrict__ X, int64_t N, int d,
+                                                         double* __restrict__ out) {
+    __shared__ double sqs[4][64 * 8];                    // gp_sq_wave: 64 * NV per wave
+    __shared__ __attribute__((aligned(16))) double tr[4][64 * RSQ_S];
+    double* sq = sqs[threadIdx.x >> 6];
+    double* t = tr[threadIdx.x >> 6];
+    const int lane = threadIdx.x & 63;
+    // wave-uniform trip count: lanes past N repeat row N - 1 and write nothing
+    for (int64_t i0 = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63); i0 < N; i0 += (int64_t)gridDim.x * 256) {
+        const int64_t i = i0 + lane;
+        double a = 0.0;
+        if constexpr (VEC) {
+            double2 pc[4], pn[4];
+            auto load = [&](int j0, double2 (&dst)[4]) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int q = 64 * k + lane, r = q >> 2, part = q & 3;
+                    const int64_t rr = i0 + r < N ? i0 + r : N - 1;
+                    const int j = j0 + 2 * part;
+                    dst[k] = j < d ? *reinterpret_cast<const double2*>(X + rr * d + j) : make_double2(0.0, 0.0);
+                }
+            };
+            load(0, pn);
+            for (int j0 = 0; j0 < d; j0 += 8) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) pc[k] = pn[k];
+                if (j0 + 8 < d) load(j0 + 8, pn);               // the next step in flight
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int q = 64 * k + lane;
+                    *reinterpret_cast<double2*>(t + (q >> 2) * RSQ_S + 2 * (q & 3)) = pc[k];
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                double v[8], p[8];
+#pragma unroll
+                for (int h = 0; h < 4; h++) {
+                    const double2 w = *reinterpret_cast<const double2*>(t + lane * RSQ_S + 2 * h);
+                    v[2 * h] = w.x;
+                    v[2 * h + 1] = w.y;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                gp_sq_wave<8>(v, p, sq);
+#pragma unroll
+                for (int u = 0; u < 8; u++)
+                    if (j0 + u < d) a = __dadd_rn(a, p[u]);
+            }
+        } else {
+            const double* x = X + (i < N ? i : N - 1) * d;
+            for (int j0 = 0; j0 < d; j0 += 8) {
+                double v[8], p[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) v[u] = j0 + u < d ? x[j0 + u] : 0.0;
+                gp_sq_wave<8>(v, p, sq);
+#pragma unroll
+                for (int u = 0; u < 8; u++)
+                    if (j0 + u < d) a = __dadd_rn(a, p[u]);
+            }
+        }
+        if (i < N) out[i] = a;
+    }
+}
+
+int launch_row_sumsq(hipStream_t s, const double* X, int64_t N, int d, double* out) {
+    if (N <= 0) return 0;
+    const unsigned grid = (unsigned)std::min<int64_t>((N + 255) / 256, 4096);
+    if (d % 2 == 0 && ((uintptr_t)X & 15) == 0) hipLaunchKernelGGL(row_sumsq_kernel<true>, dim3(grid), dim3(256), 0, s, X, N, d, out);
+    else hipLaunchKernelGGL(row_sumsq_kernel<false>, dim3(grid), dim3(256), 0, s, X, N, d, out);
+    return kstatus("row_sumsq_kernel");
+}
+
+int launch_cos_fix_seg(hipStream_t s, Pts X, int d, const double* C, int nlists, const unsigned long long* const* lists,
+                       const int32_t* const* counts, int64_t seg_rows, int nseg, const int32_t* assign, double* dist,
+                       int metric, const double* xn2, const double* nbv) {
+    if (nseg <= 0 || nlists <= 0) return 0;
+    if (nlists > 2) return -1;                       // LSHKM_ERR_ARG
+    CosLists cl{};
+    for (int i = 0; i < nlists; i++) { cl.list[i] = lists[i]; cl.counts[i] = counts[i]; }
+    const dim3 grid((unsigned)(nlists * nseg * CF_SPLIT));
+#define CF_LAUNCH(TX, M, XP) hipLaunchKernelGGL((cos_fix_seg_kernel<TX, M>), grid, dim3(256), 0, s, XP, d, C, cl, nseg, seg_rows, assign, dist, xn2, nbv)
+    if (metric == 1) {
+        if (X.f64) CF_LAUNCH(double, 1, X.d()); else CF_LAUNCH(float, 1, X.f());
+    } else {
+        if (X.f64) CF_LAUNCH(double, 0, X.d()); else CF_LAUNCH(float, 0, X.f());
+    }
+#undef CF_LAUNCH
+    return kstatus("cos_fix_seg_kernel");
+}
+
+}  // namespace lshkm

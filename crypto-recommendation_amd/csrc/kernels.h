@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fused_args.h"
+
 namespace lshkm {
 
 // Dataset rows in HBM: fp32 (the storage the hot path is tuned for: the
@@ -315,81 +317,47 @@ struct FusedLaunch {
     bool join_pending = false;
     hipEvent_t side_timing = nullptr;            // recorded on the side stream after the fix-up (timing)
     bool side_timed = false;                     // out: side_timing was recorded by this launch
-    const float* X = nullptr;
-    int64_t N = 0;
-    const _Float16* Ch = nullptr;
-    const _Float16* Cl = nullptr;
-    const float* cnh = nullptr;
-    const float* cbound = nullptr;
-    const double* C64 = nullptr;
-    int Kpad = 0;
-    const _Float16* Vh = nullptr;
-    const _Float16* Vl = nullptr;
-    const double* PT = nullptr;
-    const float* tv = nullptr;
-    const double* pnorm = nullptr;
-    const double* v1 = nullptr;
-    const int32_t* rv = nullptr;
-    float w = 0.f;
-    int L = 0, k = 0, LK = 0, LKpad = 0;
-    int64_t nb = 1;
-    int32_t* tuples = nullptr;
-    int32_t* phi = nullptr;
-    int32_t* bucket = nullptr;
-    int32_t* assign = nullptr;
-    double* dist = nullptr;
-    int32_t* ambig = nullptr;
-    unsigned long long* ambig_count = nullptr;
-    unsigned long long* hfix = nullptr;          // (row << 32 | fn mask) of uncertified hashes
-    unsigned long long* hfix_count = nullptr;
-    unsigned long long* stats = nullptr;
-    // persistent form: ambig / hfix are split in per-block segments
+    // The kernels' argument block (fused_args.h). The caller sets what passes
+    // through unchanged: the rows (X or X64, N, d), the prepared centroids (Ch,
+    // Cl, cnh, cbound, C64, Kpad, nbv, C32 / rn32, Cd), the hash family and
+    // its outputs, assign / dist, the lists with their device counters (ambig,
+    // hfix, cfix) and stats. launch_fused sets the per-pass fields itself.
+    //   ambig / ambig_count: the rows left for the caller's exact pass
+    //   hfix / hfix_count: (row << 32 | fn mask) of uncertified hashes
+    //   cfix / cfix_counts / cfix_count: winners listed for their distance alone
+    //     by the hi-only pass (cosine declines, or, with exact euclidean
+    //     distances, pow fix-ups): [list_cap] entries, counts in cfix_counts[2b + 1]
+    //   fast_dist: the euclidean winner's distance from f32(c) in f32, certified
+    //     to 2^-20 relative (else the row is refined exactly); needs C32
+    //     [Kpad][128] = f32(c) and rn32 [Kpad] = |c - f32(c)|_2 rounded up
+    //   xn2: cosine, fp64 rows: [N] sum_j pow(x_j, 2) (launch_row_sumsq)
+    FusedArgs a = [] { FusedArgs v{}; v.nb = 1; v.d = 128; return v; }();
+    // ambig / hfix / cfix are split in per-block segments
     int64_t list_cap = 0;                        // entries available in ambig and in hfix
     int32_t* seg_counts = nullptr;               // [2 * seg_cap]
     int seg_cap = 0;
     // out: nseg > 0 when the lists are segmented (segment b = [b * seg_rows, ...))
     int nseg = 0;
     int64_t seg_rows = 0;
-    // cosine Lloyd (metric 1, no hashing): nbv[c] = the reference's sequential
-    // sum of c_j^2; hfix/hfix_count then list the rows whose winner distance the
-    // certified form declined (cos_fix_seg pass)
+    // metric 1: cosine Lloyd; a.nbv[c] = the reference's sequential sum of c_j^2
     int metric = 0;
-    const double* nbv = nullptr;
-    const double* xn2 = nullptr;    // cosine, fp64 rows: [N] sum_j pow(x_j, 2) (launch_row_sumsq)
-    // euclidean fast distance (fast_dist): the winner's distance from f32(c) in
-    // f32, certified to 2^-20 relative (else the row is refined exactly);
-    // C32 [Kpad][128] = f32(c), rn32 [Kpad] = |c - f32(c)|_2 rounded up
-    const float* C32 = nullptr;
-    const float* rn32 = nullptr;
-    int fast_dist = 0;
-    // general rows (euclidean Lloyd, no hashing, Kpad <= 512): rows = 1: fp32
-    // rows of d <= 128 dims (X); rows = 2: fp64 rows of d <= 128 dims (X64).
-    // C64 is then the prep's [Kpad][128] zero-padded copy; the hi-only pass's
-    // uncertified rows go straight to the caller's exact pass (no LIST form)
+    // general rows (no hashing, Kpad <= 512): rows = 1: fp32 rows of a.d <= 128
+    // dims (a.X); rows = 2: fp64 rows of a.d <= 128 dims (a.X64). a.C64 is then
+    // the prep's [Kpad][128] zero-padded copy, a.Cd the caller's [K][d] centroids
     int rows = 0;
-    const double* X64 = nullptr;
-    int d = 128;
-    const double* Cd = nullptr;                  // general rows, cosine: the caller's [K][d] centroids
-    // K > 256 on the persistent form: passes over 256-centroid slices carry each
-    // lane's (best, runner-up, tile) in part[] (32 B per point)
+    // K > 256: passes over centroid slices carry each lane's (best, runner-up,
+    // tile) in part[] (32 B per point)
     void* part = nullptr;
     int64_t part_bytes = 0;
-    // hi-only form (euclidean): fused_hi_kernel, then the 3-product LIST form on
-    // its uncertified rows (list2 / seg_counts2: [list_cap] / [2 * seg_cap]);
-    // out: refined = rows the hi-only pass left to the 3-product form (device)
-    bool hi = false;
+    // the refinement's own output list (list2 / seg_counts2: [list_cap] /
+    // [2 * seg_cap]); out: refined = rows the hi-only passes left to it (device)
     int32_t* list2 = nullptr;
     int32_t* seg_counts2 = nullptr;
     unsigned long long* refined = nullptr;
-    // hi-only cosine: the LIST form's declined winner distances go to a second
-    // fix-up list (hfix2: [list_cap] entries after the first); out: the lists
-    // for cos_fix_seg, (list, segment counts) pairs
+    // cosine: the refinement's declined winner distances go to a second fix-up
+    // list (hfix2: [list_cap] entries); out: the lists for cos_fix_seg, (list,
+    // segment counts) pairs
     unsigned long long* hfix2 = nullptr;
-    // hi-only cosine: the hi-only pass's declined winner distances ([list_cap]
-    // entries, counts in cfix_counts[2b + 1], total in cfix_count)
-    unsigned long long* cfix = nullptr;
-    int32_t* cfix_counts = nullptr;
-    unsigned long long* cfix_count = nullptr;
     int ncos_lists = 0;
     const unsigned long long* cos_list[2] = {nullptr, nullptr};
     const int32_t* cos_counts[2] = {nullptr, nullptr};

@@ -384,6 +384,42 @@ def test_multipass_persistent_k1024(ctx, sctx, sw, metric, monkeypatch, dist_mod
     assert_dist(d0.cpu().numpy()[sub], od, mode)
 
 
+@pytest.mark.parametrize("rows_kind", ["f32_d128", "f32_d100", "f64_d100"])
+@pytest.mark.parametrize("K", [256, 300])
+@pytest.mark.parametrize("metric", ["euclidean", "cosine"])
+def test_refinement_reached(ctx, sctx, sw, metric, K, rows_kind, monkeypatch, dist_mode):
+    # the 3-product refinement (fused_persistent_kernel) is reached and right in
+    # each of its 12 instantiations: metric x one slice (K = 256) / two slices
+    # (K = 300: the multi-pass form) x row kind; N = 4099 leaves a ragged last
+    # tile. Near-duplicate centroids (rows x 1.0001) keep runner-ups close, so
+    # the hi-only pass lists rows. Rows refined at N = 4099, the same in both
+    # distance modes except where two figures are given (certified / exact):
+    #              euclidean K=256    K=300      cosine K=256  K=300
+    #   f32_d128             407 / 151  457 / 157         103    101
+    #   f32_d100             347 / 91   409 / 109         120    105
+    #   f64_d100              91        109               120    105
+    N = 4099
+    d = 128 if rows_kind == "f32_d128" else 100
+    X = ctx.synth(0x3F1 + d, N, d)
+    if rows_kind == "f64_d100":
+        X = X.double()
+    Cc = X[:K].double() * 1.0001
+    ctx.reset_stats()
+    a0, d0 = lshkm.lloyd_assign(ctx, X, Cc, metric)
+    refined = ctx.stat(lshkm.STAT_REFINED)
+    print(f"refined rows: {metric} K={K} {rows_kind} {dist_mode}: {refined}")
+    assert refined > 0
+    oa, _ = oracle.lloyd_assign(X.cpu().numpy(), Cc.cpu().numpy(), metric, None)
+    assert np.array_equal(a0.cpu().numpy(), oa)
+    monkeypatch.setenv("LSHKM_ASSIGN_PATH", "exact")
+    a1, d1 = sw.lloyd_assign(sctx, X, Cc, metric)
+    assert np.array_equal(a0.cpu().numpy(), a1.cpu().numpy())
+    # the certified distance applies to euclidean fp32 rows only; cosine and
+    # fp64 rows keep the exact-order chain in both modes
+    mode = dist_mode if metric == "euclidean" and rows_kind != "f64_d100" else "exact"
+    assert_dist(d0.cpu().numpy(), d1.cpu().numpy(), mode)
+
+
 @pytest.mark.parametrize("hashed", [False, True])
 def test_two_image_k1000(ctx, sctx, sw, hashed, monkeypatch, dist_mode):
     # the opt-in one-launch form for 512 < K <= 1024 (LSHKM_HI_TWO_IMAGE=1): the

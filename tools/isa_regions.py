@@ -2,7 +2,8 @@
 
 Build the listing with the region comments of the phase markers:
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Iinclude -Icrypto-recommendation_amd/csrc \
-        -DLSHKM_ISA_MARK -x hip -S --cuda-device-only crypto-recommendation_amd/csrc/fused.hip -o /tmp/fused.s
+        -DLSHKM_ISA_MARK -x hip -S --cuda-device-only crypto-recommendation_amd/csrc/fused_hi.hip -o /tmp/fused.s
+(fused_hi.hip: fused_hi_kernel; fused_refine.hip: fused_persistent_kernel)
 then: python tools/isa_regions.py /tmp/fused.s 'fused_hi_kernelILb1ELb0ELi0ELi1ELb1ELi0E'
 Regions are the text between consecutive ';PTMARK i' comments (static counts:
 unrolled loops count every copy, loops with a runtime trip count once).

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel resource usage of one source file (VGPRs, AGPRs, spills,
 scratch, occupancy) from hipcc's kernel-resource-usage remarks:
-  python3 tools/kres.py csrc/fused.hip [filter]   (run from crypto-recommendation_amd/)"""
+  python3 tools/kres.py csrc/fused_hi.hip [filter]   (run from crypto-recommendation_amd/; the fused pass's
+  kernels: csrc/fused_hi.hip, fused_refine.hip, fused_chunked.hip, fused_small.hip)"""
 import re
 import subprocess
 import sys

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Fused-pass timing of library variants (tools/time_fused.py), twice each in
 # alternation: tools/variants.sh TAG base name1 name2 ...  (base = liblshkm.so,
-# name = crypto-recommendation_amd/liblshkm_<name>.so; name@VAR=VALUE runs that
+# name = crypto-recommendation_amd/liblshkm_<name>.so, built by
+# `make svariant V=<name> SRC=fused_hi.hip EXTRA=...`; name@VAR=VALUE runs that
 # library with one environment setting); each run under its own limit.
 set -u
 TAG=${1:?tag}; shift
