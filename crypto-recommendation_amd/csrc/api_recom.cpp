@@ -40,6 +40,25 @@ static int read_ucl(lshkm_ctx ctx, const int32_t* ucl, int64_t nq, int K, std::v
     return 0;
 }
 
+// get_P_closest's launches for candidate lists of `total` rows (at least the
+// lists' real total), on the stream, in the ws_call workspace; no host wait.
+static int p_closest_launch(lshkm_ctx ctx, const double* X, int64_t N, int d, const double* U, int64_t nq,
+                            const int64_t* cand_ptr, const int32_t* cand_idx, int64_t total, int P, int32_t* out_idx,
+                            double* out_sim, int32_t* out_cnt) {
+    Buf &xa = ctx->ws_call[0], &sim = ctx->ws_call[1], &key = ctx->ws_call[2], &pos = ctx->ws_call[3],
+        &replay = ctx->ws_call[4], &count = ctx->ws_call[5];
+    const size_t T = (size_t)(total > 0 ? total : 1);
+    int rc;
+    if ((rc = xa.reserve(sizeof(double) * N)) || (rc = sim.reserve(sizeof(double) * T)) ||
+        (rc = key.reserve(sizeof(double) * T)) || (rc = pos.reserve(sizeof(int32_t) * T)) ||
+        (rc = replay.reserve(sizeof(int32_t) * nq)) || (rc = count.reserve(sizeof(unsigned int))))
+        return rc;
+    if ((rc = launch_rc_norms(ctx->stream, X, N, d, xa.as<double>()))) return rc;
+    return launch_rc_p_closest(ctx->stream, X, xa.as<double>(), d, U, nq, cand_ptr, cand_idx, P, sim.as<double>(),
+                               key.as<double>(), pos.as<int32_t>(), out_idx, out_sim, out_cnt, replay.as<int32_t>(),
+                               count.as<unsigned int>());
+}
+
 extern "C" {
 
 int lshkm_p_closest(lshkm_ctx ctx, const double* X, int64_t N, int d, const double* U, int64_t nq,
@@ -53,17 +72,7 @@ int lshkm_p_closest(lshkm_ctx ctx, const double* X, int64_t N, int d, const doub
     int rc;
     if ((rc = read_i64(ctx, cand_ptr + nq, &total))) return rc;
     LSHKM_CHECK(total >= 0 && (total == 0 || cand_idx), LSHKM_ERR_ARG, "bad candidate lists");
-    Buf &xa = ctx->ws_call[0], &sim = ctx->ws_call[1], &key = ctx->ws_call[2], &pos = ctx->ws_call[3],
-        &replay = ctx->ws_call[4], &count = ctx->ws_call[5];
-    const size_t T = (size_t)(total > 0 ? total : 1);
-    if ((rc = xa.reserve(sizeof(double) * N)) || (rc = sim.reserve(sizeof(double) * T)) ||
-        (rc = key.reserve(sizeof(double) * T)) || (rc = pos.reserve(sizeof(int32_t) * T)) ||
-        (rc = replay.reserve(sizeof(int32_t) * nq)) || (rc = count.reserve(sizeof(unsigned int))))
-        return rc;
-    if ((rc = launch_rc_norms(ctx->stream, X, N, d, xa.as<double>())) ||
-        (rc = launch_rc_p_closest(ctx->stream, X, xa.as<double>(), d, U, nq, cand_ptr, cand_idx, P, sim.as<double>(),
-                                  key.as<double>(), pos.as<int32_t>(), out_idx, out_sim, out_cnt,
-                                  replay.as<int32_t>(), count.as<unsigned int>()))) {
+    if ((rc = p_closest_launch(ctx, X, N, d, U, nq, cand_ptr, cand_idx, total, P, out_idx, out_sim, out_cnt))) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
@@ -543,6 +552,288 @@ int lshkm_cluster_top_n_f64(lshkm_ctx ctx, const double* X, const double* x_mean
                             int64_t nq, const int32_t* ucl, const int64_t* unk_ptr, const int32_t* unk_idx, int n_top,
                             int32_t* out) {
     return cluster_top_n_impl(ctx, X, x_mean, N, d, crow, crows, K, U, u_mean, nq, ucl, unk_ptr, unk_idx, n_top, out);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- recommender validation
+// glibc's rand() after srand(seed) (random_r.c, TYPE_3: the additive feedback
+// generator x^31 + x^3 + 1), restated: r[0] = seed (0 -> 1), r[i] =
+// 16807 * r[i-1] mod 2147483647 for i < 31 (Schrage's form on int32),
+// r[i] = r[i-31] + r[i-3] afterwards (r[31..33] = r[0..2]), the first 310
+// outputs discarded: draw n is r[344 + n] >> 1. Slot i % 31 holds r[i].
+namespace {
+struct GlibcRand {
+    uint32_t buf[31];
+    int64_t i;
+    explicit GlibcRand(uint64_t seed64) {
+        uint32_t seed = (uint32_t)seed64;
+        if (seed == 0) seed = 1;
+        int32_t word = (int32_t)seed;
+        buf[0] = (uint32_t)word;
+        for (int j = 1; j < 31; j++) {
+            const long hi = word / 127773, lo = word % 127773;
+            long w = 16807 * lo - 2836 * hi;
+            if (w < 0) w += 2147483647;
+            word = (int32_t)w;
+            buf[j] = (uint32_t)word;
+        }
+        for (i = 34; i < 344; i++) buf[i % 31] += buf[(i - 3) % 31];
+    }
+    int32_t next() {
+        const uint32_t v = (buf[i % 31] += buf[(i - 3) % 31]);
+        i++;
+        return (int32_t)(v >> 1);
+    }
+};
+
+// split_to_10 (crypto_rec.hpp:348-367): rows [10][N / 10]. A Fenwick tree of
+// the remaining positions finds the rand_i-th remaining user (what
+// input_vectors[rand_i] is after the erases before it).
+void split10(uint64_t seed, int64_t N, int32_t* rows) {
+    const int64_t F = N / 10;
+    if (F == 0) return;
+    GlibcRand g(seed);
+    std::vector<int32_t> tree((size_t)N + 1, 0);
+    for (int64_t p = 1; p <= N; p++) {
+        tree[p] += 1;
+        const int64_t up = p + (p & -p);
+        if (up <= N) tree[up] += tree[p];
+    }
+    int64_t top = 1;
+    while (top * 2 <= N) top *= 2;
+    int64_t remaining = N;
+    for (int64_t m = 0; m < 10 * F; m++) {
+        int64_t want = (int64_t)((uint64_t)g.next() % (uint64_t)remaining);   // 0-based rank among the remaining
+        int64_t pos = 0;
+        for (int64_t step = top; step > 0; step >>= 1)
+            if (pos + step <= N && tree[pos + step] <= want) {
+                pos += step;
+                want -= tree[pos];
+            }
+        rows[m] = (int32_t)pos;                                                // 0-based user (tree position pos + 1)
+        for (int64_t p = pos + 1; p <= N; p += p & -p) tree[p] -= 1;
+        remaining--;
+    }
+}
+
+struct LshHandles {
+    std::vector<lshkm_lsh> h;
+    ~LshHandles() {
+        for (lshkm_lsh x : h) (void)lshkm_lsh_destroy(x);
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int lshkm_cv_split10(uint64_t seed, int64_t N, int32_t* rows) {
+    LSHKM_CHECK(N >= 0 && N < (1ll << 31) && (rows || N < 10), LSHKM_ERR_ARG, "bad arguments");
+    split10(seed, N, rows);
+    return 0;
+}
+
+int lshkm_cv_draws(const uint64_t* seed, int64_t n, int64_t per, int32_t* draw) {
+    LSHKM_CHECK(n >= 0 && per >= 0 && (n * per == 0 || (seed && draw)), LSHKM_ERR_ARG, "bad arguments");
+    for (int64_t i = 0; i < n; i++) {
+        GlibcRand g(seed[i]);
+        for (int64_t j = 0; j < per; j++) draw[i * per + j] = g.next();
+    }
+    return 0;
+}
+
+int lshkm_cv_hide(lshkm_ctx ctx, const double* X, const double* x_mean, int64_t N, int d, const int64_t* unk_ptr,
+                  const int32_t* unk_idx, const int32_t* draw, double* H, double* h_mean, int32_t* hide_idx,
+                  double* old) {
+    LSHKM_CHECK(ctx && N >= 0 && d >= 1 && (N == 0 || (X && x_mean && unk_ptr && draw && H && h_mean && hide_idx && old)),
+                LSHKM_ERR_ARG, "bad arguments");
+    LSHKM_HIP(hipSetDevice(ctx->device));
+    return launch_cv_hide(ctx->stream, X, x_mean, nullptr, N, d, unk_ptr, unk_idx, draw, H, h_mean, hide_idx, old);
+}
+
+int lshkm_cv_exclude(lshkm_ctx ctx, const int64_t* in_ptr, const int32_t* in_idx, int64_t nq, int32_t lo, int32_t hi,
+                     int64_t* out_ptr, int32_t* out_idx) {
+    LSHKM_CHECK(ctx && in_ptr && out_ptr && nq >= 0 && lo <= hi && (out_idx == nullptr || out_idx != in_idx),
+                LSHKM_ERR_ARG, "bad arguments");
+    LSHKM_HIP(hipSetDevice(ctx->device));
+    Buf &cnt = ctx->ws_call[6], &ra = ctx->ws_call[7], &rb = ctx->ws_call[8];
+    const size_t n = (size_t)std::max<int64_t>(nq, 1);
+    int rc;
+    if ((rc = cnt.reserve(8 * n)) || (rc = ra.reserve(4 * n)) || (rc = rb.reserve(4 * n))) return rc;
+    return launch_cv_exclude(ctx->stream, in_ptr, in_idx, nq, lo, hi, cnt.as<int64_t>(), ra.as<int32_t>(),
+                             rb.as<int32_t>(), out_ptr, out_idx);
+}
+
+int lshkm_predicted_scores(lshkm_ctx ctx, const double* X, const double* x_mean, int64_t N, int d, const double* u_mean,
+                           int64_t nq, const int64_t* unk_ptr, const int32_t* unk_idx, const int32_t* nb_idx,
+                           const double* nb_sim, const int32_t* nb_cnt, int P, double* pred) {
+    LSHKM_CHECK(ctx && X && x_mean && u_mean && unk_ptr && nb_idx && nb_sim && nb_cnt && N >= 1 && d >= 1 && nq >= 0 &&
+                    P >= 1,
+                LSHKM_ERR_ARG, "bad arguments");
+    if (nq == 0) return 0;
+    LSHKM_HIP(hipSetDevice(ctx->device));
+    int64_t total = 0;
+    int rc;
+    if ((rc = read_i64(ctx, unk_ptr + nq, &total))) return rc;
+    LSHKM_CHECK(total >= 0 && (total == 0 || (unk_idx && pred)), LSHKM_ERR_ARG, "bad unknown-index lists");
+    return launch_cv_predict(ctx->stream, X, x_mean, d, u_mean, nq, total, unk_ptr, unk_idx, nb_idx, nb_sim, nb_cnt, P,
+                             pred);
+}
+
+int lshkm_cv_fold_sum(lshkm_ctx ctx, int64_t nq, const int32_t* hide_idx, const double* old, const double* pred,
+                      const int64_t* nb_ptr, double* err, double* k_sum, int64_t* count) {
+    LSHKM_CHECK(ctx && nq >= 0 && k_sum && count && (nq == 0 || (hide_idx && old && pred && nb_ptr)), LSHKM_ERR_ARG,
+                "bad arguments");
+    LSHKM_HIP(hipSetDevice(ctx->device));
+    return launch_cv_fold_sum(ctx->stream, nq, hide_idx, old, pred, nb_ptr, err, k_sum, count, false);
+}
+
+int lshkm_lsh_validate10(lshkm_ctx ctx, const double* X, const double* x_mean, int64_t N, int d, const int64_t* unk_ptr,
+                         const int32_t* unk_idx, int metric, int k, int L, int lsh_bucket_div, float w, int P,
+                         uint64_t split_seed, uint64_t hide_seed, const uint64_t* hide_seeds, const uint64_t* lsh_seeds,
+                         double* mae_host, double* fold_sum_host, int64_t* fold_cnt_host, double* err_dev) {
+    LSHKM_CHECK(ctx && mae_host && N >= 0 && N < (1ll << 31), LSHKM_ERR_ARG, "bad arguments");
+    LSHKM_CHECK(P >= 1 && d >= 1, LSHKM_ERR_ARG, "P and d must be >= 1");
+    LSHKM_CHECK(metric == LSHKM_METRIC_EUCLIDEAN || metric == LSHKM_METRIC_COSINE, LSHKM_ERR_ARG, "unknown metric");
+    const int64_t F = N / 10, M = 10 * F;
+    int64_t nb = 0;
+    if (metric == LSHKM_METRIC_EUCLIDEAN) {
+        LSHKM_CHECK(lsh_bucket_div >= 1, LSHKM_ERR_ARG, "lsh_bucket_div must be >= 1");
+        nb = (M - F) / lsh_bucket_div;                   // pool.size() / lsh_bucket_div (lsh_cube.hpp:52)
+        LSHKM_CHECK(nb >= 1, LSHKM_ERR_ARG, "pool size / lsh_bucket_div is 0 buckets (the reference divides by zero)");
+    }
+    if (F == 0) {                                        // every fold is empty: calc_user_num stays 0
+        *mae_host = 0.0;
+        for (int i = 0; i < 10; i++) {
+            if (fold_sum_host) fold_sum_host[i] = 0.0;
+            if (fold_cnt_host) fold_cnt_host[i] = 0;
+        }
+        return 0;
+    }
+    LSHKM_CHECK(X && x_mean && unk_ptr && lsh_seeds, LSHKM_ERR_ARG, "bad arguments");
+    LSHKM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int rc;
+
+    // host: the split and every user's hide draw, in split order
+    std::vector<int32_t> rows((size_t)M), draw((size_t)M);
+    split10(split_seed, N, rows.data());
+    const int32_t draw_all = GlibcRand(hide_seed).next();
+    for (int64_t m = 0; m < M; m++) draw[m] = hide_seeds ? GlibcRand(hide_seeds[rows[m]]).next() : draw_all;
+
+    // ten index handles up front (their parameter uploads wait for the stream)
+    LshHandles tabs;
+    {
+        std::vector<float> V, t;
+        std::vector<int32_t> r;
+        std::vector<double> R;
+        const size_t lk = (size_t)L * k;
+        LSHKM_CHECK(k >= 1 && L >= 1, LSHKM_ERR_ARG, "k and L must be >= 1");
+        if (metric == LSHKM_METRIC_EUCLIDEAN) { V.resize(lk * d); t.resize(lk); r.resize(lk); }
+        else R.resize(lk * d);
+        for (int i = 0; i < 10; i++) {
+            uint32_t st = 0;
+            if (metric == LSHKM_METRIC_EUCLIDEAN)
+                rc = lshkm_params_lsh_euclidean(lsh_seeds[i], L, k, d, w, V.data(), t.data(), r.data(), &st);
+            else
+                rc = lshkm_params_lsh_cosine(lsh_seeds[i], L, k, d, R.data(), &st);
+            if (rc) return rc;
+            lshkm_lsh h = nullptr;
+            if ((rc = lshkm_lsh_create(ctx, metric, d, k, L, nb, w, V.data(), t.data(), r.data(), R.data(), &h)))
+                return rc;
+            tabs.h.push_back(h);
+        }
+    }
+
+    // device state: W (the working matrix, split order) and the hidden forms
+    Buf bW, bWm, bH, bHm, bhide, bold, brows, bdraw, bpred, bhptr, bsum, bcnt, bqptr, bqidx, beptr, beidx, bscr, bra, brb,
+        bnidx, bnsim, bncnt;
+    const StreamSyncOnExit sync_guard{s};            // the buffers above are freed after the stream drained
+    const size_t Md = (size_t)M * d;
+    if ((rc = bW.reserve(8 * Md)) || (rc = bWm.reserve(8 * M)) || (rc = bH.reserve(8 * Md)) ||
+        (rc = bHm.reserve(8 * M)) || (rc = bhide.reserve(4 * M)) || (rc = bold.reserve(8 * M)) ||
+        (rc = brows.reserve(4 * M)) || (rc = bdraw.reserve(4 * M)) || (rc = bpred.reserve(8 * M)) ||
+        (rc = bhptr.reserve(8 * (M + 1))) || (rc = bsum.reserve(8 * 10)) || (rc = bcnt.reserve(8 * 10)) ||
+        (rc = bqptr.reserve(8 * (F + 1))) || (rc = beptr.reserve(8 * (F + 1))) || (rc = bscr.reserve(8 * F)) ||
+        (rc = bra.reserve(4 * F)) || (rc = brb.reserve(4 * F)) || (rc = bnidx.reserve(4 * (size_t)F * P)) ||
+        (rc = bnsim.reserve(8 * (size_t)F * P)) || (rc = bncnt.reserve(4 * F)))
+        return rc;
+    std::vector<int64_t> hptr((size_t)M + 1);        // every user's one-element unknown list {hide_idx}
+    for (int64_t m = 0; m <= M; m++) hptr[m] = m;
+    const H2D up[3] = {{brows.p, rows.data(), 4 * (size_t)M},
+                       {bdraw.p, draw.data(), 4 * (size_t)M},
+                       {bhptr.p, hptr.data(), 8 * (size_t)(M + 1)}};
+    if ((rc = h2d_batch(ctx, up, 3))) return rc;
+    double *W = bW.as<double>(), *Wm = bWm.as<double>(), *H = bH.as<double>(), *Hm = bHm.as<double>();
+    int32_t* hide = bhide.as<int32_t>();
+    if ((rc = launch_cv_gather(s, X, x_mean, brows.as<int32_t>(), M, d, W, Wm)) ||
+        (rc = launch_cv_hide(s, X, x_mean, brows.as<int32_t>(), M, d, unk_ptr, unk_idx, bdraw.as<int32_t>(), H, Hm, hide,
+                             bold.as<double>())))
+        return rc;
+
+    // candidate rows per chunk of queries: ~28 B of lists and workspace each
+    const int64_t cand_cap = test_switch("LSHKM_CV_CHUNK", "small") ? 64 : (int64_t)1 << 28;
+    // first guess from the mean bucket load (L tables of M / buckets rows each);
+    // a chunk whose lists come out larger is cut down below
+    const int64_t buckets = metric == LSHKM_METRIC_EUCLIDEAN ? nb : (int64_t)1 << std::min(k, 40);
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(F, cand_cap / std::max<int64_t>(1, (int64_t)L * (M / buckets + 1))));
+    for (int i = 0; i < 10; i++) {
+        const int64_t q0 = (int64_t)i * F;
+        // fold i's users take their hidden form (main.cpp:407-410) for good:
+        // they are the queries now and pool rows of the later folds
+        LSHKM_HIP(hipMemcpyAsync(W + q0 * d, H + q0 * d, 8 * (size_t)F * d, hipMemcpyDeviceToDevice, s));
+        LSHKM_HIP(hipMemcpyAsync(Wm + q0, Hm + q0, 8 * (size_t)F, hipMemcpyDeviceToDevice, s));
+        // hashing is per row: one build over all M rows under fold i's
+        // parameters serves the pool (slice i dropped from the results below)
+        lshkm_lsh h = tabs.h[i];
+        if ((rc = lshkm_lsh_build_f64(h, W, M))) return rc;
+        // the held-out users in chunks whose candidate lists fit cand_cap rows
+        // (the lists grow with N: a cosine bucket holds N / 2^k users per table)
+        for (int64_t qb = 0; qb < F;) {
+            const int64_t n = std::min(F - qb, chunk), u0 = q0 + qb;
+            int64_t total = 0;
+            if ((rc = lshkm_lsh_query_f64(h, W + u0 * d, n, nullptr, 1, bqptr.as<int64_t>(), nullptr, 0, &total)))
+                return rc;
+            if (total > cand_cap && n > 1) {             // size the chunk by this one's lists and ask again
+                chunk = std::max<int64_t>(1, (int64_t)((double)n * (double)cand_cap / (double)total));
+                continue;
+            }
+            const size_t T = (size_t)std::max<int64_t>(total, 1);
+            if ((rc = bqidx.reserve(4 * T)) || (rc = beidx.reserve(4 * T))) return rc;
+            if ((rc = lshkm_lsh_query_f64(h, W + u0 * d, n, nullptr, 1, bqptr.as<int64_t>(), bqidx.as<int32_t>(), total,
+                                          &total)))
+                return rc;
+            if ((rc = launch_cv_exclude(s, bqptr.as<int64_t>(), bqidx.as<int32_t>(), n, (int32_t)q0, (int32_t)(q0 + F),
+                                        bscr.as<int64_t>(), bra.as<int32_t>(), brb.as<int32_t>(), beptr.as<int64_t>(),
+                                        beidx.as<int32_t>())))
+                return rc;
+            if ((rc = p_closest_launch(ctx, W, M, d, W + u0 * d, n, beptr.as<int64_t>(), beidx.as<int32_t>(), total, P,
+                                       bnidx.as<int32_t>(), bnsim.as<double>(), bncnt.as<int32_t>())))
+                return rc;
+            // every user's one-element unknown list {hide_idx}; the users not
+            // calculated (-1) get no prediction and are never summed
+            if ((rc = launch_cv_predict(s, W, Wm, d, Wm + u0, n, n, bhptr.as<int64_t>() + u0, hide, bnidx.as<int32_t>(),
+                                        bnsim.as<double>(), bncnt.as<int32_t>(), P, bpred.as<double>())))
+                return rc;
+            if ((rc = launch_cv_fold_sum(s, n, hide + u0, bold.as<double>() + u0, bpred.as<double>() + u0,
+                                         beptr.as<int64_t>(), err_dev ? err_dev + u0 : nullptr, bsum.as<double>() + i,
+                                         bcnt.as<int64_t>() + i, qb > 0)))
+                return rc;
+            qb += n;
+        }
+    }
+    double ks[10];
+    int64_t kc[10];
+    const D2H rd[2] = {{ks, bsum.p, sizeof(ks)}, {kc, bcnt.p, sizeof(kc)}};
+    if ((rc = d2h_batch(ctx, rd, 2))) return rc;
+    double all_sum = 0;                              // main.cpp:428-434
+    for (int i = 0; i < 10; i++) {
+        if (kc[i] > 0) all_sum = all_sum + (ks[i] / (double)kc[i]);
+        if (fold_sum_host) fold_sum_host[i] = ks[i];
+        if (fold_cnt_host) fold_cnt_host[i] = kc[i];
+    }
+    *mae_host = all_sum / 10;
+    return 0;
 }
 
 }  // extern "C"

@@ -305,6 +305,22 @@ int launch_rc_top_n(hipStream_t s, const double* X, const double* x_mean, int d,
                     const int64_t* unk_ptr, const int32_t* unk_idx, const int32_t* nb_idx, const double* nb_sim,
                     const int32_t* nb_cnt, int P, int n_top, double* pred, int32_t* pidx, int32_t* out);
 
+// 10-fold validation of the LSH recommender (crossval.hip; main.cpp:393-437).
+// rows (may be NULL = identity): user m is row rows[m] of X and of the
+// unknown-index CSR.
+int launch_cv_gather(hipStream_t s, const double* X, const double* x_mean, const int32_t* rows, int64_t M, int d,
+                     double* W, double* w_mean);
+int launch_cv_hide(hipStream_t s, const double* X, const double* x_mean, const int32_t* rows, int64_t M, int d,
+                   const int64_t* unk_ptr, const int32_t* unk_idx, const int32_t* draw, double* H, double* h_mean,
+                   int32_t* hide_idx, double* old);
+int launch_cv_exclude(hipStream_t s, const int64_t* in_ptr, const int32_t* in_idx, int64_t nq, int32_t lo, int32_t hi,
+                      int64_t* cnt, int32_t* run_a, int32_t* run_b, int64_t* out_ptr, int32_t* out_idx);
+int launch_cv_predict(hipStream_t s, const double* X, const double* x_mean, int d, const double* u_mean, int64_t nq,
+                      int64_t entries, const int64_t* unk_ptr, const int32_t* unk_idx, const int32_t* nb_idx,
+                      const double* nb_sim, const int32_t* nb_cnt, int P, double* pred);
+int launch_cv_fold_sum(hipStream_t s, int64_t F, const int32_t* hide_idx, const double* old, const double* pred,
+                       const int64_t* nb_ptr, double* err, double* k_sum_out, int64_t* cnt_out, bool carry);
+
 // Fused hash + assign on split-f16 MFMA (fused.hip), d = 128.
 struct FusedLaunch {
     // optional side stream (+ fork / join events): the hash fix-up runs there

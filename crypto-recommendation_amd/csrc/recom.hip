@@ -20,6 +20,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "exact.h"
+#include "predict.h"
 
 namespace lshkm {
 
@@ -265,14 +266,7 @@ __global__ __launch_bounds__(64 * RC_WAVES) void rc_top_n_kernel(
         const double um = u_mean[q];
         for (int e = lane; e < m; e += 64) {
             const int index = unk_idx[o + e];
-            double main_sum = 0.0, abs_sum = 0.0;
-            for (int i = 0; i < cnt; i++) {
-                const double cs = nb_sim[q * P + i];
-                abs_sum = __dadd_rn(abs_sum, fabs(cs));
-                const int32_t r = nb_idx[q * P + i];
-                main_sum = __dadd_rn(main_sum, __dmul_rn(cs, __dsub_rn(X[(int64_t)r * d + index], x_mean[r])));
-            }
-            pred[o + e] = __dadd_rn(__ddiv_rn(main_sum, abs_sum), um);
+            pred[o + e] = rc_predict_at(X, x_mean, d, nb_idx + q * P, nb_sim + q * P, cnt, index, um);
             pidx[o + e] = index;
         }
         __threadfence_block();

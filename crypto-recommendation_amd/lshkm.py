@@ -137,6 +137,14 @@ def lib():
                                           i64, i64, C.POINTER(i64), C.POINTER(i64)]),
             "lshkm_cluster_chain_terms": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32,
                                                 vp]),
+            "lshkm_cv_split10": (i32, [u64, i64, vp]),
+            "lshkm_cv_draws": (i32, [vp, i64, i64, vp]),
+            "lshkm_cv_hide": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
+            "lshkm_cv_exclude": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
+            "lshkm_cv_fold_sum": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+            "lshkm_predicted_scores": (i32, [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i32, vp]),
+            "lshkm_lsh_validate10": (i32, [vp, vp, vp, i64, i32, vp, vp, i32, i32, i32, i32, f32, i32, u64, u64, vp, vp,
+                                           C.POINTER(f64), vp, vp, vp]),
             "lshkm_synth": (i32, [vp, u64, i64, i64, i32, vp]),
             "lshkm_synth_normal": (i32, [vp, u64, i64, i64, i32, vp]),
             "lshkm_clusters": (i32, [vp, vp, i64, i32, vp, vp]),
@@ -846,7 +854,114 @@ def cluster_chain_terms(ctx, u_mean, unk_ptr, unk_idx, soff, toff, sims, terms, 
     return outs if n_top is None else out
 
 
+# ------------------------------------------------ recommender validation
+def cv_split10(seed, N):
+    """split_to_10 (crypto_rec.hpp:348-367) with srand(seed): [10][N // 10] int32
+    user indexes in fold order (host only)."""
+    rows = np.empty((10, N // 10), np.int32)
+    _ck(lib().lshkm_cv_split10(int(seed), int(N), _np_ptr(rows)))
+    return rows
+
+
+def cv_draws(seeds, per=1):
+    """The first `per` values of glibc's rand() after srand(seed), per seed (host
+    only): int32 [n][per] (per = 1: hide_one_score's draw)."""
+    seeds = np.ascontiguousarray(np.atleast_1d(seeds), np.uint64)
+    draw = np.empty((seeds.shape[0], per), np.int32)
+    _ck(lib().lshkm_cv_draws(_np_ptr(seeds), seeds.shape[0], per, _np_ptr(draw)))
+    return draw
+
+
+def cv_hide(ctx, X, x_mean, unk_ptr, unk_idx, draw):
+    """hide_one_score (crypto_rec.hpp:393-449) for every user of X [N][d] fp64
+    (device tensors; draw [N] int32 = each user's rand() value). Returns (H
+    [N][d], h_mean [N], hide_idx [N] int32, -1 where the function returned
+    false, old_score [N])."""
+    torch = ctx.torch
+    N, d = X.shape
+    H = ctx.empty((N, d), torch.float64)
+    hm = ctx.empty((N,), torch.float64)
+    hi = ctx.empty((N,), torch.int32)
+    old = ctx.empty((N,), torch.float64)
+    _ck(lib().lshkm_cv_hide(ctx.h, _t_ptr(X), _t_ptr(x_mean), N, d, _t_ptr(unk_ptr),
+                            _t_ptr(unk_idx) if unk_idx.numel() else None, _t_ptr(draw), _t_ptr(H), _t_ptr(hm),
+                            _t_ptr(hi), _t_ptr(old)))
+    return H, hm, hi, old
+
+
+def cv_exclude(ctx, ptr, idx, lo, hi):
+    """Drops the rows in [lo, hi) from every list of a query result (ptr [nq+1]
+    int64 / idx int32 device tensors, ascending rows per list): (ptr, idx)."""
+    torch = ctx.torch
+    nq = ptr.shape[0] - 1
+    optr = ctx.empty((nq + 1,), torch.int64)
+    oidx = ctx.empty((max(idx.numel(), 1),), torch.int32)
+    _ck(lib().lshkm_cv_exclude(ctx.h, _t_ptr(ptr), _t_ptr(idx) if idx.numel() else None, nq, int(lo), int(hi),
+                               _t_ptr(optr), _t_ptr(oidx)))
+    ctx.sync()
+    return optr, oidx[:int(optr[nq].item())]
+
+
+def predicted_scores(ctx, X, x_mean, u_mean, unk_ptr, unk_idx, nb_idx, nb_sim, nb_cnt):
+    """get_predicted_user_sim (crypto_rec.hpp:280-306) over p_closest's lists:
+    one fp64 per entry of the unknown-index CSR, in unk_ptr order."""
+    torch = ctx.torch
+    N, d = X.shape
+    nq, P = nb_idx.shape
+    pred = ctx.empty((max(unk_idx.numel(), 1),), torch.float64)
+    _ck(lib().lshkm_predicted_scores(ctx.h, _t_ptr(X), _t_ptr(x_mean), N, d, _t_ptr(u_mean), nq, _t_ptr(unk_ptr),
+                                     _t_ptr(unk_idx) if unk_idx.numel() else None, _t_ptr(nb_idx), _t_ptr(nb_sim),
+                                     _t_ptr(nb_cnt), P, _t_ptr(pred)))
+    return pred[:unk_idx.numel()]
+
+
+def cv_fold_sum(ctx, hide_idx, old, pred, nb_ptr):
+    """One fold's k_sum and calc_user_num (main.cpp:413-425) over its users in
+    order (device tensors): (k_sum [1] fp64, count [1] int64, err [nq] fp64)."""
+    torch = ctx.torch
+    nq = hide_idx.shape[0]
+    ks = ctx.empty((1,), torch.float64)
+    cnt = ctx.empty((1,), torch.int64)
+    err = ctx.empty((max(nq, 1),), torch.float64)
+    _ck(lib().lshkm_cv_fold_sum(ctx.h, nq, _t_ptr(hide_idx), _t_ptr(old), _t_ptr(pred), _t_ptr(nb_ptr), _t_ptr(err),
+                                _t_ptr(ks), _t_ptr(cnt)))
+    return ks, cnt, err[:nq]
+
+
+def lsh_validate10(ctx, X, x_mean, unk_ptr, unk_idx, metric, k, L, lsh_bucket_div, w, P, split_seed, hide_seed,
+                   lsh_seeds, hide_seeds=None, errors=False):
+    """lsh_rec_10_fold_validation_A (main.cpp:393-437) over users X [N][d] fp64
+    (device tensors). Returns (mae, fold_sum [10], fold_cnt [10]) and, with
+    errors=True, the users' errors [10 * (N // 10)] in split order (-1: skipped)."""
+    torch = ctx.torch
+    N, d = X.shape
+    ls = np.ascontiguousarray(lsh_seeds, np.uint64)
+    assert ls.shape == (10,)
+    hs = None if hide_seeds is None else np.ascontiguousarray(hide_seeds, np.uint64)
+    assert hs is None or hs.shape == (N,)
+    mae = C.c_double()
+    fs = np.zeros(10, np.float64)
+    fc = np.zeros(10, np.int64)
+    err = ctx.empty((max(10 * (N // 10), 1),), torch.float64) if errors else None
+    _ck(lib().lshkm_lsh_validate10(ctx.h, _t_ptr(X), _t_ptr(x_mean), N, d, _t_ptr(unk_ptr),
+                                   _t_ptr(unk_idx) if unk_idx.numel() else None, _METRIC[metric], k, L,
+                                   int(lsh_bucket_div), float(np.float32(w)), P, int(split_seed), int(hide_seed),
+                                   _np_ptr(hs), _np_ptr(ls), C.byref(mae), _np_ptr(fs), _np_ptr(fc), _t_ptr(err)))
+    if errors:
+        return mae.value, fs, fc, err[:10 * (N // 10)]
+    return mae.value, fs, fc
+
+
 # ------------------------------------------------- reference-named mirrors
+def lsh_rec_10_fold_validation_A(ctx, X, x_mean, unk_ptr, unk_idx, metric_type, k, L, lsh_bucket_div, euclidean_h_w, P,
+                                 split_seed, hide_seed, lsh_seeds, hide_seeds=None):
+    """lsh_rec_10_fold_validation_A (main.cpp:393-437) with explicit seeds in
+    place of time(0) and the clock: the 10-fold mean absolute error."""
+    return lsh_validate10(ctx, X, x_mean, unk_ptr, unk_idx, metric_type, k, L, lsh_bucket_div, euclidean_h_w, P,
+                          split_seed, hide_seed, lsh_seeds, hide_seeds)[0]
+
+
+
 def create_LSH_hashtables(ctx, X, metric_type, k, L, lsh_bucket_div, euclidean_h_w, seed):
     """create_LSH_hashtables (lsh_cube.hpp:44-74) with an explicit seed in place of the clock."""
     d = X.shape[1]

@@ -586,6 +586,96 @@ int lshkm_cluster_chain_terms(lshkm_ctx ctx, int64_t nq, const double* u_mean_de
                               const double* carry_abs_dev, const int64_t* carry_cnt_dev, double* main_out_dev,
                               double* abs_out_dev, int64_t* cnt_out_dev, int n_top, int32_t* out_dev);
 
+/* ------------------------------------------------ recommender validation
+ * lsh_rec_10_fold_validation_A (main.cpp:393-437, called at :180-183) and the
+ * helpers it sits on. The reference seeds srand with time(0) and its LSH
+ * generators with the clock: both are explicit seeds here. rand() is glibc's
+ * (its additive-feedback generator after srand(seed)), restated in the library:
+ * the process-global srand / rand are never called.
+ *
+ * split_to_10 (crypto_rec.hpp:348-367), host only: srand(seed), F = N / 10;
+ * for each of 10 folds, F times: rand() % remaining.size(), that element taken
+ * and erased. rows_host [10][F]: the users (indexes into the caller's vector)
+ * in fold order; the last N % 10 users occur nowhere. An order-statistic tree
+ * replaces the reference's O(N) erase. 0 <= N < 2^31. */
+int lshkm_cv_split10(uint64_t seed, int64_t N, int32_t* rows_host /*[10][N/10]*/);
+/* The first `per` values of rand() after srand(seed_host[i]), i < n, host only:
+ * draw_host [n][per] (per = 1: hide_one_score's draw, crypto_rec.hpp:410-411). */
+int lshkm_cv_draws(const uint64_t* seed_host, int64_t n, int64_t per, int32_t* draw_host);
+/* hide_one_score (crypto_rec.hpp:393-449) for N users at once. X_dev [N][d]
+ * with means x_mean_dev [N]; unk_* = the CSR of each user's ascending unknown
+ * indexes (as lshkm_top_n_recom takes it); draw_dev [N]: each user's rand()
+ * value (lshkm_cv_draws). Per user: known_count = d - |unknown| < 2 returns
+ * false with nothing changed (:405-406); hide_index = draw % known_count is
+ * used directly as a dimension index (:411-412: it may land on an unknown
+ * index); old_score is read before the unknown entries are set to 0
+ * (:412-416); new_mean = the sequential sum from 0.0 of the other d - 1
+ * entries in index order, divided by d - 1 (:419-436); when all of them are 0
+ * the function returns false after the zeroing (:432-433).
+ * H_dev [N][d] / h_mean_dev [N]: the user as the function leaves it (unchanged;
+ * zeroed with the old mean; or hidden with the new mean); hide_idx_dev [N]:
+ * the hidden index, the user's one unknown index afterwards, or -1 where the
+ * function returned false; old_dev [N]: *old_score (0.0, main.cpp:409's initial
+ * value, where known_count < 2). */
+int lshkm_cv_hide(lshkm_ctx ctx, const double* X_dev, const double* x_mean_dev, int64_t N, int d,
+                  const int64_t* unk_ptr_dev, const int32_t* unk_idx_dev, const int32_t* draw_dev, double* H_dev,
+                  double* h_mean_dev, int32_t* hide_idx_dev, double* old_dev);
+/* merge_except_for (crypto_rec.hpp:370-390) applied to a filled query result
+ * over all folds' rows: drops the members in [lo, hi) from every query's
+ * ascending list. in_ptr_dev [nq+1] / in_idx_dev: lshkm_lsh_query's output;
+ * out_ptr_dev [nq+1] <- the new offsets; out_idx_dev (NULL: offsets only; else
+ * room for in_ptr[nq] rows, a different buffer than in_idx_dev) <- the kept
+ * members in their order. */
+int lshkm_cv_exclude(lshkm_ctx ctx, const int64_t* in_ptr_dev, const int32_t* in_idx_dev, int64_t nq, int32_t lo,
+                     int32_t hi, int64_t* out_ptr_dev, int32_t* out_idx_dev);
+/* get_predicted_user_sim (crypto_rec.hpp:280-306) over lshkm_p_closest's
+ * lists, as values: pred_dev[e] for entry e of the unknown-index CSR
+ * (unk_ptr_dev [nq+1] with unk_ptr[0] = 0, unk_idx_dev) = main_sum / abs_sum +
+ * u_mean, both sums over the user's kept neighbours in their sorted order
+ * (:289-297) -- the sums lshkm_top_n_recom sorts by. No neighbour or all
+ * similarities 0 gives 0 / 0: NaNs are x86's default NaN. */
+int lshkm_predicted_scores(lshkm_ctx ctx, const double* X_dev, const double* x_mean_dev, int64_t N, int d,
+                           const double* u_mean_dev, int64_t nq, const int64_t* unk_ptr_dev, const int32_t* unk_idx_dev,
+                           const int32_t* nb_idx_dev, const double* nb_sim_dev, const int32_t* nb_cnt_dev, int P,
+                           double* pred_dev);
+/* One fold's ordered error sum (main.cpp:413-425) over its nq held-out users in
+ * fold order: user q counts when hide_idx_dev[q] >= 0 and its neighbour list
+ * nb_ptr_dev[q] .. nb_ptr_dev[q+1] is not empty; k_sum = k_sum + fabs(old_dev[q]
+ * - pred_dev[q]), one sequential chain from 0.0 (no atomics, no tree).
+ * *k_sum_dev / *count_dev: k_sum and calc_user_num; err_dev [nq] (may be NULL):
+ * each user's error, -1.0 for the skipped ones. A NaN is x86's: fabs of the
+ * default NaN (0x7FF8...), kept by every later add. */
+int lshkm_cv_fold_sum(lshkm_ctx ctx, int64_t nq, const int32_t* hide_idx_dev, const double* old_dev,
+                      const double* pred_dev, const int64_t* nb_ptr_dev, double* err_dev, double* k_sum_dev,
+                      int64_t* count_dev);
+/* lsh_rec_10_fold_validation_A (main.cpp:393-437): the 10-fold mean absolute
+ * error of the LSH recommender over users X_dev [N][d] (means x_mean_dev,
+ * unknown-index CSR unk_*; all left unmodified, as the reference splits by
+ * value). split_seed: split_to_10's srand; hide_seed, or hide_seeds_host [N]
+ * per user when not NULL: hide_one_score's srand (the reference re-seeds with
+ * the wall-clock second on every call); lsh_seeds_host [10]: fold i's
+ * create_LSH_hashtables (lshkm_params_lsh_cosine / _euclidean; euclidean with
+ * nb = pool size / lsh_bucket_div, main.cpp:402-404).
+ * Fold i: the pool is every other fold -- folds < i in their hidden form, as
+ * the earlier loop bodies left them (:407-410 mutate in place), folds > i
+ * untouched, in fold order; each held-out user for which hide_one_score
+ * returned true and whose filtered union (lsh_cube.hpp:93-106) is not empty
+ * adds fabs(old_score - prediction at the hidden index) to k_sum in fold order
+ * (:413-424). NaNs are not filtered (a zero pool row gives a NaN k_sum).
+ * *mae_host = sum over the folds with users of k_sum / calc_user_num, / 10
+ * (:428-434); fold_sum_host / fold_cnt_host [10] (may be NULL): k_sum and
+ * calc_user_num; err_dev [10 * (N / 10)] (may be NULL): every user's error in
+ * split order, -1.0 for the skipped ones.
+ * N < 10: 0.0, no device work (every fold is empty). P < 1, d < 1,
+ * lsh_bucket_div < 1 or a euclidean nb of 0 (the reference divides by zero):
+ * LSHKM_ERR_ARG. Returns after the result is on the host. */
+int lshkm_lsh_validate10(lshkm_ctx ctx, const double* X_dev, const double* x_mean_dev, int64_t N, int d,
+                         const int64_t* unk_ptr_dev, const int32_t* unk_idx_dev, int metric, int k, int L,
+                         int lsh_bucket_div, float w, int P, uint64_t split_seed, uint64_t hide_seed,
+                         const uint64_t* hide_seeds_host /*[N] or NULL*/, const uint64_t* lsh_seeds_host /*[10]*/,
+                         double* mae_host, double* fold_sum_host /*[10]*/, int64_t* fold_cnt_host /*[10]*/,
+                         double* err_dev /*[10 * (N / 10)] or NULL*/);
+
 /* ------------------------------------------------------------ input formats
  * Host only (no device needed). VectorReader<double>::read
  * (vector_reader.hpp:54-85): lines 1..strt_line-1 kept as metadata, then one

@@ -653,6 +653,98 @@ std::vector<int> get_top_N_recom(std::vector<CustVector<T>*>& neighbors, CustVec
     return out;
 }
 
+// get_predicted_user_sim (crypto_rec.hpp:280-306): the user's dimensions with
+// the prediction main_sum / abs_sum + known mean at every unknown index.
+template <typename T>
+std::vector<T> get_predicted_user_sim(std::vector<CustVector<T>*>& neighbors, CustVector<T>& user,
+                                      std::vector<double> similarities) {
+    static_assert(std::is_same<T, double>::value, "lshkm_compat::get_predicted_user_sim matches CustVector<double> only");
+    const size_t n = neighbors.size(), d = user.getDimensions()->size();
+    std::vector<T> predicted(user.getDimensions()->begin(), user.getDimensions()->end());
+    const std::vector<int> unk = user.getUnknownIndexes();
+    if (unk.empty()) return predicted;
+    if (similarities.size() < n) throw std::invalid_argument("lshkm_compat: fewer similarities than neighbours");
+    const size_t rows = n > 0 ? n : 1;
+    std::vector<double> X(rows * d, 0.0), xm(rows, 0.0);
+    for (size_t i = 0; i < n; i++) {
+        const std::vector<T>& x = dims_of(*neighbors[i], d);
+        for (size_t j = 0; j < d; j++) X[i * d + j] = x[j];
+        xm[i] = neighbors[i]->getKnownMean();
+    }
+    const int P = n > 0 ? (int)n : 1;
+    std::vector<int32_t> nb(P, 0), cnt = {(int32_t)n};
+    std::vector<double> sm(P, 0.0);
+    for (size_t i = 0; i < n; i++) { nb[i] = (int32_t)i; sm[i] = similarities[i]; }
+    std::vector<int64_t> up = {0, (int64_t)unk.size()};
+    std::vector<int32_t> ui(unk.begin(), unk.end());
+    for (int32_t index : ui)
+        if (index < 0 || (size_t)index >= d) throw std::out_of_range("lshkm_compat: unknown index outside the vector");
+    const double um = user.getKnownMean();
+    DevMem Xd = upload(X.data(), X.size()), xmd = upload(xm.data(), rows), umd = upload(&um, 1);
+    DevMem upd = upload(up.data(), 2), uid = upload(ui.data(), ui.size());
+    DevMem nbd = upload(nb.data(), nb.size()), smd = upload(sm.data(), sm.size()), cnd = upload(cnt.data(), 1);
+    DevMem pd(sizeof(double) * ui.size());
+    check(lshkm_predicted_scores(context(), Xd.as<double>(), xmd.as<double>(), (int64_t)rows, (int)d, umd.as<double>(),
+                                 1, upd.as<int64_t>(), uid.as<int32_t>(), nbd.as<int32_t>(), smd.as<double>(),
+                                 cnd.as<int32_t>(), P, pd.as<double>()));
+    std::vector<double> p(ui.size());
+    download(p.data(), pd, p.size());
+    for (size_t e = 0; e < ui.size(); e++) predicted[ui[e]] = p[e];
+    return predicted;
+}
+
+// lsh_rec_10_fold_validation_A (main.cpp:393-437). The reference seeds
+// split_to_10 and every hide_one_score with time(0) and each fold's
+// create_LSH_hashtables with the clock: ValidationSeeds names them. The
+// caller's vectors are read and left unmodified (the reference splits copies).
+struct ValidationSeeds {
+    uint64_t split = 0, hide = 0;
+    std::vector<uint64_t> hide_per_user;      // [user_vectors.size()], or empty: `hide` for every user
+    uint64_t lsh[10] = {};
+};
+
+inline ValidationSeeds clock_validation_seeds() {
+    ValidationSeeds s;
+    s.split = s.hide = (uint64_t)(unsigned int)(int)std::chrono::system_clock::to_time_t(std::chrono::system_clock::now());
+    for (int i = 0; i < 10; i++) s.lsh[i] = clock_seed() + (unsigned long)i;   // folds never share a reading
+    return s;
+}
+
+inline double lsh_rec_10_fold_validation_A(std::vector<CustVector<double>>& user_vectors, std::string metric_type,
+                                           int k, int L, int lsh_bucket_div, double euclidean_h_w, int P,
+                                           const ValidationSeeds& seeds) {
+    const size_t n = user_vectors.size();
+    if (n < 10) return 0.0;                   // every fold is empty (main.cpp:428-434)
+    if (!seeds.hide_per_user.empty() && seeds.hide_per_user.size() != n)
+        throw std::invalid_argument("lshkm_compat: hide_per_user must hold one seed per user");
+    const size_t d = user_vectors[0].getDimensions()->size();
+    std::vector<double> X(n * d), xm(n);
+    std::vector<int64_t> up(1, 0);
+    std::vector<int32_t> ui;
+    for (size_t i = 0; i < n; i++) {
+        const std::vector<double>& x = dims_of(user_vectors[i], d);
+        for (size_t j = 0; j < d; j++) X[i * d + j] = x[j];
+        xm[i] = user_vectors[i].getKnownMean();
+        for (int index : user_vectors[i].getUnknownIndexes()) ui.push_back((int32_t)index);
+        up.push_back((int64_t)ui.size());
+    }
+    if (ui.empty()) ui.push_back(0);
+    DevMem Xd = upload(X.data(), X.size()), xmd = upload(xm.data(), n);
+    DevMem upd = upload(up.data(), up.size()), uid = upload(ui.data(), ui.size());
+    double mae = 0.0;
+    check(lshkm_lsh_validate10(context(), Xd.as<double>(), xmd.as<double>(), (int64_t)n, (int)d, upd.as<int64_t>(),
+                               uid.as<int32_t>(), metric_of(metric_type), k, L, lsh_bucket_div, (float)euclidean_h_w, P,
+                               seeds.split, seeds.hide, seeds.hide_per_user.empty() ? nullptr : seeds.hide_per_user.data(),
+                               seeds.lsh, &mae, nullptr, nullptr, nullptr));
+    return mae;
+}
+
+inline double lsh_rec_10_fold_validation_A(std::vector<CustVector<double>>& user_vectors, std::string metric_type,
+                                           int k, int L, int lsh_bucket_div, double euclidean_h_w, int P) {
+    return lsh_rec_10_fold_validation_A(user_vectors, metric_type, k, L, lsh_bucket_div, euclidean_h_w, P,
+                                        clock_validation_seeds());
+}
+
 // The 3-argument overload's clusters, kept on the device per thread. main.cpp
 // calls it once per user with a copy of that user's whole cluster
 // (main.cpp:260-269, :353-373): each cluster is marshalled and uploaded once,

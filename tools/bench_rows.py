@@ -6,7 +6,7 @@ syncs (host launch and sync latency included) -- next to the CPU restatement (or
 thread, OMP_NUM_THREADS=1, kind "port") on a bounded sample of the same
 workload, scaled to the row's unit. Prints one JSON line per row.
 
-    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64] [--no-cpu]
+    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64,cv] [--no-cpu]
 """
 import argparse
 import json
@@ -65,6 +65,34 @@ def cpu_time(fn):
     return time.perf_counter() - t0
 
 
+
+def cv_users(N, d, seed=0xBE7C4, known_256=128):
+    """The users tools/gen_cv_golden.cpp --time forms (its make_users, kind 0):
+    counter-based splitmix64 scores in [-1, 3), each known with probability
+    known_256 / 256 (two at least), the mean = the known scores' sum in index
+    order / their number, unknown indexes holding it. (x, mean, unk_ptr, unk_idx)."""
+    def mix(z):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+    with np.errstate(over="ignore"):
+        idx = np.arange(N * d, dtype=np.uint64)
+        score = (mix(np.uint64(seed) + np.uint64(2) * idx) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53 * 4.0 - 1.0
+        known = (mix(np.uint64(seed) + np.uint64(2) * idx + np.uint64(1)) >> np.uint64(56)).astype(np.int64) < known_256
+    score, known = score.reshape(N, d), known.reshape(N, d)
+    for i in np.nonzero(known.sum(axis=1) < 2)[0]:
+        for j in range(d):
+            if known[i].sum() >= 2:
+                break
+            known[i, j] = True
+    mean = np.add.accumulate(np.where(known, score, 0.0), axis=1)[:, -1] / known.sum(axis=1)
+    x = np.where(known, score, mean[:, None])
+    ui = np.nonzero(~known)[1].astype(np.int32)
+    up = np.concatenate([[0], np.cumsum((~known).sum(axis=1))]).astype(np.int64)
+    return x, mean, up, ui
+
+
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md
 
 
@@ -90,6 +118,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cv-sizes", default="20000,1000000", help="user counts of the cv row")
     ap.add_argument("--pam-shapes", default="100000x16,1000000x256", help="NxK list of the pam row (d = 128)")
     a = ap.parse_args()
     rows = set(a.rows.split(","))
@@ -361,6 +390,50 @@ def main():
         emit("k_means update (fp64 rows)", "rows/s", N, t, None, f"N={N}, d={d} fp64, K={K}; bytes: the fp64 row + id",
              bytes_per_unit=8 * d + 4)
         del X
+
+    if "cv" in rows:         # lsh_rec_10_fold_validation_A (main.cpp:393-437)
+        d, k, L, P, div = 100, 4, 5, 20, 4
+        tsec, seeds = 1546300800, np.arange(1, 11, dtype=np.uint64)       # gen_cv_golden --time: time(), the clock
+        for N in (int(v) for v in a.cv_sizes.split(",")):
+            xh, xmh, uph, uih = cv_users(N, d)
+            X, xm, up, ui = (torch.from_numpy(v).to(ctx.dev) for v in (xh, xmh, uph, uih))
+            res = {}
+
+            def whole():
+                res["v"] = lshkm.lsh_validate10(ctx, X, xm, up, ui, "cosine", k, L, div, 0.01, P, tsec, tsec, seeds)
+            t = gpu_time(ctx, whole, reps=2)
+            mae, fs, fc = res["v"]
+            # fold 0's parts through the public pieces (what the driver chains on its stream)
+            F = N // 10
+            split = torch.from_numpy(lshkm.cv_split10(tsec, N).ravel().astype(np.int64)).to(ctx.dev)
+            draw = torch.full((N,), int(lshkm.cv_draws([tsec])[0, 0]), dtype=torch.int32, device=ctx.dev)
+            H, hm, hi, old = lshkm.cv_hide(ctx, X, xm, up, ui, draw)
+            W, Wm = X[split].contiguous(), xm[split].contiguous()
+            W[:F], Wm[:F] = H[split[:F]], hm[split[:F]]
+            hi0, old0 = hi[split[:F]].contiguous(), old[split[:F]].contiguous()
+            R, _ = lshkm.params_lsh_cosine(int(seeds[0]), L, k, d)
+            lsh = lshkm.LSH(ctx, "cosine", d, k, L, R=R)
+            Q = W[:F].contiguous()
+            parts = {"hash_build": gpu_time(ctx, lambda: lsh.build(W), reps=2)}
+            ptr, idx = lsh.query(Q, True, device=True)
+            parts["query_exclude"] = gpu_time(ctx, lambda: lshkm.cv_exclude(ctx, *lsh.query(Q, True, device=True), 0, F), reps=2)
+            eptr, eidx = lshkm.cv_exclude(ctx, ptr, idx, 0, F)
+            parts["p_closest"] = gpu_time(ctx, lambda: lshkm.p_closest(ctx, W, Q, eptr, eidx, P), reps=2)
+            ni, ns, nc = lshkm.p_closest(ctx, W, Q, eptr, eidx, P)
+            hp = torch.arange(F + 1, dtype=torch.int64, device=ctx.dev)
+            parts["predict"] = gpu_time(ctx, lambda: lshkm.predicted_scores(ctx, W, Wm, Wm[:F], hp, hi0, ni, ns, nc), reps=2)
+            pred = lshkm.predicted_scores(ctx, W, Wm, Wm[:F], hp, hi0, ni, ns, nc)
+            parts["sum"] = gpu_time(ctx, lambda: lshkm.cv_fold_sum(ctx, hi0, old0, pred, eptr), reps=2)
+            ks, cnt, _ = lshkm.cv_fold_sum(ctx, hi0, old0, pred, eptr)
+            ctx.sync()
+            same = float(ks[0]) == fs[0] and int(cnt[0]) == fc[0]
+            cand = int(eptr[-1])
+            emit("lsh_rec_10_fold_validation_A", "users/s", 10 * F, t, None,
+                 f"N={N}, d={d} fp64 users, cosine, k={k}, L={L}, P={P}; mae {mae!r} ({float(mae).hex()}), "
+                 f"{int(fc.sum())} users calculated; fold 0 through the public pieces (ms): "
+                 + ", ".join(f"{n} {v * 1e3:.2f}" for n, v in parts.items())
+                 + f"; {cand} candidates after exclusion ({cand / F:.0f} per user); fold 0 sum equals the driver's: {same}")
+            del X, W, H, lsh, ptr, idx, eptr, eidx
 
     if "csv" in rows:        # VectorReader (vector_reader.hpp:54-85)
         n, d = 200_000, 64
