@@ -6,47 +6,64 @@
 namespace lshkm {
 
 // Rows listed by the fused pass with an uncertified floor (euclidean) or sign
-// (cosine): fix-up pass. Four lanes per listed row, each holding 32 contiguous
-// dims and 8 of the row's tuples (or 2 of its g values); the next row of the
-// group is loaded while the current one is computed, and the projections and
-// per-function constants sit in LDS, so the only global latency per row is
-// the prefetched one. The fp64 products are summed per lane and then across the
-// 4 lanes: hash.hip's bound covers any summation order of the 128 products
-// (depth 34 < 130); the soft-x87 fallback keeps the reference order.
+// (cosine): fix-up pass. Eight lanes per listed row. In load u of a row the
+// group reads 128 contiguous bytes (lane q the 16 at dims 32u + 4q), so one
+// load instruction covers one whole line of each of the wave's 8 rows and a
+// row's four lines are visited once each; lane q ends up with dims
+// {32u + 4q + i}, u < 4, i < 4. With k = 4 (the only k the persistent form
+// hashes with; L <= 8) lane q also holds one whole table, tuples [4q, 4q + 4).
+// Sixteen row registers per lane instead of 32 (two rows are held: the next
+// row of the group is loaded while the current one is computed) keep the
+// kernel under 128 VGPRs, 4 waves per SIMD, and the kernel lives on latency.
+// The projections and per-function constants sit in LDS, so the only global
+// latency per row is the prefetched one.
+//
+// Exactness. The fp64 products are summed per lane and then across the 8
+// lanes, so acc may differ in its last bits from any other order; hash.hip's
+// bound covers every summation order of the 128 products (depth 9 < 130).
+// A floor or sign the bound certifies is therefore the reference's; an
+// uncertified one goes to the soft-x87 chain, which walks the dims in the
+// reference's order (only its index into the LDS image follows the lanes'
+// layout). Tuples, phi and buckets are bit-identical whatever the layout;
+// only the diagnostic STAT_HASH_EXACT may move.
 constexpr int HF_WAVES = 4;
 constexpr int HF_SPLIT = 4;                           // blocks per list segment
-constexpr int HF_G = 4;                               // lanes per listed row
+constexpr int HF_G = 8;                               // lanes per listed row
 constexpr int HF_SLOTS = 64 * HF_WAVES / HF_G;        // rows per block pass
-// LDS image of the projections (fp64): dim r at (r / 32) * HF_QS + (r % 32) *
-// HF_PS; the quarters skewed by 8 words so that the 4 lanes of a row, reading
-// dim 32q + j of the same function, hit different banks (LK <= 32)
+constexpr int HF_XL = FU_D / HF_G;                    // dims per lane
+// LDS image of the projections (fp64): lane q's j-th value (dim 32(j / 4) + 4q +
+// j % 4) at q * HF_QS + j * HF_PS; the lanes' parts skewed by 4 doubles (q *
+// HF_QS = 20q double-banks mod 32: eight different ones) so that the 8 lanes
+// of a row, reading their j-th dim of the same function, hit different banks
+// (LK <= 32)
 constexpr int HF_PS = 33;
-constexpr int HF_QS = 32 * HF_PS + 8;
-constexpr size_t HF_LDS = (size_t)4 * HF_QS * 8 + 32 * (8 + 8 + 4);
-__device__ inline int hf_pidx(int r) { return (r >> 5) * HF_QS + (r & 31) * HF_PS; }
+constexpr int HF_QS = HF_XL * HF_PS + 4;
+constexpr size_t HF_LDS = (size_t)HF_G * HF_QS * 8 + 32 * (8 + 8 + 4);
+__device__ inline int hf_pidx(int r) { return ((r >> 2) & 7) * HF_QS + (((r >> 5) << 2) | (r & 3)) * HF_PS; }
 
-// lane ^ 1 / lane ^ 2 within each quad by DPP quad_perm (VALU moves)
+// lane ^ 1 / lane ^ 2 within each quad by DPP quad_perm, lane i <-> 7 - i
+// within each 8 lanes by row_half_mirror (VALU moves)
 template <int CTRL>
-__device__ inline uint32_t quad_swap(uint32_t v) {
+__device__ inline uint32_t dpp_move(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, false);
 }
 template <int CTRL>
-__device__ inline double quad_swap(double v) {
+__device__ inline double dpp_move(double v) {
     const uint64_t b = (uint64_t)__double_as_longlong(v);
-    const uint64_t lo = quad_swap<CTRL>((uint32_t)b), hi = quad_swap<CTRL>((uint32_t)(b >> 32));
+    const uint64_t lo = dpp_move<CTRL>((uint32_t)b), hi = dpp_move<CTRL>((uint32_t)(b >> 32));
     return __longlong_as_double((long long)((hi << 32) | lo));
 }
-constexpr int QP_X1 = 0xB1, QP_X2 = 0x4E;   // quad_perm [1,0,3,2], [2,3,0,1]
-// sum over the 4 lanes of a row group (a quad, all active together); every
-// lane gets the same value ((v0 + v1) + (v2 + v3) in any lane's operand order)
-__device__ inline double group4_sum(double v) {
-    v += quad_swap<QP_X1>(v);
-    v += quad_swap<QP_X2>(v);
-    return v;
-}
-__device__ inline uint32_t group4_sum(uint32_t v) {
-    v += quad_swap<QP_X1>(v);
-    v += quad_swap<QP_X2>(v);
+template <int CTRL>
+__device__ inline float dpp_move(float v) { return __uint_as_float(dpp_move<CTRL>(__float_as_uint(v))); }
+constexpr int QP_X1 = 0xB1, QP_X2 = 0x4E, HALF_MIRROR = 0x141;   // quad_perm [1,0,3,2], [2,3,0,1]; row_half_mirror
+// sum over the 8 lanes of a row group (all active together); every lane gets
+// the same value (((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7)) in any
+// lane's operand order: the mirror pairs a lane with one of the other quad)
+template <typename T>
+__device__ inline T group_sum(T v) {
+    v += dpp_move<QP_X1>(v);
+    v += dpp_move<QP_X2>(v);
+    v += dpp_move<HALF_MIRROR>(v);
     return v;
 }
 
@@ -69,71 +86,76 @@ __device__ __noinline__ int fixup_sign_x87(const float* xrow, const double* pts,
 struct FixRow {
     int64_t row;
     uint32_t mask;
-    float x[32];       // dims [32q, 32q + 32)
-    int32_t v[8];      // euclidean: tuples [8q, 8q + 8); cosine: g of tables 2q, 2q + 1
+    float x[HF_XL];    // x[4u + i] = dim 32u + 4q + i
+    int32_t v[4];      // euclidean: table q's tuples [4q, 4q + 4); cosine: v[0] = g of table q
 };
+
+// One table's 4 tuples (k = 4) as one 16-B access of 4-B alignment: a caller's
+// tuple buffer need not be 16-B aligned.
+struct alignas(4) Tup4 { int32_t v[4]; };
 
 template <bool COS>
 __device__ inline void fix_load(const FusedArgs& a, unsigned long long ent, int q, FixRow& r) {
     r.row = (int64_t)(ent >> 32);
     r.mask = (uint32_t)ent;
-    const float* xq = a.X + r.row * FU_D + 32 * q;
+    const float* xq = a.X + r.row * FU_D + 4 * q;
 #pragma unroll
-    for (int u = 0; u < 8; u++) {
-        const float4 v = *reinterpret_cast<const float4*>(xq + 4 * u);
+    for (int u = 0; u < HF_XL / 4; u++) {
+        const float4 v = *reinterpret_cast<const float4*>(xq + 32 * u);
         r.x[4 * u] = v.x; r.x[4 * u + 1] = v.y; r.x[4 * u + 2] = v.z; r.x[4 * u + 3] = v.w;
     }
     // unconditional loads (clamped indices; the extra values are never used):
     // a load under a branch makes the compiler wait for it at the merge
+    const int l = min(q, a.L - 1);
     if (COS) {
-        const int32_t* g = (a.bucket ? a.bucket : a.phi) + r.row * a.L;
-#pragma unroll
-        for (int i = 0; i < 2; i++) r.v[i] = g[min(2 * q + i, a.L - 1)];
+        r.v[0] = ((a.bucket ? a.bucket : a.phi) + r.row * a.L)[l];
     } else {
-        const int32_t* t = a.tuples + r.row * a.LK;
+        const Tup4 v = reinterpret_cast<const Tup4*>(a.tuples + r.row * a.LK)[l];
 #pragma unroll
-        for (int i = 0; i < 8; i++) r.v[i] = t[min(8 * q + i, a.LK - 1)];
+        for (int j = 0; j < 4; j++) r.v[j] = v.v[j];
     }
 }
 
 template <bool COS>
-__device__ inline void fix_row(const FusedArgs& a, const double* pts, const double* cpn, const double* ctt,
-                               const int32_t* crv, int q, FixRow& r) {
-    // four independent accumulators per lane (the fp64 FMA chains of 32 left the
-    // waves issue-stalled on their dependencies, 39 % of their cycles): nx only
-    // bounds, and the dot product's bound covers any summation order (depth 12 here)
-    double xq[4] = {0.0, 0.0, 0.0, 0.0};
+__device__ inline void fix_row(const FusedArgs& a, const double* pts, const double* cpn, const double* ctt, int q,
+                               FixRow& r) {
+    // nx >= |x| only bounds, so it is summed in f32 and rounded up (the fp64 form
+    // cost a widening and an fp64 FMA per dim and an fp64 sqrt per row). The
+    // terms are non-negative and the sum is 9 roundings deep: s >= |x|^2 (1 -
+    // 2^-20) less what underflows, < 40 * 2^-126 even with denormals flushed; so
+    // |x|^2 <= s (1 + 2^-15) + 2^-118, whose v_sqrt_f32 (1 ulp) is covered by
+    // 1 + 2^-20. An overflowing or non-finite row gives inf / NaN, no certificate.
+    float xs[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int j = 0; j < 32; j++) xq[j & 3] = fma((double)r.x[j], (double)r.x[j], xq[j & 3]);
-    const double nx = sqrt(group4_sum((xq[0] + xq[1]) + (xq[2] + xq[3])));
+    for (int j = 0; j < HF_XL; j++) xs[j & 3] = fmaf(r.x[j], r.x[j], xs[j & 3]);
+    const float s = group_sum((xs[0] + xs[1]) + (xs[2] + xs[3]));
+    const double nx = (double)__builtin_amdgcn_sqrtf(fmaf(s, 1.f + 0x1p-15f, 0x1p-118f)) * (1.0 + 0x1p-20);
     const float* xrow = a.X + r.row * FU_D;
     const int k = a.k;
     const double iwd = 1.0 / (double)a.w;
     for (uint32_t m = r.mask; m; m &= m - 1) {
         const int f = __builtin_ctz(m);
         const double* pq = pts + q * HF_QS + f;
-        // keep the fp64 widening inside the loop (hoisted, it holds 64 VGPRs)
-#pragma unroll
-        for (int j = 0; j < 32; j++) asm volatile("" : "+v"(r.x[j]));
+        // the dot product: four independent accumulators per lane (one fp64 FMA
+        // chain left the waves issue-stalled on its dependencies); its bound
+        // covers any summation order
         double aq[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int j = 0; j < 32; j++) aq[j & 3] = fma(pq[j * HF_PS], (double)r.x[j], aq[j & 3]);
-        const double acc = group4_sum((aq[0] + aq[1]) + (aq[2] + aq[3]));
+        for (int j = 0; j < HF_XL; j++) aq[j & 3] = fma(pq[j * HF_PS], (double)r.x[j], aq[j & 3]);
+        const double acc = group_sum((aq[0] + aq[1]) + (aq[2] + aq[3]));
         const double P = cpn[f] * nx * (1.0 + 0x1p-40);
         if (COS) {
             const double B = (double)(FU_D + 3) * 0x1p-52 * P + 0x1p-1000;
             int bit;
             if (acc > B && acc < 0x1p1000) bit = 1;
             else if (acc < -B && acc > -0x1p1000) bit = 0;
-            else {                                   // the same decision in all 4 lanes
+            else {                                   // the same decision in all 8 lanes
                 bit = fixup_sign_x87(xrow, pts, f);
                 if (q == 0) atomicAdd(a.stats + STAT_HASH_EXACT, 1ull);
             }
             // g = bits MSB first (CosineGGen): function l*k + i is bit k-1-i of table l
             const int l = f / k, b = 1 << (k - 1 - (f - l * k));
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-                if (l == 2 * q + i) r.v[i] = bit ? (r.v[i] | b) : (r.v[i] & ~b);
+            if (l == q) r.v[0] = bit ? (r.v[0] | b) : (r.v[0] & ~b);
         } else {
             // y by the reciprocal (iw = RN(1/w)): three roundings of 2^-53 each
             // relative, inside the |y| 2^-50 term
@@ -143,46 +165,62 @@ __device__ inline void fix_row(const FusedArgs& a, const double* pts, const doub
                              fabs(y) * 0x1p-50;
             const double lo = floor(y - B), hi = floor(y + B);
             int32_t hv = (int32_t)lo;
-            if (lo != hi) {                          // the same decision in all 4 lanes
+            if (lo != hi) {                          // the same decision in all 8 lanes
                 hv = fixup_floor_x87(xrow, pts, f, tt, a.w);
                 if (q == 0) atomicAdd(a.stats + STAT_HASH_EXACT, 1ull);
             }
 #pragma unroll
-            for (int i = 0; i < 8; i++) r.v[i] = f == 8 * q + i ? hv : r.v[i];
-            if ((f >> 3) == q) a.tuples[r.row * a.LK + f] = hv;
+            for (int i = 0; i < 4; i++) r.v[i] = f == 4 * q + i ? hv : r.v[i];
         }
     }
-    const uint32_t kmask = k >= 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
-    if (COS) {
+}
+
+// Wait here for a row's loads (and the list entry loaded after them). The
+// vector-memory counter retires in order and the number of a row's stores
+// varies, so a wait for the next row's loads placed after the current row's
+// stores also waits for those stores' acknowledgements. The loop waits between
+// the computation and the stores instead: the loads have had the whole
+// computation to land, and the stores stay in flight through the next row's
+// computation.
+__device__ inline void fix_settle(FixRow& r, unsigned long long& ent) {
+    asm volatile("" : "+v"(r.row), "+v"(r.mask), "+v"(ent));
 #pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int l = 2 * q + i;
-            if (l < a.L && (r.mask & (kmask << (l * k)))) {
-                if (a.phi) a.phi[r.row * a.L + l] = r.v[i];
-                if (a.bucket) a.bucket[r.row * a.L + l] = r.v[i];
-            }
+    for (int j = 0; j < HF_XL; j++) asm volatile("" : "+v"(r.x[j]));
+#pragma unroll
+    for (int j = 0; j < 4; j++) asm volatile("" : "+v"(r.v[j]));
+}
+
+// The row's stores, apart from its computation: the kernel's loop waits for the
+// next row's loads between the two (fix_settle). k = 4 (launch_fused sends
+// every other k to the chunked form): lane q's tuples [4q, 4q + 4) are the
+// whole table q, so each lane stores its own table where touched, tuples (the
+// unflagged ones as loaded) and phi / bucket, with no sum across lanes and no
+// loop over the tables for the whole wave.
+template <bool COS>
+__device__ inline void fix_store(const FusedArgs& a, const int32_t* crv, int q, const FixRow& r) {
+    const int k = a.k;
+    const uint32_t kmask = k >= 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
+    const bool touched = q < a.L && (r.mask & (kmask << (q * k)));
+    if (COS) {
+        if (touched) {
+            if (a.phi) a.phi[r.row * a.L + q] = r.v[0];
+            if (a.bucket) a.bucket[r.row * a.L + q] = r.v[0];
         }
         return;
     }
-    // touched tables: phi from the lanes' partial sums of the phi terms (the
-    // uint32 sum wraps the same in any order)
-    uint32_t term[8];
+    // the uint32 sum of the phi terms wraps the same in any order; computed in
+    // every lane (tables >= L hold clamped loads), stored where touched
+    uint32_t hn = 0;
 #pragma unroll
-    for (int i = 0; i < 8; i++) term[i] = 8 * q + i < a.LK ? phi_term(r.v[i], crv[8 * q + i]) : 0u;
-    for (int l = 0; l < a.L; l++) {
-        if (!(r.mask & (kmask << (l * k)))) continue;                // the same in all 4 lanes
-        uint32_t hn = 0;
+    for (int j = 0; j < 4; j++) hn += phi_term(r.v[j], crv[4 * q + j]);
+    if (touched) {
+        Tup4 v;
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int f = 8 * q + i;
-            hn += f >= l * k && f < l * k + k ? term[i] : 0u;
-        }
-        hn = group4_sum(hn);
-        if (q == 0) {
-            const uint32_t ph = phi_final(hn);
-            if (a.phi) a.phi[r.row * a.L + l] = (int32_t)ph;
-            if (a.bucket) a.bucket[r.row * a.L + l] = bucket_fast(ph, a.bdiv);
-        }
+        for (int j = 0; j < 4; j++) v.v[j] = r.v[j];
+        *reinterpret_cast<Tup4*>(a.tuples + r.row * a.LK + 4 * q) = v;
+        const uint32_t ph = phi_final(hn);
+        if (a.phi) a.phi[r.row * a.L + q] = (int32_t)ph;
+        if (a.bucket) a.bucket[r.row * a.L + q] = bucket_fast(ph, a.bdiv);
     }
 }
 
@@ -190,7 +228,7 @@ template <bool COS>
 __global__ __launch_bounds__(64 * HF_WAVES) void hash_fixup_kernel(FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* pts = reinterpret_cast<double*>(smem);   // skewed [128][32]
-    double* cpn = pts + 4 * HF_QS;                   // [32] |p_f| (rounded up)
+    double* cpn = pts + HF_G * HF_QS;                // [32] |p_f| (rounded up)
     double* ctt = cpn + 32;                          // [32] t_f
     int32_t* crv = reinterpret_cast<int32_t*>(ctt + 32);   // [32] r_f
     const int nseg = gridDim.x / HF_SPLIT;       // segments across XCDs (cos_fix_seg_kernel)
@@ -199,10 +237,18 @@ __global__ __launch_bounds__(64 * HF_WAVES) void hash_fixup_kernel(FusedArgs a) 
     if (n == 0) return;                                                 // block-uniform
     const unsigned long long* list = a.hfix + (int64_t)seg * a.seg_rows;
     const int LK = a.LK, LKpad = a.LKpad;
+    // constant trip count and clamped, unconditional loads: all 16 in flight
+    // together (a loop over e < FU_D * 32 with the load under f < LK stayed
+    // rolled, one L2 round trip per step)
+    {
+        const int f = threadIdx.x & 31, fc = min(f, LKpad - 1);
+        double pv[FU_D * 32 / (64 * HF_WAVES)];
 #pragma unroll
-    for (int e = threadIdx.x; e < FU_D * 32; e += 64 * HF_WAVES) {
-        const int r = e >> 5, f = e & 31;
-        pts[hf_pidx(r) + f] = f < LK ? a.PT[r * LKpad + f] : 0.0;
+        for (int i = 0; i < FU_D * 32 / (64 * HF_WAVES); i++)
+            pv[i] = a.PT[((threadIdx.x >> 5) + i * (2 * HF_WAVES)) * LKpad + fc];
+#pragma unroll
+        for (int i = 0; i < FU_D * 32 / (64 * HF_WAVES); i++)
+            pts[hf_pidx((threadIdx.x >> 5) + i * (2 * HF_WAVES)) + f] = f < LK ? pv[i] : 0.0;
     }
     if (threadIdx.x < 32) {
         const int f = threadIdx.x;
@@ -220,10 +266,13 @@ __global__ __launch_bounds__(64 * HF_WAVES) void hash_fixup_kernel(FusedArgs a) 
     FixRow cur, nxt;
     fix_load<COS>(a, list[e], q, cur);
     unsigned long long ent2 = list[min(e + STRIDE, n - 1)];
+    fix_settle(cur, ent2);
     for (; e < n; e += STRIDE) {
         fix_load<COS>(a, ent2, q, nxt);
         ent2 = list[min(e + 2 * STRIDE, n - 1)];
-        fix_row<COS>(a, pts, cpn, ctt, crv, q, cur);
+        fix_row<COS>(a, pts, cpn, ctt, q, cur);
+        fix_settle(nxt, ent2);
+        fix_store<COS>(a, crv, q, cur);
         cur = nxt;
     }
 }
