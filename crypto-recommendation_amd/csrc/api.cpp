@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <random>
 #include <sstream>
 #include <string>
@@ -18,6 +20,21 @@
 namespace lshkm {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
+
+int device_cu_count(int* ncu) {
+    static std::mutex mu;
+    static std::map<int, int> cus;             // device index -> CUs
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return kstatus("hipGetDevice");
+    std::lock_guard<std::mutex> lock(mu);
+    if (!cus.count(dev) &&
+        hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+        cus.erase(dev);
+        return kstatus("hipDeviceGetAttribute");
+    }
+    *ncu = cus[dev];
+    return 0;
+}
 }  // namespace lshkm
 
 using namespace lshkm;

@@ -265,14 +265,7 @@ __global__ __launch_bounds__(AS_THREADS, 2) void assign_mfma_kernel(
                 ambig[slot] = (int32_t)row;
             }
         }
-        const unsigned long long fb = __ballot(fix);
-        if (fb) {
-            const int leader = __builtin_ctzll(fb);
-            unsigned long long base = 0;
-            if (lane == leader) base = atomicAdd(ambig_count + 1, (unsigned long long)__popcll(fb));
-            base = __shfl(base, leader);
-            if (fix) ambig[N + base + __popcll(fb & ((1ull << lane) - 1ull))] = (int32_t)row;
-        }
+        seg_append(fix, (int32_t)row, ambig_count + 1, ambig + N, lane);
         return;
     }
     double accd = 0.0;

@@ -61,6 +61,21 @@ __device__ inline void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Append this lane's entry (where want) to a list segment with fill count
+// *count (LDS or global): one atomic per wave by its first wanting lane, the
+// entries in lane order. Every lane that can want calls it together. (The fused
+// pass's kernels keep the idiom written out: profiles/README.md.)
+template <typename E, typename C>
+__device__ __forceinline__ void seg_append(bool want, E entry, C* count, E* seg, int lane) {
+    const unsigned long long m = __ballot(want);
+    if (!m) return;
+    const int leader = __builtin_ctzll(m);
+    C base = 0;
+    if (lane == leader) base = atomicAdd(count, (C)__popcll(m));
+    base = __shfl(base, leader);
+    if (want) seg[base + __popcll(m & ((1ull << lane) - 1ull))] = entry;
+}
+
 // Grid size for a grid-stride kernel: at least one block, at most cap.
 inline unsigned gsz(int64_t work, int64_t per_block, int64_t cap) {
     int64_t b = (work + per_block - 1) / per_block;
@@ -87,5 +102,8 @@ enum Stat {
 };
 
 constexpr int WAVE = 64;
+
+// CUs of the current device (cached, thread-safe); 0, or -2 with the HIP error recorded.
+int device_cu_count(int* ncu);
 
 }  // namespace lshkm

@@ -309,13 +309,8 @@ static int launch_coin_first_t(hipStream_t s, const T* h, int64_t N, int k, int3
     const int64_t n = N * k;
     const int64_t total = (int64_t)k * hspan;
     if (total <= CF_LDS_MAX && k <= CF_KMAX) {
-        static int cus[64] = {0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return kstatus("hipGetDevice");
-        if (dev < 64 && !cus[dev] &&
-            hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            return kstatus("hipDeviceGetAttribute");
-        const int64_t ncu = dev < 64 && cus[dev] > 0 ? cus[dev] : 256;
+        int ncu = 0;
+        if (device_cu_count(&ncu)) return -2;
         // >= 2048 rows per block so the LDS table's setup and merge stay small
         const int64_t nblk = std::max<int64_t>(1, std::min<int64_t>(4 * ncu, (N + 2047) / 2048));
         const int64_t rpb = ((N + nblk - 1) / nblk + 63) & ~(int64_t)63;

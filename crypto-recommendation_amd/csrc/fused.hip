@@ -67,13 +67,8 @@ int fused_validate(bool hash, const FusedLaunch& f, const FusedArgs& a, bool chu
 
 // One block per CU; the lists' segment size; the workspace checks.
 int fused_plan(bool hash, FusedLaunch& f, FusedArgs& a, FusedPlan& p) {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return kstatus("hipGetDevice");
-    if (dev < 64 && !cus[dev] &&
-        hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return kstatus("hipDeviceGetAttribute");
-    const int ncu = dev < 64 && cus[dev] > 0 ? cus[dev] : 256;
+    int ncu = 0;
+    if (device_cu_count(&ncu)) return -2;
     const int64_t ntiles = (a.N + 31) / 32;
     const int64_t want = (ntiles + FP_WAVES - 1) / FP_WAVES;
     const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(ncu, want));

@@ -14,8 +14,8 @@
 // distance is recomputed in reference order (fp64 chain over j, sqrt).
 // Otherwise the row goes to the exact all-centroid pass (assign.hip).
 // Hash values: y = (dot~ + t)/w in fp64 with the split bound; a floor it
-// cannot certify is redone from the exact row with the fp64 bound of
-// hash.hip, and then, if needed, with the soft-x87 emulation.
+// cannot certify is redone from the exact row with the fp64 bound, and
+// then, if needed, with the soft-x87 emulation (hash_exact.h).
 #include "fused_impl.h"
 
 namespace lshkm {
@@ -39,9 +39,11 @@ __device__ inline void split8(const float* x, half8& hi, half8& lo) {
     }
 }
 
-// Exact (reference-order) hash of one projection from the fp32 row in HBM.
-__device__ int32_t hash_exact_row(const float* __restrict__ xrow, const double* __restrict__ PT, int LKpad, int f,
-                                  float t, float w, double pn, unsigned long long* stats) {
+// Exact (reference-order) hash of one projection from the fp32 row in HBM (as
+// hash_mfma.hip's hmf_exact without its row chunks: inlined here, those cost
+// the kernel a wave of occupancy).
+__device__ int32_t chunked_exact_row(const float* __restrict__ xrow, const double* __restrict__ PT, int LKpad, int f,
+                                     float t, float w, double pn, unsigned long long* stats) {
     double acc = 0.0, xn2 = 0.0;
     for (int j = 0; j < FU_D; j++) {
         const double xj = (double)xrow[j];
@@ -49,16 +51,11 @@ __device__ int32_t hash_exact_row(const float* __restrict__ xrow, const double* 
         acc = fma(PT[(size_t)j * LKpad + f], xj, acc);
     }
     const double P = pn * sqrt(xn2) * (1.0 + 0x1p-40);
-    const double tt = (double)t, ww = (double)w;
-    const double y = (acc + tt) / ww;
-    const double B = ((double)(FU_D + 2) * 0x1p-52 * (P + fabs(tt))) / ww + fabs(y) * 0x1p-51;
-    const double lo = floor(y - B), hi = floor(y + B);
-    if (lo == hi) return (int32_t)lo;
-    sx80 s = sx_zero();
-    for (int j = 0; j < FU_D; j++) s = sx_add_double(s, __dmul_rn(PT[(size_t)j * LKpad + f], (double)xrow[j]));
-    s = sx_add_double(s, tt);
+    const double tt = (double)t;
+    int32_t v;
+    if (hash_decide_floor(acc, P, tt, w, FU_D, v)) return v;
     atomicAdd(stats + STAT_HASH_EXACT, 1ull);
-    return (int32_t)sx_floor_i64(sx_div(s, sx_from_float(w)));
+    return hash_x87_floor([&](int j) { return PT[(size_t)j * LKpad + f]; }, xrow, FU_D, tt, w);
 }
 
 // Load rows [r0, r0 + 64) of a [rows][128] f16 matrix into the padded LDS image.
@@ -146,7 +143,7 @@ __global__ __launch_bounds__(FU_THREADS, 2) void fused_kernel(FusedArgs a) {
             const double lo = floor(y - B), hi = floor(y + B);
             int32_t hv;
             if (lo == hi && x_ok) hv = (int32_t)lo;
-            else hv = hash_exact_row(a.X + row * FU_D, a.PT, a.LKpad, f, a.tv[f], a.w, a.pnorm[f], a.stats);
+            else hv = chunked_exact_row(a.X + row * FU_D, a.PT, a.LKpad, f, a.tv[f], a.w, a.pnorm[f], a.stats);
             hs[lp * 32 + f] = hv;
         }
         __syncthreads();

@@ -282,21 +282,14 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
     unsigned long long* hfix_seg = a.hfix + (int64_t)blockIdx.x * a.seg_rows;
     unsigned long long* cfix_seg = a.cfix ? a.cfix + (int64_t)blockIdx.x * a.seg_rows : nullptr;
     if (HASH) {
-        for (int e = threadIdx.x; e < 32 * 16; e += FH_THREADS) {
-            const int r = e >> 4, g = e & 15;
-            *reinterpret_cast<float4*>(lvh + r * FU_RS + g * 8) = *reinterpret_cast<const float4*>(a.Vh + r * FU_D + g * 8);
-            *reinterpret_cast<float4*>(lvl + r * FU_RS + g * 8) = *reinterpret_cast<const float4*>(a.Vl + r * FU_D + g * 8);
-        }
+        hash_stage_images<FH_THREADS>(a.Vh, a.Vl, lvh, lvl);
         if (threadIdx.x < 32) {
             const int f = threadIdx.x;
             const bool on = f < a.LK;
-            // euclidean: the window in units of y = (acc + t) / w; cosine: of the
-            // inner product itself (hash_mfma.hip)
-            const double iwu = MET == 1 ? 1.0 : (double)(1.0f / a.w) * (1.0 + 0x1p-20);
-            const double tf = MET == 1 || !on ? 0.0 : fabs((double)a.tv[f]);
-            lpn0[f] = on ? (float)((FU_A1H * a.pnorm[f] * (1.0 + 0x1p-20) + FU_A2 * FU_SQRT_D) * iwu * (1.0 + 0x1p-18)) : 0.f;
-            lv10[f] = on ? (float)((FU_A2 * a.v1[f] * (1.0 + 0x1p-20) + (0x1p-40 + 0x1p-23) * tf) * iwu * (1.0 + 0x1p-18) +
-                                   0x1p-126) : 0.f;
+            float P = 0.f, Q = 0.f;
+            if (on) hash_window<MET == 0>(a.pnorm[f], a.v1[f], MET == 0 ? a.tv[f] : 0.f, a.w, P, Q);
+            lpn0[f] = P;
+            lv10[f] = Q;
             lt0[f] = on && MET == 0 ? a.tv[f] : 0.f;
             lr0[f] = on && MET == 0 ? a.rv[f] : 0;
         }
@@ -320,20 +313,9 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
     // this lane's 64 values of row (tile, col) in the B-operand layout (rows past
     // the end read row N-1: their results are never stored)
     auto load_row = [&](int64_t tl, float (&dst)[64]) {
-        if constexpr (ROWS != 0) {
-            const int64_t rr = tl * 32 + col;
-            load_row_gen<ROWS>(a, rr < a.N ? rr : a.N - 1, h, dst);
-            return;
-        }
-        const int64_t rr = tl * 32 + col;
-        const float* xr = a.X + (rr < a.N ? rr : a.N - 1) * FU_D + 8 * h;
-#pragma unroll
-        for (int s = 0; s < 8; s++) {
-            const float4 p0 = *reinterpret_cast<const float4*>(xr + 16 * s);
-            const float4 p1 = *reinterpret_cast<const float4*>(xr + 16 * s + 4);
-            dst[8 * s + 0] = p0.x; dst[8 * s + 1] = p0.y; dst[8 * s + 2] = p0.z; dst[8 * s + 3] = p0.w;
-            dst[8 * s + 4] = p1.x; dst[8 * s + 5] = p1.y; dst[8 * s + 6] = p1.z; dst[8 * s + 7] = p1.w;
-        }
+        const int64_t rr = tl * 32 + col, rc = rr < a.N ? rr : a.N - 1;
+        if constexpr (ROWS != 0) load_row_gen<ROWS>(a, rc, h, dst);
+        else load_row_b(a.X + rc * FU_D + 8 * h, dst);
     };
     PT_DECL
     for (int64_t tile = tfirst + wave; NIMG == 2 ? rd < nround : tile < ntiles; tile += tstride, rd++) {
@@ -343,16 +325,6 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
         load_row(tile, xf);
         half8 bh[8];
         float2v n2a = {0.f, 0.f}, n2b = {0.f, 0.f}, r2 = {0.f, 0.f};
-        // hi part of 8 values (LO: and the lo part), |x|^2 and |x - xh|^2 partial sums
-        auto split_step = [&](int s, half8& lo, auto lo_tag) {
-            split8_hi<decltype(lo_tag)::value>(xf + 8 * s, bh[s], lo, r2);
-#pragma unroll
-            for (int j = 0; j < 8; j += 4) {
-                const float2v u = {xf[8 * s + j], xf[8 * s + j + 1]}, v = {xf[8 * s + j + 2], xf[8 * s + j + 3]};
-                n2a = __builtin_elementwise_fma(u, u, n2a);
-                n2b = __builtin_elementwise_fma(v, v, n2b);
-            }
-        };
         double xn2, nx, nxr, nxh;
         bool x_ok;
         auto finish_norms = [&]() {
@@ -373,7 +345,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
 #pragma unroll
             for (int s = 0; s < 8; s++) {
                 half8 unused;
-                split_step(s, unused, std::false_type{});
+                split_norm_step<false>(xf + 8 * s, bh[s], unused, n2a, n2b, r2);
             }
             finish_norms();
         }
@@ -384,28 +356,18 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
             {
                 const _Float16* vh_row = lvh + col * FU_RS + 8 * h;
                 const _Float16* vl_row = lvl + col * FU_RS + 8 * h;
-                // per 16-dim step: the lo products first, then the hi products into
-                // the same accumulator (16 roundings relative to the step's sum of
-                // |terms|, the lo parts' own roundings ~2^-11 smaller), steps added
-                // in f32 (+7): 23 -> 24 roundings, still inside FU_A1H; one
-                // accumulator fewer than the separate lo chain (fits 168 VGPRs)
                 floatx16 tot;
 #pragma unroll
                 for (int s = 0; s < 8; s++) {
-                    half8 bls;
-                    split_step(s, bls, std::true_type{});
-                    const half8 ah = *reinterpret_cast<const half8*>(vh_row + 16 * s);
-                    const half8 al = *reinterpret_cast<const half8*>(vl_row + 16 * s);
-                    const floatx16 z = {};
-                    floatx16 acc_s = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[s], z, 0, 0, 0);
-                    acc_s = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bls, acc_s, 0, 0, 0);
-                    acc_s = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[s], acc_s, 0, 0, 0);
+                    half8 bl;
+                    split_norm_step<true>(xf + 8 * s, bh[s], bl, n2a, n2b, r2);
+                    const floatx16 acc = hash_tile_step(s, vh_row, vl_row, bh[s], bl);
                     if (s == 0) {
-                        tot = acc_s;
+                        tot = acc;
                     } else {
 #pragma unroll
                         for (int r = 0; r < 16; r += 2) {
-                            const float2v t2 = {tot[r], tot[r + 1]}, a2 = {acc_s[r], acc_s[r + 1]};
+                            const float2v t2 = {tot[r], tot[r + 1]}, a2 = {acc[r], acc[r + 1]};
                             const float2v u2 = t2 + a2;
                             tot[r] = u2.x;
                             tot[r + 1] = u2.y;
@@ -416,22 +378,10 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
                 for (int r = 0; r < 16; r++) acc_hi[r] = tot[r];
             }
             finish_norms();
-            // Certification in f32 (the floor only needs y to ~2^-20): with
-            // u = f32(dot~ + t), y = f32(u * f32(1/w)),
-            //   |y - (x.v + t)/w| <= (Ed + 2^-23 |u| + 2^-40 |t|) / w + 2^-21 |y|,
-            // Ed = A1 |v||x| + A2 (|v|_1 + |x|_1) + 2^-23 |dot~| (the split bound and
-            // the final hi + lo add; the reference's x87 / double-product roundings
-            // are below 2^-50 (|v||x| + |t|)). With |x|_1 <= sqrt(d) |x|, |dot~| <=
-            // |u| + |t| and |u| / w <= |y| (1 + 2^-19), that is at most
-            //   B = |y| G + |x| P_f + Q_f,   G = (2^-22 + 2^-20)(1 + 2^-18),
-            //   P_f = (A1 |v| + A2 sqrt(d)) / w,  Q_f = (A2 |v|_1 + (2^-23 + 2^-40)|t|) / w
-            // (prologue; the 1 + 2^-18 factors cover the f32 roundings of B, y - B,
-            // y + B): floor(y - B) == floor(y + B) certifies the reference's floorl.
-            // hc is an opaque zero: it keeps the per-function constants as LDS
-            // reads inside the loop instead of hoisted VGPRs.
+            // hash_tile.h's certificates; hc, an opaque zero, keeps the per-function
+            // constants as LDS reads inside the loop instead of hoisted VGPRs.
             const float iw = MET == 1 ? 1.f : 1.0f / a.w;
             const float nxf = (float)nx * (1.f + 0x1p-20f);
-            constexpr float G = (0x1p-22f + 0x1p-20f) * (1.f + 0x1p-18f);
             int hc = 0;
             asm volatile("" : "+v"(hc));
             const float* lt = lt0 + hc;
@@ -451,10 +401,9 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         const int f = 4 * l + q;
-                        const float u = acc_hi[4 * g + q];
-                        const float B = fmaf(nxf, lP[f], lQ[f]);
-                        gv = (gv << 1) | (u >= 0.f ? 1 : 0);
-                        if (!(fabsf(u) > B)) fmask |= 1u << f;
+                        int bit;
+                        if (!certify_sign_f32(acc_hi[4 * g + q], nxf, lP[f], lQ[f], bit)) fmask |= 1u << f;
+                        gv = (gv << 1) | bit;
                     }
                     if (a.phi) a.phi[o] = gv;
                     if (a.bucket) a.bucket[o] = gv;
@@ -464,12 +413,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const int f = 4 * l + q;
-                    const float u = acc_hi[4 * g + q] + lt[f];
-                    const float y = u * iw;
-                    const float B = fmaf(fabsf(y), G, fmaf(nxf, lP[f], lQ[f]));
-                    const float lo = floorf(y - B), hi = floorf(y + B);
-                    hv[q] = (int32_t)lo;
-                    if (lo != hi) fmask |= 1u << f;
+                    if (!certify_floor_f32(acc_hi[4 * g + q], lt[f], iw, nxf, lP[f], lQ[f], hv[q])) fmask |= 1u << f;
                 }
                 if (a.tuples) *reinterpret_cast<int4*>(a.tuples + o * 4) = make_int4(hv[0], hv[1], hv[2], hv[3]);
                 uint32_t hn = 0;

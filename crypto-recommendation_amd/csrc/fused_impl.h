@@ -15,9 +15,9 @@
 
 #include "common.h"
 #include "kernels.h"
-#include "softx87.h"
+#include "hash_exact.h"
 #include "exact.h"
-#include "tile.h"
+#include "hash_tile.h"
 #include "fused_args.h"
 
 namespace lshkm {

@@ -115,14 +115,7 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
             load_row_gen<ROWS>(a, valid ? row : a.N - 1, h, xf);
         } else {
             // rows past N read row N-1 (results for them are never written)
-            const float* xr = a.X + (valid ? row : a.N - 1) * FU_D + 8 * h;
-#pragma unroll
-            for (int s = 0; s < 8; s++) {
-                const float4 p0 = *reinterpret_cast<const float4*>(xr + 16 * s);
-                const float4 p1 = *reinterpret_cast<const float4*>(xr + 16 * s + 4);
-                xf[8 * s + 0] = p0.x; xf[8 * s + 1] = p0.y; xf[8 * s + 2] = p0.z; xf[8 * s + 3] = p0.w;
-                xf[8 * s + 4] = p1.x; xf[8 * s + 5] = p1.y; xf[8 * s + 6] = p1.z; xf[8 * s + 7] = p1.w;
-            }
+            load_row_b(a.X + (valid ? row : a.N - 1) * FU_D + 8 * h, xf);
         }
         half8 bh[8], bl[8];
         float2v n2a = {0.f, 0.f}, n2b = {0.f, 0.f};

@@ -70,16 +70,10 @@ __device__ inline T group_sum(T v) {
 // the rare sequential fallbacks, out of line (their registers would lower the
 // occupancy of the whole kernel)
 __device__ __noinline__ int32_t fixup_floor_x87(const float* xrow, const double* pts, int f, double tt, float w) {
-    sx80 sxs = sx_zero();
-    for (int j = 0; j < FU_D; j++) sxs = sx_add_double(sxs, __dmul_rn(pts[hf_pidx(j) + f], (double)xrow[j]));
-    sxs = sx_add_double(sxs, tt);
-    return (int32_t)sx_floor_i64(sx_div(sxs, sx_from_float(w)));
+    return hash_x87_floor([&](int j) { return pts[hf_pidx(j) + f]; }, xrow, FU_D, tt, w);
 }
 __device__ __noinline__ int fixup_sign_x87(const float* xrow, const double* pts, int f) {
-    SxSum sx;
-    sx.init();
-    for (int j = 0; j < FU_D; j++) sx.add(__dmul_rn(pts[hf_pidx(j) + f], (double)xrow[j]));
-    return sx_hash_sign(sx);
+    return hash_x87_sign([&](int j) { return pts[hf_pidx(j) + f]; }, xrow, FU_D);
 }
 
 // One listed row as the group's lane q holds it.
@@ -145,11 +139,8 @@ __device__ inline void fix_row(const FusedArgs& a, const double* pts, const doub
         const double acc = group_sum((aq[0] + aq[1]) + (aq[2] + aq[3]));
         const double P = cpn[f] * nx * (1.0 + 0x1p-40);
         if (COS) {
-            const double B = (double)(FU_D + 3) * 0x1p-52 * P + 0x1p-1000;
             int bit;
-            if (acc > B && acc < 0x1p1000) bit = 1;
-            else if (acc < -B && acc > -0x1p1000) bit = 0;
-            else {                                   // the same decision in all 8 lanes
+            if (!hash_decide_sign(acc, P, FU_D, bit)) {   // the same decision in all 8 lanes
                 bit = fixup_sign_x87(xrow, pts, f);
                 if (q == 0) atomicAdd(a.stats + STAT_HASH_EXACT, 1ull);
             }
@@ -165,7 +156,8 @@ __device__ inline void fix_row(const FusedArgs& a, const double* pts, const doub
                              fabs(y) * 0x1p-50;
             const double lo = floor(y - B), hi = floor(y + B);
             int32_t hv = (int32_t)lo;
-            if (lo != hi) {                          // the same decision in all 8 lanes
+            // outside the int range the reference's FISTP stores INT_MIN: the x87 form
+            if (!(lo == hi && fabs(lo) < 0x1p31)) {  // the same decision in all 8 lanes
                 hv = fixup_floor_x87(xrow, pts, f, tt, a.w);
                 if (q == 0) atomicAdd(a.stats + STAT_HASH_EXACT, 1ull);
             }

@@ -14,16 +14,13 @@
 // wave-uniform scalar loads from a transposed [d][LKpad] fp64 table, so each
 // j step is one LDS read + one cvt + fpw fp64 FMAs per lane.
 //
-// Exactness: the reference sums double-rounded products in x87 long double.
-// fp32 x fp32 products are exact in fp64, so the fp64 FMA chain differs from
-// the long-double chain by at most (d+2) 2^-52 (|v|.|x| + |t|) / w (+ 2^-51 |y|
-// for the final two roundings); a floor (or sign) that this bound cannot
-// certify is recomputed in the same kernel with the soft-x87 emulation
-// (softx87.h), bit for bit what the reference computes. Bytes per point:
+// Exactness: the fp64 FMA chain with a rigorous bound; a floor (or sign) the
+// bound cannot certify is recomputed in the same kernel with the soft-x87
+// emulation, bit for bit what the reference computes (hash_exact.h). Bytes per point:
 // 4d read + 4(L k) tuples + 8 L phi/bucket written.
 #include "common.h"
 #include "kernels.h"
-#include "softx87.h"
+#include "hash_exact.h"
 #include "lshkm_synth.h"
 
 namespace lshkm {
@@ -127,35 +124,18 @@ __global__ __launch_bounds__(HASH_THREADS) void proj_hash_kernel(
             const int f = fb + u;
             if (f >= LK) break;
             const double P = pnorm[f] * xn;
+            // what the fp64 bound cannot decide: sequential x87 semantics
+            const auto proj = [&](int j) { return PT[(size_t)j * LKpad + f]; };
             int32_t hv;
             if (MODE == HM_LSH_EUCLID || MODE == HM_CUBE_EUCLID_H) {
-                const double tt = (double)tvec[f], ww = (double)p.w;
-                const double y = (acc[u] + tt) / ww;
-                const double B = ((double)(d + 2) * 0x1p-52 * (P + fabs(tt)) + 0x1p-1000) / ww + fabs(y) * 0x1p-51;
-                const double lo = floor(y - B), hi = floor(y + B);
-                // certified, and inside the int range (the reference's FISTP stores
-                // INT_MIN outside it); inf / nan never pass
-                if (lo == hi && fabs(lo) < 0x1p31) {
-                    hv = (int32_t)lo;
-                } else {
-                    // Exact: sequential x87 semantics (cust_vector.hpp:117-118, euclidean_h_gen.hpp:75).
-                    SxSum s;
-                    s.init();
-                    for (int j = 0; j < d; j++) s.add(__dmul_rn(PT[(size_t)j * LKpad + f], (double)xr[j]));
-                    hv = sx_hash_floor(s, tt, p.w);
+                const double tt = (double)tvec[f];
+                if (!hash_decide_floor(acc[u], P, tt, p.w, d, hv)) {
+                    hv = hash_x87_floor(proj, xr, d, tt, p.w);
                     if (valid) atomicAdd(stats + STAT_HASH_EXACT, 1ull);
                 }
-            } else {
-                const double B = (double)(d + 3) * 0x1p-52 * P + 0x1p-1000;
-                if (acc[u] > B && acc[u] < 0x1p1000) hv = 1;       // finite: no product overflowed
-                else if (acc[u] < -B && acc[u] > -0x1p1000) hv = 0;
-                else {
-                    SxSum s;
-                    s.init();
-                    for (int j = 0; j < d; j++) s.add(__dmul_rn(PT[(size_t)j * LKpad + f], (double)xr[j]));
-                    hv = sx_hash_sign(s);
-                    if (valid) atomicAdd(stats + STAT_HASH_EXACT, 1ull);
-                }
+            } else if (!hash_decide_sign(acc[u], P, d, hv)) {
+                hv = hash_x87_sign(proj, xr, d);
+                if (valid) atomicAdd(stats + STAT_HASH_EXACT, 1ull);
             }
             if (valid) hs[lane * LK + f] = hv;
         }

@@ -8,22 +8,15 @@
 //   EuclideanFGen's inner h values (euclidean_f_gen.hpp:65-79) and their range;
 //   HypercubeGen over CosineHGen (hypercube_gen.hpp:63-73): the vertex.
 //
-// A wave takes 32 points as the MFMA B operand (lane half h: dims 16s+8h..+7
-// of point lane&31) and the 32 projection rows (hi and lo f16 images, LDS) as
-// A: per 16-dim step the lo products first, then the hi products, into one
-// accumulator; the steps are added in f32. The certificate is the fused
-// kernel's hash tile's (fused.hip): a floor (or a sign) is
-// certified when the rigorous window |acc~ - the reference's x87 value| <=
-// FU_A1H |v||x| + FU_A2 (sqrt(d)|x| + |v|_1) (+ the t and 1/w roundings) lies
-// inside one integer cell (on one side of 0). The others — about 4% of rows
-// at w = 0.4, fewer for larger w and for signs — are listed per block and
-// redone by hash_mfma_fix_kernel from the exact row: the fp64 FMA chain with
-// hash.hip's bound, and the soft-x87 emulation when that bound cannot decide.
+// The split-f16 hash tile and its f32 certificates are hash_tile.h's (shared
+// with the fused pass). The uncertified values -- about 4% of rows
+// at w = 0.4, fewer for larger w and for signs -- are listed per block and
+// redone by hash_mfma_fix_kernel from the exact row (hmf_exact, hash_exact.h).
 // Bytes per point: 512 read + the outputs (LSH euclidean: 4 L k + 4 L).
 #include "common.h"
 #include "kernels.h"
-#include "softx87.h"
-#include "tile.h"
+#include "hash_exact.h"
+#include "hash_tile.h"
 
 namespace lshkm {
 
@@ -79,21 +72,14 @@ __global__ __launch_bounds__(64 * HMF_W, HMF_BPC) void hash_mfma_kernel(HashMfma
     int* lmisc = lval + HMF_W * 32 * HMF_VS;                   // [0] list count, [1] min, [2] max
     constexpr bool EUCLID = MODE == HM_LSH_EUCLID || MODE == HM_CUBE_EUCLID_H;
 
-    for (int e = threadIdx.x; e < 32 * 16; e += 64 * HMF_W) {
-        const int r = e >> 4, g = e & 15;
-        *reinterpret_cast<float4*>(lvh + r * FU_RS + g * 8) = *reinterpret_cast<const float4*>(a.Vh + r * FU_D + g * 8);
-        *reinterpret_cast<float4*>(lvl + r * FU_RS + g * 8) = *reinterpret_cast<const float4*>(a.Vl + r * FU_D + g * 8);
-    }
+    hash_stage_images<64 * HMF_W>(a.Vh, a.Vl, lvh, lvl);
     if (threadIdx.x < 32) {
         const int f = threadIdx.x;
         const bool on = f < a.LK;
-        // euclidean: the window in units of y = (acc + t) / w (fused.hip's hash
-        // tile); cosine: in units of the inner product itself
-        const double iwu = EUCLID ? (double)(1.0f / a.w) * (1.0 + 0x1p-20) : 1.0;
-        const double tf = EUCLID && on ? fabs((double)a.tv[f]) : 0.0;
-        lP[f] = on ? (float)((FU_A1H * a.pnorm[f] * (1.0 + 0x1p-20) + FU_A2 * FU_SQRT_D) * iwu * (1.0 + 0x1p-18)) : 0.f;
-        lQ[f] = on ? (float)((FU_A2 * a.v1[f] * (1.0 + 0x1p-20) + (0x1p-40 + 0x1p-23) * tf) * iwu * (1.0 + 0x1p-18) +
-                             0x1p-126) : 0.f;
+        float P = 0.f, Q = 0.f;
+        if (on) hash_window<EUCLID>(a.pnorm[f], a.v1[f], EUCLID ? a.tv[f] : 0.f, a.w, P, Q);
+        lP[f] = P;
+        lQ[f] = Q;
         lt[f] = on && EUCLID ? a.tv[f] : 0.f;
         lr[f] = on && MODE == HM_LSH_EUCLID ? a.rv[f] : 0;
     }
@@ -107,7 +93,6 @@ __global__ __launch_bounds__(64 * HMF_W, HMF_BPC) void hash_mfma_kernel(HashMfma
     int32_t* lv = lval + wave * 32 * HMF_VS;
     unsigned long long* seg = a.list + (int64_t)blockIdx.x * a.seg_rows;
     const float iw = EUCLID ? 1.0f / a.w : 1.f;
-    constexpr float G = (0x1p-22f + 0x1p-20f) * (1.f + 0x1p-18f);
     int hmin = 0x7FFFFFFF, hmax = (int)0x80000000;
     const _Float16* vh_row = lvh + col * FU_RS + 8 * h;
     const _Float16* vl_row = lvl + col * FU_RS + 8 * h;
@@ -139,12 +124,7 @@ __global__ __launch_bounds__(64 * HMF_W, HMF_BPC) void hash_mfma_kernel(HashMfma
                 n2a = __builtin_elementwise_fma(u, u, n2a);
                 n2b = __builtin_elementwise_fma(v, v, n2b);
             }
-            const half8 ah = *reinterpret_cast<const half8*>(vh_row + 16 * s);
-            const half8 al = *reinterpret_cast<const half8*>(vl_row + 16 * s);
-            const floatx16 z = {};
-            floatx16 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, z, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
+            const floatx16 acc = hash_tile_step(s, vh_row, vl_row, bh, bl);
             if (s == 0) {
                 tot = acc;
             } else {
@@ -166,7 +146,7 @@ __global__ __launch_bounds__(64 * HMF_W, HMF_BPC) void hash_mfma_kernel(HashMfma
         uint32_t fmask = 0;
         // LSH euclidean with k = 4 (the reference default): table l = 2g + h is
         // D registers 4g..4g+3 of lane half h, so tuples, phi and the bucket are
-        // written from registers (fused.hip's layout)
+        // written from registers (the fused pass's layout too)
         const bool k4 = MODE == HM_LSH_EUCLID && k == 4;
 #pragma unroll
         for (int g = 0; g < 4; g++) {
@@ -178,18 +158,8 @@ __global__ __launch_bounds__(64 * HMF_W, HMF_BPC) void hash_mfma_kernel(HashMfma
                 if (f >= LK) continue;
                 int32_t v;
                 bool ok;
-                if (EUCLID) {
-                    const float y = (tot[4 * g + q] + lt[f]) * iw;
-                    const float B = fmaf(fabsf(y), G, fmaf(nxf, lP[f], lQ[f]));
-                    const float lo = floorf(y - B), hi = floorf(y + B);
-                    v = (int32_t)lo;
-                    ok = lo == hi;
-                } else {
-                    const float u = tot[4 * g + q];
-                    const float B = fmaf(nxf, lP[f], lQ[f]);
-                    v = u >= 0.f ? 1 : 0;
-                    ok = fabsf(u) > B;
-                }
+                if (EUCLID) ok = certify_floor_f32(tot[4 * g + q], lt[f], iw, nxf, lP[f], lQ[f], v);
+                else ok = certify_sign_f32(tot[4 * g + q], nxf, lP[f], lQ[f], v);
                 if (!(ok && x_ok)) fmask |= 1u << f;
                 hv4[q] = v;
                 if (!k4) lv[col * HMF_VS + f] = v;
@@ -213,15 +183,7 @@ __global__ __launch_bounds__(64 * HMF_W, HMF_BPC) void hash_mfma_kernel(HashMfma
             }
         }
         fmask |= __shfl_xor(fmask, 32);
-        const unsigned long long fb = __ballot(valid && fmask != 0u && h == 1);
-        if (fb) {
-            const int leader = __builtin_ctzll(fb);
-            int base = 0;
-            if (lane == leader) base = atomicAdd(lmisc, __popcll(fb));
-            base = __shfl(base, leader);
-            if (valid && fmask != 0u && h == 1)
-                seg[base + __popcll(fb & ((1ull << lane) - 1ull))] = ((unsigned long long)row << 32) | fmask;
-        }
+        seg_append(valid && fmask != 0u && h == 1, ((unsigned long long)row << 32) | fmask, lmisc, seg, lane);
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         // outputs, lanes over (point, value) pairs of the tile
@@ -285,9 +247,9 @@ __global__ __launch_bounds__(64 * HMF_W, HMF_BPC) void hash_mfma_kernel(HashMfma
     }
 }
 
-// Exact value of function f for one fp32 row: hash.hip's fp64 FMA chain and
-// bound (the row streamed in 32-dim chunks, the projections read through the
-// cache), then the soft-x87 chain when that bound cannot decide.
+// Exact value of function f for one listed fp32 row: the fp64 FMA chain and its
+// bound (hash_exact.h; the row streamed in 32-dim chunks, the projections read
+// through the cache), then the soft-x87 chain when that bound cannot decide.
 template <bool EUCLID>
 __device__ int32_t hmf_exact(const float* __restrict__ xrow, const double* __restrict__ pt, int LKpad, int f,
                              double tt, float w, double pn, unsigned long long* stats) {
@@ -309,22 +271,12 @@ __device__ int32_t hmf_exact(const float* __restrict__ xrow, const double* __res
         }
     }
     const double P = pn * sqrt(xn2) * (1.0 + 0x1p-40);
-    if (EUCLID) {
-        const double ww = (double)w;
-        const double y = (acc + tt) / ww;
-        const double B = ((double)(FU_D + 2) * 0x1p-52 * (P + fabs(tt)) + 0x1p-1000) / ww + fabs(y) * 0x1p-51;
-        const double lo = floor(y - B), hi = floor(y + B);
-        if (lo == hi && fabs(lo) < 0x1p31) return (int32_t)lo;
-    } else {
-        const double B = (double)(FU_D + 3) * 0x1p-52 * P + 0x1p-1000;
-        if (acc > B && acc < 0x1p1000) return 1;
-        if (acc < -B && acc > -0x1p1000) return 0;
-    }
-    SxSum s;
-    s.init();
-    for (int j = 0; j < FU_D; j++) s.add(__dmul_rn(pt[(size_t)j * LKpad + f], (double)xrow[j]));
+    int32_t v;
+    int bit;
+    if (EUCLID ? hash_decide_floor(acc, P, tt, w, FU_D, v) : hash_decide_sign(acc, P, FU_D, bit)) return EUCLID ? v : bit;
     atomicAdd(stats + STAT_HASH_EXACT, 1ull);
-    return EUCLID ? sx_hash_floor(s, tt, w) : sx_hash_sign(s);
+    const auto proj = [&](int j) { return pt[(size_t)j * LKpad + f]; };
+    return EUCLID ? hash_x87_floor(proj, xrow, FU_D, tt, w) : hash_x87_sign(proj, xrow, FU_D);
 }
 
 constexpr int HMF_FIX_THREADS = 256;
@@ -408,12 +360,8 @@ int launch_hash_mfma(hipStream_t s, int mode, const float* X, int64_t N, const H
         set_error("launch_hash_mfma: needs d = 128, 1 <= L*k <= 32 and the split image");
         return -1;
     }
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return kstatus("hipGetDevice");
-    if (dev < 64 && !cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return kstatus("hipDeviceGetAttribute");
-    const int ncu = dev < 64 && cus[dev] > 0 ? cus[dev] : 256;
+    int ncu = 0;
+    if (device_cu_count(&ncu)) return -2;
     const int64_t ntiles = (N + 31) / 32;
     const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)ncu * HMF_BPC, (ntiles + HMF_W - 1) / HMF_W));
     HashMfmaArgs a;

@@ -1383,14 +1383,10 @@ int launch_rc_terms(hipStream_t s, Pts X, const double* x_mean, int d, const int
     // persistent: the resident waves (LDS-limited) times 2, each walking its
     // items as a pipeline (a grid of 65,536 one-item blocks would pay the
     // pipeline's fill per block)
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return kstatus("launch_rc_terms (device)");
-    if (dev < 64 && !cus[dev] &&
-        hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return kstatus("launch_rc_terms (CU count)");
+    int ncu = 0;
+    if (device_cu_count(&ncu)) return -2;
     const int64_t per_cu = std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)lds_cl);
-    const int64_t resident = (dev < 64 && cus[dev] > 0 ? cus[dev] : 256) * per_cu;
+    const int64_t resident = ncu * per_cu;
     const dim3 cgrid((unsigned)std::min<int64_t>(
         {groups->nitems, (int64_t)RC_TERMS_GMAX, test_switch("LSHKM_TERMS_GRID", "r4") ? 4 * resident : 2 * resident}));
     RcItem* items = reinterpret_cast<RcItem*>(groups->items);

@@ -1,7 +1,8 @@
 // tile.h — the split-f16 MFMA tile helpers shared by the fused hash+assign
-// pass (fused.hip) and the standalone MFMA hash (hash_mfma.hip): operand
-// types, the certification constants of DESIGN.md §4, EuclideanPhi's 32-bit
-// arithmetic (euclidean_phi_gen.hpp:70-92) and the bucket division.
+// pass (fused.hip) and the standalone MFMA hash (hash_mfma.hip; the hash tile
+// itself: hash_tile.h): operand types, the certification constants of DESIGN.md
+// §4, EuclideanPhi's 32-bit arithmetic (euclidean_phi_gen.hpp:70-92) and the
+// bucket division.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,10 +76,6 @@ __device__ inline uint32_t phi_final(uint32_t hn) {
     if (hn >= PHI_M) hn -= PHI_M;
     if (hn >= PHI_M) hn -= PHI_M;
     return hn;
-}
-// phi % nb (cust_hashtable.hpp:68); phi < 2^31
-__device__ inline int32_t bucket_of(uint32_t ph, int64_t nb) {
-    return nb <= 0xFFFFFFFFll ? (int32_t)(ph % (uint32_t)nb) : (int32_t)ph;
 }
 // Certified hashes have |h| < 2^22 and r in [0, 100] (euclidean_phi_gen.hpp:64;
 // ProjTable::r_small), so h * r does not wrap, both operands fit 24 bits (one

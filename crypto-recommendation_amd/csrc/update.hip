@@ -454,18 +454,6 @@ __global__ __launch_bounds__(64) void km_chain_lanes_kernel(const TX* __restrict
     }
 }
 
-// Append entry i to the lane list (order kept within a wave: ballot prefix,
-// one atomic per wave).
-__device__ inline void km_lane_append(bool want, int32_t i, int32_t* __restrict__ list, unsigned int* __restrict__ cnt) {
-    const unsigned long long m = __ballot(want);
-    if (!m) return;
-    const int lane = (int)(threadIdx.x & 63), leader = __builtin_ctzll(m);
-    unsigned int base = 0;
-    if (lane == leader) base = atomicAdd(cnt, (unsigned int)__popcll(m));
-    base = __shfl(base, leader);
-    if (want) list[base + __popcll(m & ((1ull << lane) - 1ull))] = i;
-}
-
 // Per (c, j): the exact sum if the chain provably never rounds, else a flag for
 // the sequential kernel. carry (sharded exact mode): the chain starts from it.
 __global__ void km_fx_finalize_kernel(const KmFx* __restrict__ acc, const int64_t* __restrict__ crow, int K, int d,
@@ -500,7 +488,7 @@ __global__ void km_fx_finalize_kernel(const KmFx* __restrict__ acc, const int64_
     const bool lane_chain = !ok && lanes && cnt <= KM_LANE_MAX;
     if (ok) sums[i] = s;
     else if (!lane_chain) atomicOr(flag + c, 1 << min(31, (int)(i % d) / 64));
-    if (lanes) km_lane_append(lane_chain, (int32_t)i, lanes, lane_cnt);
+    if (lanes) seg_append(lane_chain, (int32_t)i, lane_cnt, lanes, (int)(threadIdx.x & 63));
     if (stat) {
         const unsigned long long nb = __ballot(!ok);
         if (nb && (threadIdx.x & 63) == __builtin_ctzll(nb)) atomicAdd(stat, (unsigned long long)__popcll(nb));
@@ -1145,7 +1133,7 @@ __global__ void km_lane_list_kernel(const uint8_t* __restrict__ mask, int64_t n,
                                     unsigned int* __restrict__ cnt) {
     for (int64_t b = (int64_t)blockIdx.x * blockDim.x; b < n; b += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = b + threadIdx.x;
-        km_lane_append(i < n && mask[i] == 2, (int32_t)i, list, cnt);
+        seg_append(i < n && mask[i] == 2, (int32_t)i, cnt, list, (int)(threadIdx.x & 63));
     }
 }
 

@@ -4,7 +4,10 @@ or sign get their tuples / phi / buckets from the fix-up, and these must be the
 oracle's bit for bit whatever the lanes' layout of a row is. Small shapes that
 reach every path of the kernel: ragged lists, one and several blocks, a tuple
 buffer of 4-byte alignment, the soft-x87 fallback through the LDS image, every
-function of every row, the cosine form, and two calls in a row."""
+function of every row, the cosine form, and two calls in a row. And the three
+hash paths against each other (the fused pass + its fix-up, the standalone MFMA
+hash + its fix kernel, the fp64 kernel) on rows no certificate passes: out of
+the f16 range, non-finite, and with |(x.v + t) / w| beyond the int range."""
 import ctypes as C
 
 import numpy as np
@@ -165,3 +168,69 @@ def test_fixup_repeat_call(ctx, dist_mode):
         Xh = oracle.synth(seed, N, D)
         fixed, _ = _check_euclid(ctx, Xh, 5, 4, 64, dist_mode)
         assert fixed > 0
+
+
+# ---- the three hash paths on the rows that defeat every certificate -------------
+SP_N, SP_K, SP_W = 2048 + 17, 64, 0.01
+
+
+@pytest.fixture(scope="module")
+def special_rows():
+    from test_gpu_hash_mfma import rows
+    X = rows(SP_N, 77)            # zero, 1e-30, x4e4, inf, NaN, subnormal, 3e38, tied grids
+    X[700:720] *= np.float32(3e7)  # |(x.v + t) / w| >= 2^31 at w = 0.01, both signs: the reference stores INT_MIN
+    X[720:740] *= np.float32(2e6)  # ... and around 2^31
+    return np.ascontiguousarray(X, np.float32)
+
+
+def _same(got, want, what, rows=None):
+    for name, u, v in zip(("tuples", "phi", "bucket"), got, want):
+        assert (u is None) == (v is None), (what, name)
+        if u is None:
+            continue
+        if rows is not None:
+            u = u[rows]
+        bad = np.nonzero((u != v).reshape(len(u), -1).any(axis=1))[0]
+        assert bad.size == 0, (what, name, (bad if rows is None else rows[bad])[:20])
+
+
+def _host(ts):
+    return [None if t is None else t.cpu().numpy() for t in ts]
+
+
+@pytest.mark.parametrize("metric,L,k,form", [("euclidean", 5, 4, "persistent"), ("cosine", 5, 4, "persistent"),
+                                             ("euclidean", 3, 7, "chunked")])
+def test_hash_paths_agree_on_special_rows(ctx, sctx, sw, special_rows, monkeypatch, metric, L, k, form):
+    from test_gpu_hash_mfma import fp64_path
+    Xh = special_rows
+    X = to_dev(ctx, Xh)
+    Cd = to_dev(ctx, _centroids(SP_K))
+    nb = 41
+    if metric == "euclidean":
+        V, t, r, _ = lshkm.params_lsh_euclidean(123, L, k, D, SP_W)
+        mk = lambda M, c: M.LSH(c, metric, D, k, L, nb, SP_W, V=V, t=t, r=r)
+    else:
+        R, _ = lshkm.params_lsh_cosine(123, L, k, D)
+        mk = lambda M, c: M.LSH(c, metric, D, k, L, R=R)
+    # the fused pass (chunked: the streaming form, forced in the test build) + its fix-up
+    M, c = (lshkm, ctx) if form == "persistent" else (sw, sctx)
+    if form == "chunked":
+        monkeypatch.setenv("LSHKM_FUSED_FORM", "chunked")
+    fused = _host(M.hash_assign(mk(M, c), X, Cd, None, tuples=True, phi=True, bucket=True,
+                                metric=None if metric == "euclidean" else "cosine")[:3])
+    c.sync()
+    # the standalone MFMA hash + its fix kernel, and the fp64 kernel
+    mfma = _host(mk(lshkm, ctx).hash(X))
+    with fp64_path():
+        fp64 = _host(mk(sw, sctx).hash(X))
+    _same(fused, fp64, "fused pass vs fp64 kernel")
+    _same(mfma, fp64, "MFMA hash vs fp64 kernel")
+    fin = np.nonzero(np.isfinite(Xh).all(axis=1))[0]
+    if metric == "euclidean":
+        want = oracle.lsh_hash_euclid(Xh[fin], V, t, np.float32(SP_W), r, nb)
+        assert (want[0][np.isin(fin, np.arange(700, 720))] == np.int32(-2 ** 31)).any()   # the rows do leave the int range
+    else:
+        og = oracle.lsh_hash_cosine(Xh[fin], R.reshape(L, k, D))
+        want = (None, og, og)
+    _same(fused, want, "fused pass vs oracle", fin)
+    _same(mfma, want, "MFMA hash vs oracle", fin)

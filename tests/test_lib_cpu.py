@@ -93,6 +93,19 @@ def test_softx87_matches_long_double(tmp_path):
     assert "bad=0" in out.stdout
 
 
+def test_hash_certificates_match_long_double(tmp_path):
+    # csrc/hash_exact.h: the fp64 floor / sign decisions and the soft-x87 forms vs
+    # the real long double on > 1e6 rows (random, a few x87 ulps from an integer
+    # and from 0, |y| around 2^31, inf / NaN); a certified value may never differ
+    exe = tmp_path / "hash_cert_check"
+    subprocess.run(["g++", "-O1", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tests", "hash_cert_check.cpp")],
+                   check=True)
+    out = subprocess.run([str(exe), "1000000"], capture_output=True, text=True)
+    print(out.stdout)                         # the declined share
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "bad=0" in out.stdout
+
+
 def test_kmseg_matches_chain(tmp_path):
     # the binade-segment evaluation of the fp64 chain (csrc/kmseg.h) vs the plain chain
     exe = tmp_path / "kmseg_check"
