@@ -498,73 +498,84 @@ int lshkm_lsh_hash_f64(lshkm_lsh lsh, const double* X, int64_t N, int32_t* tuple
 // ------------------------------------------------------------------- Lloyd
 }  // extern "C"
 
-// Kernel path for assignment: d = 128 takes the split-f16 fused kernel
-// (hi-only passes over 512-centroid slices + the 3-product refinement of the
-// rows they list; cosine: normalised centroids), else the f32-MFMA kernel (d <= 256), else the exact pass.
+// Kernel path for assignment: the split-f16 fused pass where one of its forms
+// runs the shape (fused_route, fused_layout.h: fp32 rows of d = 128 -- path 0
+// -- and, K <= 512, fp64 rows and fp32 rows of d < 128 zero-padded dims -- path
+// 3), else the f32-MFMA kernel (d <= 256; fp64 rows rounded to f32 on load, the
+// bound widened accordingly), else the exact pass.
 // LSHKM_ASSIGN_PATH = "f32" / "exact" forces a path (tests compare them).
-// fp64 rows and fp32 rows of d < 128 dims (d <= 128, K <= 512; either metric)
-// take the hi-only form too (path 3: zero-padded dims); other
-// fp64 rows the f32-MFMA kernel (rows rounded to f32 on load, the bound
-// widened accordingly) or the exact pass.
 static int assign_path(int metric, int d, int K, bool f64) {
     if (test_switch("LSHKM_ASSIGN_PATH", "exact")) return 2;
-    const bool f32 = test_switch("LSHKM_ASSIGN_PATH", "f32");
-    if (d == 128 && !f32 && !f64) {
-        if (metric == LSHKM_METRIC_EUCLIDEAN || !test_switch("LSHKM_FUSED_FORM", "chunked")) return 0;
+    if (!test_switch("LSHKM_ASSIGN_PATH", "f32")) {
+        const FusedRoute r = fused_route(metric != LSHKM_METRIC_EUCLIDEAN, f64, d, K, false, 0, 0,
+                                         test_switch("LSHKM_FUSED_FORM", "chunked"));
+        if (r.form != FusedForm::none) return r.rows == 0 ? 0 : 3;
     }
-    if (!f32 && d <= 128 && K <= 512) return 3;
     return assign_dp(d) > 0 ? 1 : 2;
 }
 
-// Euclidean winner distances of the hi-only pass (fp32 rows), per context
-// (lshkm_ctx_set_dist_mode): LSHKM_DIST_CERTIFIED (default) takes them from
-// f32(c) in f32, certified to 2^-20 relative -- inside the 1e-5 relative the
-// north star sets for float distances; cluster IDs stay bit-exact, and a row
-// whose bound fails gets the reference-order fp64 chain. LSHKM_DIST_EXACT: the
-// reference-order fp64 chain for every row (bit-exact distances). The context's
-// mode alone decides (no environment override in the product library).
-static bool fast_dist_on(const lshkm_ctx_s* ctx) {
-    return ctx->dist_mode == LSHKM_DIST_CERTIFIED;
+// One pass for hashing + assignment: an index of the assignment's metric whose
+// split image is on the device (euclidean: fused_ok, r within the fix-up's
+// range), on the shapes a fused form hashes (fused_route: L*k <= 32; cosine k = 4)
+static bool fuse_hash(const lshkm_lsh_s* lsh, int metric, int K, bool f64) {
+    const lshkm::ProjTable& pj = lsh->proj;
+    if (lsh->metric != metric || !(metric == LSHKM_METRIC_EUCLIDEAN ? pj.fused_ok : pj.mfma_ok)) return false;
+    return fused_route(metric != LSHKM_METRIC_EUCLIDEAN, f64, pj.d, K, true, pj.k, pj.LK,
+                       test_switch("LSHKM_FUSED_FORM", "chunked")).form != FusedForm::none;
 }
 
 // K <= 1024, d <= 256: the exact pass scores every centroid in f32 first and
 // runs the exact order only on the candidates the bound leaves (euclidean, and
 // cosine on fp32 rows); LSHKM_EXACT_PASS=full: every centroid
-static bool exact_pruned(Pts X, int d, int K, int metric) {
+bool lshkm::exact_pruned(Pts X, int d, int K, int metric) {
     return K <= 1024 && d <= 256 && !test_switch("LSHKM_EXACT_PASS", "full") &&
            (metric == LSHKM_METRIC_EUCLIDEAN || !X.f64);
 }
 
-// The pruned pass's centroid prep ahead of the fused pass (ws_ct): the listed
-// rows' pass then starts as soon as the refinement ends.
-static int exact_listed_prep(lshkm_ctx ctx, Pts X, int d, const double* C, int K, int metric) {
+static size_t exact_ct_bytes(const AssignJob& q) { return (size_t)q.d * ((q.K + 255) / 256 * 256) * 8; }
+
+int lshkm::exact_listed_prep(lshkm_ctx ctx, const AssignJob& q) {
     int rc;
-    if ((rc = ctx->ws_ct.reserve((size_t)d * ((K + 255) / 256 * 256) * 8))) return rc;
-    return launch_assign_pruned_prep(ctx->stream, X.f64, d, C, K, (float*)ctx->ws_ct.p,
-                                     metric == LSHKM_METRIC_EUCLIDEAN ? 0 : 1);
+    if ((rc = ctx->ws_ct.reserve(exact_ct_bytes(q)))) return rc;
+    return launch_assign_pruned_prep(ctx->stream, q.X.f64, q.d, q.C, q.K, (float*)ctx->ws_ct.p,
+                                     q.metric == LSHKM_METRIC_EUCLIDEAN ? 0 : 1);
 }
 
-// Exact reference-order pass over the rows listed in ws_ambig (count on device).
-// Segmented lists (seg_counts != NULL) come from the persistent fused form.
-// prepped: exact_listed_prep ran for these centroids on this stream.
-static int exact_listed(lshkm_ctx ctx, Pts X, int d, const double* C, int K, int metric,
-                        const unsigned long long* cnt, int64_t N, int32_t* assign, double* dist,
-                        const int32_t* seg_counts = nullptr, int64_t seg_rows = 0, int nseg = 0,
-                        const int32_t* rows = nullptr, bool exact_dist = true, bool prepped = false,
-                        const double* xn2 = nullptr, const double* nbv = nullptr) {
-    if (!rows) rows = (const int32_t*)ctx->ws_ambig.p;
-    const bool prune = exact_pruned(X, d, K, metric);
-    if (!prune && (metric != LSHKM_METRIC_EUCLIDEAN || (!seg_counts && d > 256)))
-        return launch_assign_exact(ctx->stream, X, N, d, C, K, metric, rows, cnt, N, assign, dist, seg_counts,
-                                   seg_rows, nseg, xn2, nbv);
+int lshkm::exact_listed(lshkm_ctx ctx, const AssignJob& q, const RowList& l, bool exact_dist, bool prepped,
+                        const double* xn2, const double* nbv) {
+    const bool prune = exact_pruned(q.X, q.d, q.K, q.metric);
+    if (!prune && (q.metric != LSHKM_METRIC_EUCLIDEAN || (l.nseg == 0 && q.d > 256)))
+        return launch_assign_exact(ctx->stream, q, l, xn2, nbv);
     int rc;
-    if ((rc = ctx->ws_ct.reserve((size_t)d * ((K + 255) / 256 * 256) * 8))) return rc;
-    if (prune)
-        return launch_assign_pruned_list(ctx->stream, X, d, C, K, (float*)ctx->ws_ct.p, rows, cnt, N, assign, dist,
-                                         seg_counts, seg_rows, nseg, metric == LSHKM_METRIC_EUCLIDEAN ? 0 : 1,
-                                         exact_dist ? 1 : 0, prepped);
-    return launch_assign_exact_list(ctx->stream, X, d, C, K, (double*)ctx->ws_ct.p, rows, cnt, N, assign, dist,
-                                    seg_counts, seg_rows, nseg);
+    if ((rc = ctx->ws_ct.reserve(exact_ct_bytes(q)))) return rc;
+    if (prune) return launch_assign_pruned_list(ctx->stream, q, (float*)ctx->ws_ct.p, l, exact_dist ? 1 : 0, prepped);
+    return launch_assign_exact_list(ctx->stream, q, (double*)ctx->ws_ct.p, l);
+}
+
+// The f32-MFMA sequence (d <= 256): certified scores, the listed exact pass,
+// the cosine distance fix-ups.
+static int assign_f32_mfma(lshkm_ctx ctx, const AssignJob& q) {
+    hipStream_t s = ctx->stream;
+    const int DP = assign_dp(q.d), Kpad = (q.K + 63) / 64 * 64;
+    const int64_t N = q.N;
+    int rc;
+    if ((rc = ctx->ws_c32.reserve((size_t)Kpad * DP * 4)) || (rc = ctx->ws_cconst.reserve((size_t)3 * Kpad * 4)) ||
+        (rc = ctx->ws_ambig.reserve((size_t)std::max<int64_t>(N, 1) * 2 * 4)) ||   // ambiguous rows | cosine fix-ups
+        (rc = ctx->ws_counter.reserve(64)))
+        return rc;
+    unsigned long long* cnt = (unsigned long long*)ctx->ws_counter.p;
+    LSHKM_HIP(hipMemsetAsync(cnt, 0, 16, s));
+    if ((rc = launch_centroid_prep(s, q.C, q.K, Kpad, q.d, DP, q.metric, q.X.f64, (float*)ctx->ws_c32.p, (float*)ctx->ws_cconst.p))) return rc;
+    if ((rc = launch_assign_mfma(s, q.X, N, q.d, DP, q.C, q.K, Kpad, q.metric, (const float*)ctx->ws_c32.p, (const float*)ctx->ws_cconst.p,
+                                 q.assign, q.dist, (int32_t*)ctx->ws_ambig.p, cnt))) return rc;
+    RowList l;
+    l.p = (int32_t*)ctx->ws_ambig.p; l.count = cnt; l.bound = N;
+    if ((rc = exact_listed(ctx, q, l, true, false, nullptr, nullptr))) return rc;
+    if (q.metric != LSHKM_METRIC_EUCLIDEAN &&
+        ((rc = launch_cos_fix(s, q.X, N, q.d, q.C, (const int32_t*)ctx->ws_ambig.p + N, cnt + 1, q.assign, q.dist)) ||
+         (rc = launch_add_counter(s, (unsigned long long*)ctx->stats.p + STAT_COS_FIX, cnt + 1)))) return rc;
+    // ambiguous-count statistic
+    return launch_add_counter(s, (unsigned long long*)ctx->stats.p + STAT_ASSIGN_AMBIG, cnt);
 }
 
 // force_exact: exact distances whatever the context's mode (range
@@ -573,173 +584,25 @@ static int assign_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const double* C, 
                        const int32_t* src_rows_host, int32_t* assign, double* dist, lshkm_lsh lsh, int32_t* tuples,
                        int32_t* phi, int32_t* bucket, bool force_exact = false) {
     hipStream_t s = ctx->stream;
-    const int DP = assign_dp(d);
     const int path = assign_path(metric, d, K, X.f64);
-    // one pass for hashing + assignment: the euclidean index with euclidean
-    // Lloyd (fused_ok: d = 128, L*k <= 32), or the cosine index with cosine Lloyd
-    // on the hi-only form (k = 4)
-    const bool fuse_hash = lsh && path == 0 && lsh->metric == metric &&
-                           (metric == LSHKM_METRIC_EUCLIDEAN ? lsh->proj.fused_ok
-                                                             : (lsh->proj.mfma_ok && lsh->proj.k == 4));
+    AssignRequest q;
+    q.X = X; q.N = N; q.d = d; q.C = C; q.K = K; q.metric = metric; q.assign = assign; q.dist = dist;
+    q.tuples = tuples; q.phi = phi; q.bucket = bucket; q.force_exact = force_exact;
+    if (lsh && path == 0 && fuse_hash(lsh, metric, K, X.f64)) q.lsh = lsh;
     int rc;
-    if (lsh && !fuse_hash && (rc = hash_rows(ctx, lsh->metric == LSHKM_METRIC_EUCLIDEAN ? HM_LSH_EUCLID : HM_LSH_COSINE,
-                                             X, N, lsh->proj, lsh->nb,
-                                             lsh->metric == LSHKM_METRIC_EUCLIDEAN ? tuples : nullptr, phi, bucket,
-                                             nullptr))) { LSHKM_LAUNCH_CHECK(); return rc; }
-    if (path == 0 || path == 3) {
-        const int rows_kind = path == 3 ? (X.f64 ? 2 : 1) : 0;
-        const int Kpad = (K + 63) / 64 * 64;
-        const bool cosine = metric != LSHKM_METRIC_EUCLIDEAN;
-        // euclidean winner distances: the certified f32 form (default) or the
-        // reference-order fp64 chain (LSHKM_DIST_EXACT)
-        const bool fast = !cosine && rows_kind != 2 && !force_exact && fast_dist_on(ctx);
-        // exact distances of the hi-only pass: rows whose chain met an inexact
-        // square (glibc's pow(x, 2) may differ from x*x) are listed for the fix-up
-        const bool pwfix = !cosine && !fast;
-        // ws_hfix regions: [hash fix-ups] then, cosine: [declines of the hi-only
-        // pass][declines of the refinement]; euclidean exact: [pow fix-ups]
-        const int nfix_regions = 1 + (cosine ? 2 : 0) + (pwfix ? 1 : 0);
-        const int64_t list_cap = N + FUSED_LIST_SLACK;
-        const int64_t part_tiles = std::max<int64_t>((N + 31) / 32, (list_cap + 31) / 32 + FUSED_MAX_SEGS);
-        if ((rc = ctx->ws_c32.reserve((size_t)Kpad * 128 * 2 * 2)) ||
-            (rc = ctx->ws_cconst.reserve((size_t)(Kpad + 8) * 4 + (size_t)Kpad * 8)) ||
-            (rc = ctx->ws_ambig.reserve((size_t)(N + FUSED_LIST_SLACK) * 4)) || (rc = ctx->ws_counter.reserve(64)) ||
-            (rc = ctx->ws_seg.reserve((size_t)FUSED_MAX_SEGS * 2 * 4)) ||
-            ((fuse_hash || cosine || pwfix) && (rc = ctx->ws_hfix.reserve((size_t)(N + FUSED_LIST_SLACK) * 8 * nfix_regions))) ||
-            ((cosine || pwfix) && (rc = ctx->ws_seg3.reserve((size_t)FUSED_MAX_SEGS * 2 * 4))) ||
-            (Kpad > 256 && (rc = ctx->ws_part.reserve((size_t)part_tiles * 64 * 16))) ||
-            (rc = ctx->ws_ambig2.reserve((size_t)list_cap * 4)) ||
-            (rc = ctx->ws_seg2.reserve((size_t)FUSED_MAX_SEGS * 2 * 4)) ||
-            (fuse_hash && !cosine && !tuples && (rc = ctx->ws_tuples.reserve((size_t)std::max<int64_t>(N, 1) * lsh->proj.LK * 4))))
-            return rc;
-        unsigned long long* cnt = (unsigned long long*)ctx->ws_counter.p;
-        LSHKM_HIP(hipMemsetAsync(cnt, 0, 32, s));         // [0] ambiguous rows, [1] hash fix-up rows, [2] refined rows, [3] cosine declines / pow fix-ups
-        _Float16* Ch = (_Float16*)ctx->ws_c32.p;
-        _Float16* Cl = Ch + (size_t)Kpad * 128;
-        float* cbound = (float*)ctx->ws_cconst.p;          // 4 floats, then cnh[Kpad]
-        float* cnh = cbound + 8;
-        double* nbv = (double*)(cnh + Kpad);               // cosine: [Kpad] sequential |c|^2 (Kpad % 64 == 0: aligned)
-        float* C32 = nullptr;
-        float* rn32 = nullptr;
-        // the f32 image also serves the K <= 256 gather when every centroid value
-        // is an f32 (dataset rows: the first Lloyd iteration), exact as doubles
-        // (test switch LSHKM_GATHER32=0: the fp64 winner rows always)
-        if (fast || (!cosine && rows_kind != 2 && Kpad <= 256 && !test_switch("LSHKM_GATHER32", "0"))) {
-            if ((rc = ctx->ws_cf32.reserve((size_t)Kpad * 128 * 4 + (size_t)Kpad * 4))) return rc;
-            C32 = (float*)ctx->ws_cf32.p;
-            rn32 = C32 + (size_t)Kpad * 128;
-        }
-        double* C64p = nullptr;                            // d < 128: zero-padded fp64 centroids
-        if (rows_kind != 0 && d != 128) {
-            if ((rc = ctx->ws_c64p.reserve((size_t)Kpad * 128 * 8))) return rc;
-            C64p = (double*)ctx->ws_c64p.p;
-        }
-        // the timed fused pass starts before the centroid prep
-        if (ctx->timing) LSHKM_HIP(hipEventRecord(ctx->tev[0], s));
-        if ((rc = launch_fused_prep(s, C, K, Kpad, Ch, Cl, cnh, cbound, cosine ? 1 : 0, nbv, C32, rn32, d, C64p))) { LSHKM_LAUNCH_CHECK(); return rc; }
-        const bool xprep = exact_pruned(X, d, K, metric);
-        if (xprep && (rc = exact_listed_prep(ctx, X, d, C, K, metric))) { LSHKM_LAUNCH_CHECK(); return rc; }
-        FusedLaunch f;
-        FusedArgs& a = f.a;
-        a.C32 = C32; a.rn32 = rn32; a.fast_dist = fast ? 1 : 0;
-        f.rows = rows_kind; a.d = d; a.Cd = C;
-        a.X = X.f64 ? nullptr : X.f(); a.X64 = X.f64 ? X.d() : nullptr;
-        a.N = N; a.Ch = Ch; a.Cl = Cl; a.cnh = cnh; a.cbound = cbound; a.C64 = C64p ? C64p : C; a.Kpad = Kpad;
-        a.assign = assign; a.dist = dist; a.ambig = (int32_t*)ctx->ws_ambig.p; a.ambig_count = cnt;
-        a.stats = (unsigned long long*)ctx->stats.p;
-        f.list_cap = N + FUSED_LIST_SLACK;
-        f.seg_counts = (int32_t*)ctx->ws_seg.p;
-        f.seg_cap = FUSED_MAX_SEGS;
-        if (Kpad > 256) { f.part = ctx->ws_part.p; f.part_bytes = part_tiles * 64 * 16; }
-        f.list2 = (int32_t*)ctx->ws_ambig2.p;
-        f.seg_counts2 = (int32_t*)ctx->ws_seg2.p;
-        f.refined = cnt + 2;
-        if (pwfix) {
-            a.cfix = (unsigned long long*)ctx->ws_hfix.p + (N + FUSED_LIST_SLACK);
-            a.cfix_counts = (int32_t*)ctx->ws_seg3.p;
-            a.cfix_count = cnt + 3;
-        }
-        if (cosine && rows_kind == 2) {
-            if ((rc = ctx->ws_xn2.reserve((size_t)std::max<int64_t>(N, 1) * 8))) return rc;
-            if ((rc = launch_row_sumsq(s, X.d(), N, d, (double*)ctx->ws_xn2.p))) { LSHKM_LAUNCH_CHECK(); return rc; }
-            a.xn2 = (const double*)ctx->ws_xn2.p;
-        }
-        if (cosine) {
-            f.metric = 1; a.nbv = nbv;
-            a.hfix = (unsigned long long*)ctx->ws_hfix.p; a.hfix_count = cnt + 1;
-            a.cfix = a.hfix + (N + FUSED_LIST_SLACK);
-            a.cfix_counts = (int32_t*)ctx->ws_seg3.p;
-            a.cfix_count = cnt + 3;
-            f.hfix2 = a.cfix + (N + FUSED_LIST_SLACK);
-        }
-        if (fuse_hash) {
-            const ProjTable& pj = lsh->proj;
-            a.Vh = pj.vh_d.as<_Float16>(); a.Vl = pj.vl_d.as<_Float16>(); a.PT = pj.PT_d.as<double>();
-            a.tv = pj.t_d.as<float>(); a.pnorm = pj.pn_d.as<double>(); a.v1 = pj.v1_d.as<double>();
-            a.rv = pj.r_d.as<int32_t>(); a.w = pj.w; a.L = pj.L; a.k = pj.k; a.LK = pj.LK; a.LKpad = pj.LKpad;
-            a.nb = lsh->nb; a.phi = phi; a.bucket = bucket;
-            a.tuples = cosine ? nullptr : tuples ? tuples : (int32_t*)ctx->ws_tuples.p;
-            a.hfix = (unsigned long long*)ctx->ws_hfix.p; a.hfix_count = cnt + 1;
-        }
-        if (fuse_hash && ctx->side_init() == 0) {
-            f.side = ctx->side_stream; f.fork = ctx->fork_ev; f.join = ctx->join_ev;
-            f.defer_join = !cosine;        // euclidean: the exact pass also overlaps the fix-up
-            if (ctx->timing) f.side_timing = ctx->tev[2];
-        }
-        ctx->tev_side = false;
-        // the side stream's hash fix-up writes only tuples / phi / bucket: joined
-        // before this call's last launch, and on every error path after the fork
-        struct SideJoin {
-            lshkm_ctx c;
-            bool pending = false;
-            ~SideJoin() { if (pending) (void)hipStreamSynchronize(c->side_stream); }
-        } sj{ctx};
-        rc = launch_fused(s, fuse_hash, f);
-        sj.pending = f.join_pending;
-        ctx->tev_side = f.side_timed;      // only a launch that recorded tev[2] extends the pass
-        if (rc) { LSHKM_LAUNCH_CHECK(); return rc; }
-        if (ctx->timing) LSHKM_HIP(hipEventRecord(ctx->tev[1], s));
-        if ((rc = exact_listed(ctx, X, d, C, K, metric, cnt, N, assign, dist, f.nseg ? f.final_counts : nullptr,
-                               f.seg_rows, f.nseg, f.nseg ? f.final_list : nullptr, !fast, xprep,
-                               cosine ? f.a.xn2 : nullptr, cosine ? nbv : nullptr))) { LSHKM_LAUNCH_CHECK(); return rc; }
-        if (sj.pending) {
-            LSHKM_HIP(hipStreamWaitEvent(s, f.join, 0));
-            sj.pending = false;
-        }
-        {
-            int di[3], n = 0;
-            const unsigned long long* sp[3];
-            di[n] = STAT_REFINED; sp[n++] = cnt + 2;
-            if (fuse_hash) { di[n] = STAT_HASH_FIX; sp[n++] = cnt + 1; }
-            di[n] = STAT_ASSIGN_AMBIG; sp[n++] = cnt;
-            if ((rc = launch_add_counters(s, (unsigned long long*)ctx->stats.p, n, di, sp))) { LSHKM_LAUNCH_CHECK(); return rc; }
-        }
-        if (cosine || pwfix) {
-            if ((rc = launch_cos_fix_seg(s, X, d, C, f.ncos_lists, f.cos_list, f.cos_counts, f.seg_rows, f.nseg, assign,
-                                         dist, cosine ? 1 : 0, cosine ? f.a.xn2 : nullptr, cosine ? nbv : nullptr))) { LSHKM_LAUNCH_CHECK(); return rc; }
-            if ((rc = launch_add_counter(s, (unsigned long long*)ctx->stats.p + (cosine ? STAT_COS_FIX : STAT_POW_FIX), cnt + 3))) { LSHKM_LAUNCH_CHECK(); return rc; }
-        }
-    } else if (path == 1) {
-        const int Kpad = (K + 63) / 64 * 64;
-        if ((rc = ctx->ws_c32.reserve((size_t)Kpad * DP * 4)) || (rc = ctx->ws_cconst.reserve((size_t)3 * Kpad * 4)) ||
-            (rc = ctx->ws_ambig.reserve((size_t)std::max<int64_t>(N, 1) * 2 * 4)) ||   // ambiguous rows | cosine fix-ups
-            (rc = ctx->ws_counter.reserve(64)))
-            return rc;
-        unsigned long long* cnt = (unsigned long long*)ctx->ws_counter.p;
-        LSHKM_HIP(hipMemsetAsync(cnt, 0, 16, s));
-        if ((rc = launch_centroid_prep(s, C, K, Kpad, d, DP, metric, X.f64, (float*)ctx->ws_c32.p, (float*)ctx->ws_cconst.p))) { LSHKM_LAUNCH_CHECK(); return rc; }
-        if ((rc = launch_assign_mfma(s, X, N, d, DP, C, K, Kpad, metric, (const float*)ctx->ws_c32.p, (const float*)ctx->ws_cconst.p,
-                                     assign, dist, (int32_t*)ctx->ws_ambig.p, cnt))) { LSHKM_LAUNCH_CHECK(); return rc; }
-        if ((rc = exact_listed(ctx, X, d, C, K, metric, cnt, N, assign, dist))) { LSHKM_LAUNCH_CHECK(); return rc; }
-        if (metric != LSHKM_METRIC_EUCLIDEAN &&
-            ((rc = launch_cos_fix(s, X, N, d, C, (const int32_t*)ctx->ws_ambig.p + N, cnt + 1, assign, dist)) ||
-             (rc = launch_add_counter(s, (unsigned long long*)ctx->stats.p + STAT_COS_FIX, cnt + 1)))) { LSHKM_LAUNCH_CHECK(); return rc; }
-        // ambiguous-count statistic
-        if ((rc = launch_add_counter(s, (unsigned long long*)ctx->stats.p + STAT_ASSIGN_AMBIG, cnt))) { LSHKM_LAUNCH_CHECK(); return rc; }
-    } else {
+    if (lsh && !q.lsh && (rc = hash_rows(ctx, lsh->metric == LSHKM_METRIC_EUCLIDEAN ? HM_LSH_EUCLID : HM_LSH_COSINE,
+                                         X, N, lsh->proj, lsh->nb,
+                                         lsh->metric == LSHKM_METRIC_EUCLIDEAN ? tuples : nullptr, phi, bucket,
+                                         nullptr))) { LSHKM_LAUNCH_CHECK(); return rc; }
+    if (path == 0 || path == 3) rc = fused_assign(ctx, q);
+    else if (path == 1) rc = assign_f32_mfma(ctx, q);
+    else {
         // Exact reference-order pass over every centroid (cosine metric, or d > 256).
-        if ((rc = launch_assign_exact(s, X, N, d, C, K, metric, nullptr, nullptr, N, assign, dist))) { LSHKM_LAUNCH_CHECK(); return rc; }
+        RowList all;
+        all.bound = N;
+        rc = launch_assign_exact(s, q, all);
     }
+    if (rc) { LSHKM_LAUNCH_CHECK(); return rc; }
     if (src_rows_host) {
         if ((rc = ctx->ws_src.reserve((size_t)K * 4))) return rc;
         // The same rows as the previous override already sit in ws_src (Lloyd

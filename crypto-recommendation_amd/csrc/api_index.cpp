@@ -27,17 +27,16 @@ int lshkm::hash_rows(lshkm_ctx ctx, int mode, Pts X, int64_t N, const ProjTable&
     unsigned long long* stats = (unsigned long long*)ctx->stats.p;
     int rc;
     if (!X.f64 && pj.mfma_ok && !force64) {
-        const int64_t cap = N + FUSED_LIST_SLACK;
         // the fix-up pass rebuilds a table's phi from the stored tuples
-        if (mode == HM_LSH_EUCLID && !out_h) {
-            if ((rc = ctx->ws_tuples.reserve((size_t)N * pj.LK * 4))) return rc;
-            out_h = ctx->ws_tuples.as<int32_t>();
-        }
-        if ((rc = ctx->ws_hfix.reserve((size_t)cap * 8)) || (rc = ctx->ws_seg.reserve((size_t)FUSED_MAX_SEGS * 2 * 4)))
+        const HashLayout l = hash_layout(N, pj.LK, mode == HM_LSH_EUCLID && !out_h);
+        if ((l.tuples && (rc = ctx->ws_tuples.reserve(l.tuples))) || (rc = ctx->ws_hfix.reserve(l.fix)) ||
+            (rc = ctx->ws_seg.reserve(l.seg1)))
             return rc;
+        if (l.tuples) out_h = ctx->ws_tuples.as<int32_t>();
+        RecList list;
+        list.p = ctx->ws_hfix.as<unsigned long long>(); list.counts = ctx->ws_seg.as<int32_t>(); list.bound = l.list_cap;
         const bool w16 = want16 && mode == HM_CUBE_EUCLID_H;
-        if ((rc = launch_hash_mfma(ctx->stream, mode, X.f(), N, pj.mfma_params(nb), out_h, out_phi, out_bucket, mm,
-                                   (unsigned long long*)ctx->ws_hfix.p, cap, (int32_t*)ctx->ws_seg.p, FUSED_MAX_SEGS * 2,
+        if ((rc = launch_hash_mfma(ctx->stream, mode, X.f(), N, pj.mfma_params(nb), out_h, out_phi, out_bucket, mm, list,
                                    stats, w16)))
             return rc;
         if (h16) *h16 = w16;

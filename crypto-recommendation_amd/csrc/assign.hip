@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256) void assign_exact_kernel(
     if (seg_counts) {            // XE_SPLIT blocks per segment of the persistent fused form's list
         const int seg = blockIdx.x % (gridDim.x / XE_SPLIT);   // segments across XCDs (cos_fix_seg_kernel)
         rows += (int64_t)seg * seg_rows;
-        total = seg_counts[2 * seg];
+        total = seg_counts[SEG_SLOTS * seg + SEG_ROWS];
         wglobal = (int64_t)(blockIdx.x / (gridDim.x / XE_SPLIT)) * 4 + (threadIdx.x >> 6);
         nw = XE_SPLIT * 4;
     }
@@ -444,10 +444,15 @@ __global__ __launch_bounds__(256) void assign_exact_kernel(
     }
 }
 
-int launch_assign_exact(hipStream_t s, Pts X, int64_t N, int d, const double* C, int K, int metric,
-                        const int32_t* rows, const unsigned long long* row_count, int64_t max_rows,
-                        int32_t* assign, double* dist, const int32_t* seg_counts, int64_t seg_rows, int nseg,
-                        const double* xn2, const double* nbv) {
+int launch_assign_exact(hipStream_t s, const AssignJob& q, const RowList& l, const double* xn2, const double* nbv) {
+    const Pts X = q.X;
+    const int64_t N = q.N, max_rows = l.bound, seg_rows = l.seg_rows;
+    const int d = q.d, K = q.K, metric = q.metric, nseg = l.nseg;
+    const double* C = q.C;
+    const int32_t *rows = l.p, *seg_counts = l.seg_counts();
+    const unsigned long long* row_count = l.count;
+    int32_t* assign = q.assign;
+    double* dist = q.dist;
     if (max_rows <= 0) return 0;
     // rows == NULL: every row (fallback path); else a device-counted list that is
     // usually ~0.3% of the rows: one block per CU, waves loop over the list.
@@ -492,7 +497,7 @@ __global__ __launch_bounds__(64 * XB_WAVES) void assign_exact_batch_kernel(
         const int nseg = gridDim.x / XB_SPLIT;   // segments across XCDs (cos_fix_seg_kernel)
         const int seg = blockIdx.x % nseg, part = blockIdx.x / nseg;
         rows += (int64_t)seg * seg_rows;
-        total = seg_counts[2 * seg];
+        total = seg_counts[SEG_SLOTS * seg + SEG_ROWS];
         g0 = (int64_t)part * XB_WAVES + wave;
         gstride = (int64_t)XB_SPLIT * XB_WAVES;
     } else {
@@ -765,7 +770,7 @@ __global__ __launch_bounds__(64 * XP_WAVES) void assign_pruned_kernel(
         const int nseg = gridDim.x / XP_SPLIT;   // segments across XCDs (cos_fix_seg_kernel)
         const int seg = blockIdx.x % nseg, part = blockIdx.x / nseg;
         rows += (int64_t)seg * seg_rows;
-        total = seg_counts[2 * seg];
+        total = seg_counts[SEG_SLOTS * seg + SEG_ROWS];
         g0 = (int64_t)part * XP_WAVES + wave;
         gstride = (int64_t)XP_SPLIT * XP_WAVES;
     } else {
@@ -972,7 +977,7 @@ __global__ __launch_bounds__(64 * XP_WAVES) void assign_pruned_wide_kernel(
     // (per-segment waves left the pass waiting on the fullest segments)
     int64_t ngroups;
     if (seg_counts) {
-        for (int sg = threadIdx.x; sg < nseg; sg += 64 * XP_WAVES) gpre[sg + 1] = (seg_counts[2 * sg] + R - 1) / R;
+        for (int sg = threadIdx.x; sg < nseg; sg += 64 * XP_WAVES) gpre[sg + 1] = (seg_counts[SEG_SLOTS * sg + SEG_ROWS] + R - 1) / R;
         __syncthreads();
         if (threadIdx.x == 0) {
             gpre[0] = 0;
@@ -998,7 +1003,7 @@ __global__ __launch_bounds__(64 * XP_WAVES) void assign_pruned_wide_kernel(
             }
             grows = rows + (int64_t)lo * seg_rows;
             gbase = (g - gpre[lo]) * R;
-            cnt = seg_counts[2 * lo];
+            cnt = seg_counts[SEG_SLOTS * lo + SEG_ROWS];
         } else {
             grows = rows;
             gbase = g * R;
@@ -1140,10 +1145,16 @@ int launch_assign_pruned_prep(hipStream_t s, bool xf64, int d, const double* C, 
     return kstatus("exact_prep_kernel");
 }
 
-int launch_assign_pruned_list(hipStream_t s, Pts X, int d, const double* C, int K, float* ws,
-                              const int32_t* rows, const unsigned long long* row_count, int64_t max_rows,
-                              int32_t* assign, double* dist, const int32_t* seg_counts, int64_t seg_rows, int nseg,
-                              int metric, int exact_dist, bool prepped) {
+int launch_assign_pruned_list(hipStream_t s, const AssignJob& q, float* ws, const RowList& l, int exact_dist,
+                              bool prepped) {
+    const Pts X = q.X;
+    const int64_t max_rows = l.bound, seg_rows = l.seg_rows;
+    const int d = q.d, K = q.K, nseg = l.nseg, metric = q.metric == 0 ? 0 : 1;   // 1: cosine
+    const double* C = q.C;
+    const int32_t *rows = l.p, *seg_counts = l.seg_counts();
+    const unsigned long long* row_count = l.count;
+    int32_t* assign = q.assign;
+    double* dist = q.dist;
     if (max_rows <= 0) return 0;
     if (d > XB_DMAX || K > 1024 || (seg_counts && nseg <= 0)) {
         set_error("launch_assign_pruned_list: unsupported shape");
@@ -1192,9 +1203,15 @@ int launch_assign_pruned_list(hipStream_t s, Pts X, int d, const double* C, int 
     return kstatus("assign_pruned_kernel");
 }
 
-int launch_assign_exact_list(hipStream_t s, Pts X, int d, const double* C, int K, double* CT,
-                             const int32_t* rows, const unsigned long long* row_count, int64_t max_rows,
-                             int32_t* assign, double* dist, const int32_t* seg_counts, int64_t seg_rows, int nseg) {
+int launch_assign_exact_list(hipStream_t s, const AssignJob& q, double* CT, const RowList& l) {
+    const Pts X = q.X;
+    const int64_t max_rows = l.bound, seg_rows = l.seg_rows;
+    const int d = q.d, K = q.K, nseg = l.nseg;
+    const double* C = q.C;
+    const int32_t *rows = l.p, *seg_counts = l.seg_counts();
+    const unsigned long long* row_count = l.count;
+    int32_t* assign = q.assign;
+    double* dist = q.dist;
     if (max_rows <= 0) return 0;
     if (d > XB_DMAX || (seg_counts && nseg <= 0)) {
         set_error("launch_assign_exact_list: unsupported shape");

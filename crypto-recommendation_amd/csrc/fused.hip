@@ -15,103 +15,120 @@
 // range is guarded: a point with |x_j| > 2^15 (or non-finite) or a centroid set
 // with |c_j| > 2^15 is never certified, so such inputs take the exact path.
 //
-// This file is the launch sequence alone; the kernels live in fused_hi.hip
+// This file is the host side alone: fused_assign, from the workspace to the
+// last fix-up. The kernels live in fused_hi.hip
 // (scores from the hi products only: most rows are certified there),
 // fused_refine.hip (the 3-product refinement of the rows it lists),
 // fused_small.hip (centroid prep and the fix-ups) and fused_chunked.hip (the
 // streaming form for k != 4), and fused_impl.h holds what they share.
+#include "../../include/lshkm.h"
 #include "fused_impl.h"
+#include "index.h"
 
 namespace lshkm {
 
 namespace {
 
-// What a launch works out once: the grid (one block per CU) and the forms.
+// What a call works out once: the grid (one block per CU), the lists' segment
+// size and the passes.
 struct FusedPlan {
     bool hash = false, cos = false;
+    int rows = 0;
     int nblk = 0;
+    int64_t seg_rows = 0;
     int np_hi = 0;       // hi-only passes (FH_KMAX centroids each)
     int np_refine = 0;   // refinement passes (FP_KMAX centroids each)
-    bool side = false;   // the hash fix-up runs on the side stream
 };
 
-int fused_validate(bool hash, const FusedLaunch& f, const FusedArgs& a, bool chunked, bool multi_ok, int npass) {
-    if (f.rows != 0 && (hash || a.Kpad > FH_KMAX || f.a.d < 1 || f.a.d > FU_D || (f.metric == 1 && !a.Cd) ||
-                        (f.rows == 1 ? !a.X : (f.rows != 2 || !a.X64)))) {
-        set_error("launch_fused: general rows run the hi-only form without hashing, K <= 512, d <= 128");
-        return -1;
-    }
-    // refinement pass state: one slot per (segment, tile) of the list
-    if (npass > 1 && f.part_bytes < ((f.list_cap + 31) / 32 + FUSED_MAX_SEGS) * 64 * 16) {
-        set_error("launch_fused: pass-state buffer too small for the refinement");
-        return -1;
-    }
-    if (f.metric == 1 && (chunked || !multi_ok || !a.nbv || !a.hfix || !a.hfix_count || (hash && a.k != 4))) {
-        set_error("launch_fused: cosine runs the hi-only form only (hashing: k = 4)");
-        return -1;
-    }
-    if (f.metric == 1 && f.rows == 2 && !a.xn2) {
-        set_error("launch_fused: cosine on fp64 rows needs the rows' sums of squares");
-        return -1;
-    }
-    if ((f.metric == 1 || !a.fast_dist) && (!a.cfix || !a.cfix_counts || !a.cfix_count)) {
-        set_error("launch_fused: the hi-only cosine form needs the decline list, the exact euclidean one the pow fix-up list");
-        return -1;
-    }
-    if (hash && (a.LK > 32 || a.L * a.k != a.LK)) {              // the fix-ups hold <= 32 functions per row
-        set_error("launch_fused: hashing needs L * k <= 32");
-        return -1;
-    }
+// The context's buffers at fused_layout's sizes, as typed pointers: the one
+// place that names them (the allocation order is part of the contract: a
+// buffer grows in place of its own earlier allocation only).
+int fused_workspace(lshkm_ctx ctx, const FusedShape& sh, FusedWorkspace& w) {
+    const FusedLayout l = fused_layout(sh);
+    int rc;
+    struct { Buf& b; size_t bytes; } const bufs[] = {
+        {ctx->ws_c32, l.c16},      {ctx->ws_cconst, l.cconst}, {ctx->ws_ambig, l.list1}, {ctx->ws_counter, l.counter},
+        {ctx->ws_seg, l.seg1},     {ctx->ws_hfix, l.fix},      {ctx->ws_seg3, l.seg3},   {ctx->ws_part, l.part},
+        {ctx->ws_ambig2, l.list2}, {ctx->ws_seg2, l.seg2},     {ctx->ws_tuples, l.tuples}, {ctx->ws_cf32, l.cf32},
+        {ctx->ws_c64p, l.c64p},    {ctx->ws_xn2, l.xn2}};
+    for (const auto& e : bufs)
+        if (e.bytes && (rc = e.b.reserve(e.bytes))) return rc;
+    const auto at = [](const Buf& b, size_t off) { return off == FusedLayout::NONE ? nullptr : (char*)b.p + off; };
+    w.list_cap = l.list_cap;
+    w.Ch = (_Float16*)at(ctx->ws_c32, 0); w.Cl = (_Float16*)at(ctx->ws_c32, l.cl_off);
+    w.cbound = (float*)at(ctx->ws_cconst, 0); w.cnh = (float*)at(ctx->ws_cconst, l.cnh_off);
+    w.nbv = (double*)at(ctx->ws_cconst, l.nbv_off);
+    if (l.cf32) { w.C32 = (float*)at(ctx->ws_cf32, 0); w.rn32 = (float*)at(ctx->ws_cf32, l.rn32_off); }
+    if (l.c64p) w.C64p = ctx->ws_c64p.as<double>();
+    w.list1 = ctx->ws_ambig.as<int32_t>(); w.seg1 = ctx->ws_seg.as<int32_t>();
+    w.list2 = ctx->ws_ambig2.as<int32_t>(); w.seg2 = ctx->ws_seg2.as<int32_t>();
+    if (l.seg3) w.seg3 = ctx->ws_seg3.as<int32_t>();
+    w.hfix = (unsigned long long*)at(ctx->ws_hfix, l.hfix_off);
+    w.cfix = (unsigned long long*)at(ctx->ws_hfix, l.cfix_off);
+    w.hfix2 = (unsigned long long*)at(ctx->ws_hfix, l.hfix2_off);
+    if (l.part) w.part = ctx->ws_part.as<float4>();
+    w.cnt = ctx->ws_counter.as<unsigned long long>();
+    if (l.xn2) w.xn2 = ctx->ws_xn2.as<double>();
+    if (l.tuples) w.tuples = ctx->ws_tuples.as<int32_t>();
     return 0;
 }
 
-// One block per CU; the lists' segment size; the workspace checks.
-int fused_plan(bool hash, FusedLaunch& f, FusedArgs& a, FusedPlan& p) {
-    int ncu = 0;
-    if (device_cu_count(&ncu)) return -2;
-    const int64_t ntiles = (a.N + 31) / 32;
-    const int64_t want = (ntiles + FP_WAVES - 1) / FP_WAVES;
-    const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(ncu, want));
-    // list segments: block b's tiles hold at most W * 32 * ceil(tiles / (grid * W))
-    // rows, for every wave count W a kernel may run with
-    a.seg_rows = 0;
-    for (const int W : {FP_WAVES, FH_WAVES_MIN, FH_WAVES_MAX})
-        a.seg_rows = std::max<int64_t>(a.seg_rows, (int64_t)W * 32 * ((ntiles + (int64_t)nblk * W - 1) / ((int64_t)nblk * W)));
-    a.seg_counts = f.seg_counts;
-    if (!f.seg_counts || f.seg_cap < nblk || (int64_t)nblk * a.seg_rows > f.list_cap) {
-        set_error("launch_fused: list workspace too small");
-        return -1;
+// The kernels' argument block, from the request and the workspace: everything
+// but the lists and the per-pass fields, which each stage sets for itself.
+FusedArgs fused_common_args(lshkm_ctx ctx, const AssignRequest& q, const FusedShape& sh, const FusedWorkspace& w) {
+    FusedArgs a{};
+    a.X = q.X.f64 ? nullptr : q.X.f(); a.X64 = q.X.f64 ? q.X.d() : nullptr;
+    a.N = q.N; a.d = q.d;
+    a.xvec = sh.rows == 1 ? (a.d % 4 == 0 && ((uintptr_t)a.X & 15) == 0) : (a.d % 2 == 0 && ((uintptr_t)a.X64 & 15) == 0);
+    a.Ch = w.Ch; a.Cl = w.Cl; a.cnh = w.cnh; a.cbound = w.cbound; a.Kpad = sh.Kpad();
+    a.C64 = w.C64p ? w.C64p : q.C; a.Cd = q.C;
+    a.C32 = w.C32; a.rn32 = w.rn32; a.fast_dist = sh.fast ? 1 : 0;
+    a.assign = q.assign; a.dist = q.dist;
+    a.stats = ctx->stats.as<unsigned long long>();
+    a.nb = 1;
+    if (q.lsh) {
+        const ProjTable& pj = q.lsh->proj;
+        a.Vh = pj.vh_d.as<_Float16>(); a.Vl = pj.vl_d.as<_Float16>(); a.PT = pj.PT_d.as<double>();
+        a.tv = pj.t_d.as<float>(); a.pnorm = pj.pn_d.as<double>(); a.v1 = pj.v1_d.as<double>();
+        a.rv = pj.r_d.as<int32_t>(); a.w = pj.w; a.L = pj.L; a.k = pj.k; a.LK = pj.LK; a.LKpad = pj.LKpad;
+        a.nb = q.lsh->nb;
     }
-    f.nseg = nblk;
-    f.seg_rows = a.seg_rows;
-    if (hash && (!a.hfix || !a.hfix_count || (f.metric == 0 && !a.tuples) || a.LKpad > 32)) {   // pts[] holds 128 x 32 projections
-        set_error("launch_fused: hashing needs the fix-up list, a tuple buffer and L*k <= 32");
-        return -1;
-    }
-    if (!f.list2 || !f.seg_counts2 || !f.refined || (f.a.Kpad > FH_KMAX && !f.part) || (f.metric == 1 && !f.hfix2)) {
-        set_error("launch_fused: the hi-only form needs the second list and its counters");
-        return -1;
-    }
-    p.hash = hash;
-    p.cos = f.metric == 1;
-    p.nblk = nblk;
-    p.np_hi = (f.a.Kpad + FH_KMAX - 1) / FH_KMAX;
-    p.np_refine = (f.a.Kpad + FP_KMAX - 1) / FP_KMAX;
-    p.side = hash && f.side && f.fork && f.join;
-    return 0;
+    a.bdiv = make_bucket_div(a.nb);
+    if (sh.cosine) { a.nbv = w.nbv; a.xn2 = w.xn2; }
+    a.cfix = w.cfix; a.cfix_counts = w.seg3; a.cfix_count = w.cfix ? w.cnt + CNT_CFIX : nullptr;
+    a.pass_first = 1; a.pass_last = 1;
+    return a;
 }
 
-// The hi-only passes over all rows; the rows they cannot certify go to a.ambig.
-int fused_hi_passes(hipStream_t s, const FusedLaunch& f, FusedArgs& a, const FusedPlan& p) {
+// The LSH outputs and the hash fix-up list of the pass that hashes (cosine
+// passes list their declined hashes there without hashing too).
+void hash_outputs(FusedArgs& a, const AssignRequest& q, const FusedShape& sh, const FusedWorkspace& w) {
+    a.hfix = w.hfix; a.hfix_count = w.hfix ? w.cnt + CNT_HFIX : nullptr;
+    if (!q.lsh) return;
+    a.phi = q.phi; a.bucket = q.bucket;
+    a.tuples = sh.cosine ? nullptr : q.tuples ? q.tuples : w.tuples;
+}
+
+// One of the call's lists: a segment per block of the plan's grid
+template <typename T>
+DevList<T> segmented(T* p, unsigned long long* count, int32_t* counts, const AssignRequest& q, const FusedPlan& plan) {
+    DevList<T> l;
+    l.p = p; l.count = count; l.bound = q.N; l.counts = counts;
+    l.seg_rows = plan.seg_rows; l.nseg = plan.nblk;
+    return l;
+}
+
+// The hi-only passes over all rows; the rows they cannot certify go to list1.
+int fused_hi_passes(hipStream_t s, const FusedArgs& hi, const FusedPlan& p) {
     const bool gather_on = !test_switch("LSHKM_GATHER", "0");
     int rc;
-    if (f.rows != 0) {
+    if (p.rows != 0) {
         // general rows: one pass (Kpad <= 512)
         HiForm h;
-        h.metric = f.metric; h.rows = f.rows;
-        h.fast = !p.cos && a.fast_dist;
-        h.gath = !p.cos && !h.fast && f.rows == 1 && a.Kpad <= FH_GATH_KMAX && gather_on;
-        return launch_fused_hi_pass(s, p.nblk, h, a);
+        h.metric = p.cos; h.rows = p.rows;
+        h.fast = !p.cos && hi.fast_dist;
+        h.gath = !p.cos && !h.fast && p.rows == 1 && hi.Kpad <= FH_GATH_KMAX && gather_on;
+        return launch_fused_hi_pass(s, p.nblk, h, hi);
     }
     // 512 < K <= 1024, euclidean, LSHKM_HI_TWO_IMAGE=1: one two-image launch
     // instead of two passes with carried state. Measured at C5 (N = 10M,
@@ -121,15 +138,16 @@ int fused_hi_passes(hipStream_t s, const FusedLaunch& f, FusedArgs& a, const Fus
     if (!p.cos && p.np_hi == 2 && test_switch("LSHKM_HI_TWO_IMAGE", "1")) {
         HiForm h;
         h.hash = p.hash; h.two_image = true;
-        return launch_fused_hi_pass(s, p.nblk, h, a);
+        return launch_fused_hi_pass(s, p.nblk, h, hi);
     }
     for (int i = 0; i < p.np_hi; i++) {
         const int c0 = i * FH_KMAX;
-        a.Ch = f.a.Ch + (size_t)c0 * FU_D; a.cnh = f.a.cnh + c0;
-        a.Kpad = std::min(FH_KMAX, f.a.Kpad - c0);
+        FusedArgs a = hi;
+        a.Ch = hi.Ch + (size_t)c0 * FU_D; a.cnh = hi.cnh + c0;
+        a.Kpad = std::min(FH_KMAX, hi.Kpad - c0);
         a.t0 = c0 / 32; a.pass_first = i == 0; a.pass_last = i == p.np_hi - 1;
         HiForm h;
-        h.hash = p.hash && i == 0; h.mp = p.np_hi > 1; h.metric = f.metric;
+        h.hash = p.hash && i == 0; h.mp = p.np_hi > 1; h.metric = p.cos;
         if (!p.cos && !h.mp) {
             // K <= 256: the certified f32 winner distance compiled in, else the
             // winner rows by the LDS-DMA gather (LSHKM_GATHER=0: register loads)
@@ -144,123 +162,194 @@ int fused_hi_passes(hipStream_t s, const FusedLaunch& f, FusedArgs& a, const Fus
     return 0;
 }
 
-// The hash fix-up touches only tuples / phi / bucket of its listed rows: on
-// the side stream beside the refinement when one is given.
-int fused_hash_fixup(hipStream_t s, FusedLaunch& f, const FusedArgs& a, const FusedPlan& p) {
-    hipStream_t hs = p.side ? f.side : s;
-    if (p.side) {
-        if (hipEventRecord(f.fork, s) != hipSuccess || hipStreamWaitEvent(f.side, f.fork, 0) != hipSuccess)
-            return kstatus("launch_fused (fork)");
-    }
-    if (p.hash) launch_hash_fixup(hs, (unsigned)p.nblk, p.cos, a);
-    if (p.side && f.side_timing) {
-        if (hipEventRecord(f.side_timing, f.side) != hipSuccess) {
-            (void)hipStreamSynchronize(f.side);
-            return kstatus("launch_fused (timing)");
-        }
-        f.side_timed = true;
-    }
-    if (p.side && hipEventRecord(f.join, f.side) != hipSuccess) {
-        // never return with the fix-up unordered against later work on s
-        (void)hipStreamSynchronize(f.side);
-        return kstatus("launch_fused (join)");
-    }
-    return 0;
-}
-
-// The 3-product refinement of the rows in a.ambig, FP_KMAX centroids per pass;
-// what it cannot certify goes to list2 for the caller's exact pass.
-int fused_refine_passes(hipStream_t s, const FusedLaunch& f, const FusedArgs& a, const FusedPlan& p) {
-    FusedArgs r = a;
-    r.list_in = a.ambig; r.list_counts = f.seg_counts; r.list_seg_rows = a.seg_rows;
-    r.ambig = f.list2; r.seg_counts = f.seg_counts2; r.ambig_count = f.a.ambig_count;
-    r.hfix = p.cos ? f.hfix2 : f.a.hfix; r.hfix_count = p.cos ? f.a.cfix_count : f.a.hfix_count;
-    r.tuples = nullptr; r.phi = nullptr; r.bucket = nullptr;
+// The 3-product refinement of the rows in list1, FP_KMAX centroids per pass;
+// what it cannot certify goes to list2 for the listed exact pass.
+int fused_refine_passes(hipStream_t s, const FusedArgs& rf, const FusedPlan& p) {
     for (int i = 0; i < p.np_refine; i++) {
         const int c0 = i * FP_KMAX;
-        r.Ch = f.a.Ch + (size_t)c0 * FU_D; r.Cl = f.a.Cl + (size_t)c0 * FU_D; r.cnh = f.a.cnh + c0;
-        r.Kpad = std::min(FP_KMAX, f.a.Kpad - c0);
+        FusedArgs r = rf;
+        r.Ch = rf.Ch + (size_t)c0 * FU_D; r.Cl = rf.Cl + (size_t)c0 * FU_D; r.cnh = rf.cnh + c0;
+        r.Kpad = std::min(FP_KMAX, rf.Kpad - c0);
         r.t0 = c0 / 32; r.pass_first = i == 0; r.pass_last = i == p.np_refine - 1;
-        const int rc = launch_fused_refine_pass(s, (unsigned)p.nblk, f.metric, p.np_refine > 1, f.rows, r);
+        const int rc = launch_fused_refine_pass(s, (unsigned)p.nblk, p.cos, p.np_refine > 1, p.rows, r);
         if (rc) return rc;
     }
     return 0;
 }
 
-// out: the lists the caller still has to work through
-void fused_output_lists(FusedLaunch& f, const FusedArgs& a, const FusedPlan& p) {
-    f.final_list = f.list2;
-    f.final_counts = f.seg_counts2;
-    if (!p.cos && !a.fast_dist && a.cfix) {      // the hi-only pass's pow fix-ups (exact distances)
-        f.ncos_lists = 1;
-        f.cos_list[0] = a.cfix; f.cos_counts[0] = a.cfix_counts;
+// The side stream between its fork and the main stream's wait on its join
+// event. The hash fix-up there writes only tuples / phi / bucket; whatever way
+// fused_assign returns after the fork, the fix-up is ordered against later
+// work on the main stream: by join(), or by draining the side stream here.
+struct SideFork {
+    lshkm_ctx c;
+    bool open = false;
+    int fork() {
+        if (hipEventRecord(c->fork_ev, c->stream) != hipSuccess ||
+            hipStreamWaitEvent(c->side_stream, c->fork_ev, 0) != hipSuccess)
+            return kstatus("fused_assign (fork)");
+        open = true;
+        return 0;
     }
-    if (p.cos) {
-        f.ncos_lists = 2;
-        f.cos_list[0] = a.cfix; f.cos_counts[0] = a.cfix_counts;
-        f.cos_list[1] = f.hfix2; f.cos_counts[1] = f.seg_counts2;
+    // the side stream's work is all enqueued: its timing event, its join event
+    int end_side() {
+        if (c->timing) {
+            if (hipEventRecord(c->tev[2], c->side_stream) != hipSuccess) return kstatus("fused_assign (timing)");
+            c->tev_side = true;      // only a call that recorded tev[2] extends the timed pass
+        }
+        if (hipEventRecord(c->join_ev, c->side_stream) != hipSuccess) return kstatus("fused_assign (join)");
+        return 0;
     }
-}
+    int join() {
+        if (!open) return 0;
+        if (hipStreamWaitEvent(c->stream, c->join_ev, 0) != hipSuccess) return kstatus("fused_assign (join)");
+        open = false;
+        return 0;
+    }
+    ~SideFork() { if (open) (void)hipStreamSynchronize(c->side_stream); }
+};
+
+#ifdef LSHKM_PHASE_TIMING
+// Per-phase wave cycles of the passes between its construction and its end,
+// printed there.
+struct PhaseReport {
+    hipStream_t s;
+    unsigned long long* d = nullptr;
+    explicit PhaseReport(hipStream_t s_) : s(s_) {
+        static unsigned long long* prof_d = nullptr;
+        if (!prof_d) (void)hipMalloc(&prof_d, 64);
+        (void)hipMemsetAsync(prof_d, 0, 64, s);
+        d = prof_d;
+    }
+    ~PhaseReport() {
+        unsigned long long v[6];
+        (void)hipMemcpyAsync(v, d, 48, hipMemcpyDeviceToHost, s);
+        (void)hipStreamSynchronize(s);
+        // hi-only form: [0] load + split + hash, [1] centroid tiles, [2] certificate + chain + stores
+        // (the refinement's fused_persistent_kernel adds its own phases 0-4 over its few rows)
+        fprintf(stderr, "PHASES %llu %llu %llu %llu %llu\n", v[0], v[1], v[2], v[3], v[4]);
+    }
+};
+#endif
 
 }  // namespace
 
-int launch_fused(hipStream_t s, bool hash, FusedLaunch& f) {
-    f.nseg = 0;
-    f.side_timed = false;
-    if (f.a.N <= 0) return 0;
-    // the caller's block, then the fields this launch derives
-    FusedArgs a = f.a;
-    a.bdiv = make_bucket_div(a.nb);
-    a.part = nullptr; a.t0 = 0; a.pass_first = 1; a.pass_last = 1;
-    a.list_in = nullptr; a.list_counts = nullptr; a.list_seg_rows = 0;
-    a.prof = nullptr;
-    a.pw_lds = 0;
-    a.fast_dist = f.a.fast_dist && f.metric == 0 && f.rows != 2 && a.C32 && a.rn32 ? 1 : 0;
-    a.d = f.rows == 0 ? FU_D : f.a.d;
-    a.xvec = f.rows == 1 ? (a.d % 4 == 0 && ((uintptr_t)a.X & 15) == 0)
-                         : (a.d % 2 == 0 && ((uintptr_t)a.X64 & 15) == 0);
-#ifdef LSHKM_PHASE_TIMING
-    static unsigned long long* prof_d = nullptr;
-    if (!prof_d) (void)hipMalloc(&prof_d, 64);
-    (void)hipMemsetAsync(prof_d, 0, 64, s);
-    a.prof = prof_d;
-    struct PhaseReport {      // printed after the launch sequence below
-        hipStream_t s; unsigned long long* d;
-        ~PhaseReport() {
-            unsigned long long v[6];
-            (void)hipMemcpyAsync(v, d, 48, hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            // hi-only form: [0] load + split + hash, [1] centroid tiles, [2] certificate + chain + stores
-            // (the refinement's fused_persistent_kernel adds its own phases 0-4 over its few rows)
-            fprintf(stderr, "PHASES %llu %llu %llu %llu %llu\n", v[0], v[1], v[2], v[3], v[4]);
-        }
-    } report{s, prof_d};
-#endif
-    const bool chunked = test_switch("LSHKM_FUSED_FORM", "chunked") && f.rows == 0;   // the streaming form (tests)
-    const int npass = (a.Kpad + FP_KMAX - 1) / FP_KMAX;
-    const bool multi_ok = npass == 1 || (f.part && f.part_bytes >= ((a.N + 31) / 32) * 64 * 16);
+int fused_assign(lshkm_ctx ctx, const AssignRequest& q) {
+    hipStream_t s = ctx->stream;
+    const bool cosine = q.metric != LSHKM_METRIC_EUCLIDEAN;
+    const ProjTable* pj = q.lsh ? &q.lsh->proj : nullptr;
+    const FusedRoute route = fused_route(cosine, q.X.f64, q.d, q.K, pj != nullptr, pj ? pj->k : 0, pj ? pj->LK : 0,
+                                         test_switch("LSHKM_FUSED_FORM", "chunked"));
+    if (route.form == FusedForm::none || (pj && (q.lsh->metric != q.metric || !pj->mfma_ok))) {
+        set_error("fused_assign: no fused form runs this shape (fused_route, fused_layout.h)");
+        return LSHKM_ERR_ARG;
+    }
+    FusedShape sh;
+    sh.N = q.N; sh.d = q.d; sh.K = q.K; sh.cosine = cosine; sh.rows = route.rows;
+    sh.hash = pj != nullptr; sh.LK = pj ? pj->LK : 0;
+    // euclidean winner distances: the certified f32 form (the context's default
+    // mode) or the reference-order fp64 chain (LSHKM_DIST_EXACT, force_exact)
+    sh.fast = !cosine && sh.rows != 2 && !q.force_exact && ctx->dist_mode == LSHKM_DIST_CERTIFIED;
+    // the f32 image also serves the K <= 256 gather when every centroid value
+    // is an f32 (dataset rows: the first Lloyd iteration), exact as doubles
+    // (test switch LSHKM_GATHER32=0: the fp64 winner rows always)
+    sh.image32 = sh.fast || (!cosine && sh.rows != 2 && sh.Kpad() <= 256 && !test_switch("LSHKM_GATHER32", "0"));
+    sh.own_tuples = sh.hash && !cosine && !q.tuples;
+    const bool pwfix = sh.pwfix();
     int rc;
-    if ((rc = fused_validate(hash, f, a, chunked, multi_ok, npass))) return rc;
-    if (chunked || !multi_ok || (hash && a.k != 4)) return launch_fused_chunked(s, hash, a);
+    FusedWorkspace w;
+    if ((rc = fused_workspace(ctx, sh, w))) return rc;
+    LSHKM_HIP(hipMemsetAsync(w.cnt, 0, FUSED_COUNTER_CLEAR, s));
+    // the timed fused pass starts before the centroid prep
+    if (ctx->timing) LSHKM_HIP(hipEventRecord(ctx->tev[0], s));
+    ctx->tev_side = false;
+    if ((rc = launch_fused_prep(s, q.C, q.K, q.d, cosine ? 1 : 0, w))) return rc;
+    // the listed pass's centroid prep ahead of the passes: it then starts as
+    // soon as the refinement ends
+    const bool xprep = exact_pruned(q.X, q.d, q.K, q.metric);
+    if (xprep && (rc = exact_listed_prep(ctx, q))) return rc;
+    if (w.xn2 && (rc = launch_row_sumsq(s, q.X.d(), q.N, q.d, w.xn2))) return rc;
 
-    FusedPlan p;
-    if ((rc = fused_plan(hash, f, a, p))) return rc;
-    a.part = reinterpret_cast<float4*>(f.part);
-    a.ambig_count = f.refined;
-    if ((rc = fused_hi_passes(s, f, a, p))) return rc;
-    if ((rc = fused_hash_fixup(s, f, a, p))) return rc;
-    if ((rc = fused_refine_passes(s, f, a, p))) {
-        if (p.side) (void)hipStreamSynchronize(f.side);
+    const FusedArgs common = fused_common_args(ctx, q, sh, w);
+    // the rows left for the listed exact pass: flat in list1 (the chunked form;
+    // N = 0), else the refinement's segments in list2
+    RowList exact_rows;
+    exact_rows.p = w.list1; exact_rows.count = w.cnt + CNT_AMBIG; exact_rows.bound = q.N;
+    RecList dist_fix[2];      // winners listed for their distance alone
+    int ndist_fix = 0;
+    SideFork side{ctx};
+    if (q.N > 0 && route.form == FusedForm::chunked) {
+        FusedArgs a = common;
+        hash_outputs(a, q, sh, w);
+        a.ambig = w.list1; a.ambig_count = w.cnt + CNT_AMBIG;
+        if ((rc = launch_fused_chunked(s, sh.hash, a))) return rc;
+    } else if (q.N > 0) {
+        FusedPlan p;
+        p.hash = sh.hash; p.cos = cosine; p.rows = sh.rows;
+        int ncu = 0;
+        if (device_cu_count(&ncu)) return LSHKM_ERR_HIP;
+        p.nblk = fused_grid(q.N, ncu);
+        p.seg_rows = fused_seg_rows(q.N, p.nblk);
+        if (p.nblk > FUSED_MAX_SEGS) {       // (then nblk * seg_rows <= list_cap: fused_layout.h)
+            set_error("fused_assign: more blocks than list segments");
+            return LSHKM_ERR_ARG;
+        }
+        p.np_hi = (sh.Kpad() + FH_KMAX - 1) / FH_KMAX;
+        p.np_refine = (sh.Kpad() + FP_KMAX - 1) / FP_KMAX;
+        const RowList l1 = segmented(w.list1, w.cnt + CNT_REFINED, w.seg1, q, p);
+        const RecList lh = segmented(w.hfix, w.cnt + CNT_HFIX, w.seg1, q, p);
+        const RowList l2 = segmented(w.list2, w.cnt + CNT_AMBIG, w.seg2, q, p);
+        FusedArgs seg = common;
+        seg.seg_rows = p.seg_rows; seg.part = w.part;
+#ifdef LSHKM_PHASE_TIMING
+        PhaseReport report(s);
+        seg.prof = report.d;
+#endif
+        FusedArgs hi = seg;
+        hash_outputs(hi, q, sh, w);
+        hi.ambig = l1.p; hi.ambig_count = l1.count; hi.seg_counts = l1.counts;
+        if ((rc = fused_hi_passes(s, hi, p))) return rc;
+        // the hash fix-up touches only tuples / phi / bucket of its listed
+        // rows: on the side stream, beside the refinement (euclidean: and the
+        // listed exact pass), when the context has one
+        if (sh.hash) {
+            const bool forked = ctx->side_init() == 0;
+            if (forked && (rc = side.fork())) return rc;
+            launch_hash_fixup(forked ? ctx->side_stream : s, lh, cosine, hi);
+            if (forked && (rc = side.end_side())) return rc;
+        }
+        FusedArgs rf = seg;
+        rf.list_in = l1.p; rf.list_counts = l1.counts; rf.list_seg_rows = l1.seg_rows;
+        rf.ambig = l2.p; rf.ambig_count = l2.count; rf.seg_counts = l2.counts;
+        // its declined cosine distances go to hfix2 (counts beside list2's)
+        rf.hfix = cosine ? w.hfix2 : hi.hfix; rf.hfix_count = cosine ? w.cnt + CNT_CFIX : hi.hfix_count;
+        if ((rc = fused_refine_passes(s, rf, p))) return rc;
+        if (cosine && (rc = side.join())) return rc;
+        if ((rc = kstatus("fused_hi_kernel"))) return rc;
+        exact_rows = l2;
+        if (cosine || pwfix) dist_fix[ndist_fix++] = segmented(w.cfix, w.cnt + CNT_CFIX, w.seg3, q, p);
+        if (cosine) dist_fix[ndist_fix++] = segmented(w.hfix2, w.cnt + CNT_CFIX, w.seg2, q, p);
+    }
+    if (ctx->timing) LSHKM_HIP(hipEventRecord(ctx->tev[1], s));
+    if ((rc = exact_listed(ctx, q, exact_rows, !sh.fast, xprep, cosine ? w.xn2 : nullptr, cosine ? w.nbv : nullptr)))
         return rc;
+    if ((rc = side.join())) return rc;
+    {
+        int di[3], n = 0;
+        const unsigned long long* sp[3];
+        di[n] = STAT_REFINED; sp[n++] = w.cnt + CNT_REFINED;
+        if (sh.hash) { di[n] = STAT_HASH_FIX; sp[n++] = w.cnt + CNT_HFIX; }
+        di[n] = STAT_ASSIGN_AMBIG; sp[n++] = w.cnt + CNT_AMBIG;
+        if ((rc = launch_add_counters(s, ctx->stats.as<unsigned long long>(), n, di, sp))) return rc;
     }
-    fused_output_lists(f, a, p);
-    if (p.side && f.defer_join) {
-        f.join_pending = true;          // the caller joins (after its exact pass)
-    } else if (p.side && hipStreamWaitEvent(s, f.join, 0) != hipSuccess) {
-        (void)hipStreamSynchronize(f.side);
-        return kstatus("launch_fused (join)");
+    if (cosine || pwfix) {
+        if ((rc = launch_cos_fix_seg(s, q, ndist_fix, dist_fix, cosine ? w.xn2 : nullptr, cosine ? w.nbv : nullptr)))
+            return rc;
+        if ((rc = launch_add_counter(s, ctx->stats.as<unsigned long long>() + (cosine ? STAT_COS_FIX : STAT_POW_FIX),
+                                     w.cnt + CNT_CFIX)))
+            return rc;
     }
-    return kstatus("fused_hi_kernel");
+    return 0;
 }
 
 }  // namespace lshkm

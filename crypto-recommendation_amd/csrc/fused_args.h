@@ -1,10 +1,12 @@
 // fused_args.h — the argument block of the fused hash + assign kernels
 // (fused_hi.hip, fused_refine.hip, fused_chunked.hip and the fix-ups of
-// fused_small.hip; filled by the caller through FusedLaunch::a, kernels.h).
+// fused_small.hip; fused.hip's fused_assign fills it from the request and the
+// workspace, each stage its own lists and per-pass fields).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fused_layout.h"
 #include "tile.h"
 
 namespace lshkm {
@@ -43,13 +45,14 @@ struct FusedArgs {
     unsigned long long* hfix;        // persistent form: rows with an uncertified floor
     unsigned long long* hfix_count;
     // hi-only cosine form: rows whose winner distance the certified quotient
-    // declined (cos_fix_seg pass); counts in cfix_counts[2b + 1]
+    // declined (cos_fix_seg pass); counts in cfix_counts[SEG_SLOTS * b + SEG_FIX]
     unsigned long long* cfix;
     int32_t* cfix_counts;
     unsigned long long* cfix_count;
     unsigned long long* stats;
     // persistent form: block b owns ambig/hfix entries [b * seg_rows, (b+1) * seg_rows)
-    // and reports their counts in seg_counts[2b] (ambiguous), seg_counts[2b+1] (fix-up)
+    // and reports their counts in seg_counts[SEG_SLOTS * b + SEG_ROWS] (ambiguous) and
+    // [SEG_SLOTS * b + SEG_FIX] (fix-up): fused_layout.h
     int64_t seg_rows;
     int32_t* seg_counts;
     BucketDiv bdiv;          // phi % nb by multiply-high
@@ -61,12 +64,12 @@ struct FusedArgs {
     float4* part;
     int t0, pass_first, pass_last;
     // refinement of the rows a hi-only pass left uncertified (fused_refine.hip): block b
-    // takes the rows list_in[b * list_seg_rows ..][0 .. list_counts[2b])
+    // takes the rows list_in[b * list_seg_rows ..][0 .. list_counts[SEG_SLOTS * b + SEG_ROWS])
     const int32_t* list_in;
     const int32_t* list_counts;
     int64_t list_seg_rows;
     unsigned long long* prof;        // LSHKM_PHASE_TIMING builds only: per-phase wave cycles
-    const float* C32;                // fast_dist: [Kpad][128] f32(c) and |c - f32(c)| (FusedLaunch)
+    const float* C32;                // fast_dist: [Kpad][128] f32(c) and |c - f32(c)| (FusedWorkspace)
     const float* rn32;
     int fast_dist;
     // general rows (fused_hi_kernel<..., ROWS = 1 / 2>): fp32 (X) or fp64 (X64)

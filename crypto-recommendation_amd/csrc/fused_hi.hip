@@ -786,15 +786,16 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
     }
     PT_FLUSH
     __syncthreads();
+    // thread t writes slot t: SEG_ROWS (uncertified rows), SEG_FIX (hash fix-ups)
     if (threadIdx.x < 2 && (!MP || (threadIdx.x == 0 ? (!HASH && a.pass_last != 0) : (HASH && a.pass_first)))) {
         const int c = lcount[threadIdx.x];
-        a.seg_counts[2 * blockIdx.x + threadIdx.x] = c;
+        a.seg_counts[SEG_SLOTS * blockIdx.x + threadIdx.x] = c;
         if (c) atomicAdd(threadIdx.x == 0 ? a.ambig_count : a.hfix_count, (unsigned long long)c);
     }
     // slot 2: cosine declines / euclidean pow fix-ups (exact distances)
     if ((MET == 1 || !fastd) && threadIdx.x == 2 && (!MP || (!HASH && a.pass_last))) {
         const int c = lcount[2];
-        a.cfix_counts[2 * blockIdx.x + 1] = c;
+        a.cfix_counts[SEG_SLOTS * blockIdx.x + SEG_FIX] = c;
         if (c) atomicAdd(a.cfix_count, (unsigned long long)c);
     }
 }

@@ -1,6 +1,7 @@
 // fused_impl.h — what the fused-pass translation units share: the device
-// helpers and sizes used by more than one kernel file, and the host entry of
-// each kernel file (fused.hip's launch_fused calls them in sequence).
+// helpers and sizes used by more than one kernel file, the typed workspace, and
+// the host entry of each kernel file (fused.hip's fused_assign calls them in
+// sequence).
 //   fused_chunked.hip  fused_kernel<HASH>: the streaming form (k != 4; tests)
 //   fused_hi.hip       fused_hi_kernel: one f16 MFMA per centroid product
 //   fused_refine.hip   fused_persistent_kernel: the 3-product refinement of
@@ -23,18 +24,39 @@
 namespace lshkm {
 
 // ---- settled launch shapes (the measurements: DESIGN.md, "tried and rejected")
-constexpr int FP_WAVES = 8;          // refinement: 2 waves per SIMD, the exact row kept in registers (<= 256 VGPRs)
+// (the wave counts and centroids per pass that size the workspace: fused_layout.h)
+static_assert(FU_D == FUSED_DIMS, "fused_layout.h states the kernels' dimension");
 constexpr int FP_THREADS = 64 * FP_WAVES;
-constexpr int FP_KMAX = 256;         // centroids per refinement pass (hi + lo images in LDS)
-constexpr int FH_KMAX = 512;         // centroids per hi-only pass (hi image only)
 constexpr int FH_GATH_KMAX = 256;    // hi-only: the LDS-DMA gather ring fits beside this many centroids
-constexpr int FH_WAVES_MIN = 8, FH_WAVES_MAX = 12;   // fh_waves() over all instantiations
 constexpr int FP_HC_BYTES = 32 * (4 + 4 + 4 + 4);     // hash constants |v|_2, |v|_1, t, r
 constexpr int MFMA_PRIO = 1;         // s_setprio inside the centroid loop (measured +1-3%)
 constexpr int CHAIN_PRIO = 2;        // s_setprio around the hi-only kernel's winner chain (measured -0.02 ms)
 
+// ---- the workspace of one call, typed (fused.hip binds it to the context's
+// buffers by fused_layout.h's sizes and regions; null: this shape has none)
+struct FusedWorkspace {
+    int64_t list_cap = 0;
+    _Float16 *Ch = nullptr, *Cl = nullptr;       // [Kpad][128] split-f16 centroid images
+    float *cbound = nullptr, *cnh = nullptr;     // FusedArgs::cbound / cnh
+    double* nbv = nullptr;                       // [Kpad] sequential |c|^2 (cosine)
+    float *C32 = nullptr, *rn32 = nullptr;       // f32(c) [Kpad][128] and |c - f32(c)|_2 [Kpad] rounded up
+    double* C64p = nullptr;                      // general rows of d < 128: zero-padded fp64 centroids
+    int32_t *list1 = nullptr, *seg1 = nullptr;   // the hi-only passes' rows (seg1: + the hash fix-ups' counts)
+    int32_t *list2 = nullptr, *seg2 = nullptr;   // the refinement's rows (seg2: + its declines' counts)
+    int32_t* seg3 = nullptr;                     // counts of cfix
+    unsigned long long *hfix = nullptr, *cfix = nullptr, *hfix2 = nullptr;   // FusedLayout::fix regions
+    float4* part = nullptr;                      // pass state (Kpad > FP_KMAX)
+    unsigned long long* cnt = nullptr;           // CNT_* device counters
+    double* xn2 = nullptr;                       // cosine on fp64 rows: [N] sum_j pow(x_j, 2)
+    int32_t* tuples = nullptr;                   // hashing without a caller's tuple buffer
+};
+
 // ---- host entries of the kernel files. Each picks its instantiation from
 // run-time values; a combination no kernel was built for is an error (-1).
+// Centroid prep into w (Ch, Cl, cnh, cbound; cosine: nbv; C32 / rn32 and C64p where bound).
+int launch_fused_prep(hipStream_t s, const double* C, int K, int d, int metric, const FusedWorkspace& w);
+// out[i] = sum_j pow(x_ij, 2) in j order (glibc's pow, gpow2.h), fp64 rows
+int launch_row_sumsq(hipStream_t s, const double* X, int64_t N, int d, double* out);
 int launch_fused_chunked(hipStream_t s, bool hash, const FusedArgs& a);
 // One hi-only pass over all rows; a.Kpad centroids from a.Ch / a.cnh.
 struct HiForm {
@@ -49,8 +71,13 @@ struct HiForm {
 int launch_fused_hi_pass(hipStream_t s, unsigned nblk, const HiForm& f, FusedArgs a);
 // One refinement pass over the rows of a.list_in; a.Kpad <= FP_KMAX centroids.
 int launch_fused_refine_pass(hipStream_t s, unsigned nblk, int metric, bool mp, int rows, const FusedArgs& a);
-// Fix-up of the listed hash values (a.hfix, segment counts in a.seg_counts).
-void launch_hash_fixup(hipStream_t s, unsigned nseg, bool cosine, const FusedArgs& a);
+// Fix-up of the hash values listed in l (a: the pass's block; its list fields are set from l).
+void launch_hash_fixup(hipStream_t s, const RecList& l, bool cosine, FusedArgs a);
+// Winners listed by the fused kernels for their distance alone (nlists <= 2
+// segmented lists of one grid): metric 1 the soft-x87 cosine, metric 0 the
+// euclidean chain with glibc's pow(x, 2) (gpow2.h).
+int launch_cos_fix_seg(hipStream_t s, const AssignJob& q, int nlists, const RecList* lists, const double* xn2,
+                       const double* nbv);
 
 // Profiling builds (make prof -> liblshkm_prof.so) accumulate s_memtime per
 // phase of the persistent loop; the product library compiles these away.

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
     const int ntile32 = Kpad >> 5;
     // this block's segment of the input list
     const int32_t* lrows = a.list_in + (int64_t)blockIdx.x * a.list_seg_rows;
-    const int64_t lcnt = (int64_t)a.list_counts[2 * blockIdx.x];
+    const int64_t lcnt = (int64_t)a.list_counts[SEG_SLOTS * blockIdx.x + SEG_ROWS];
     const int64_t ptile0 = (int64_t)blockIdx.x * ((a.list_seg_rows + 31) >> 5);   // part slots
 
     PT_DECL
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
     // slot 0: ambiguous rows; slot 1: the cosine fix-up list (the last pass decides both)
     if (threadIdx.x < 2 && (!MP || (threadIdx.x == 0 ? a.pass_last != 0 : (MET == 1 && a.pass_last)))) {
         const int c = lcount[threadIdx.x];
-        a.seg_counts[2 * blockIdx.x + threadIdx.x] = c;
+        a.seg_counts[SEG_SLOTS * blockIdx.x + threadIdx.x] = c;
         if (c) atomicAdd(threadIdx.x == 0 ? a.ambig_count : a.hfix_count, (unsigned long long)c);
     }
 }

@@ -183,7 +183,7 @@ __device__ inline void fix_settle(FixRow& r, unsigned long long& ent) {
 }
 
 // The row's stores, apart from its computation: the kernel's loop waits for the
-// next row's loads between the two (fix_settle). k = 4 (launch_fused sends
+// next row's loads between the two (fix_settle). k = 4 (fused_route sends
 // every other k to the chunked form): lane q's tuples [4q, 4q + 4) are the
 // whole table q, so each lane stores its own table where touched, tuples (the
 // unflagged ones as loaded) and phi / bucket, with no sum across lanes and no
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(64 * HF_WAVES) void hash_fixup_kernel(FusedArgs a) 
     int32_t* crv = reinterpret_cast<int32_t*>(ctt + 32);   // [32] r_f
     const int nseg = gridDim.x / HF_SPLIT;       // segments across XCDs (cos_fix_seg_kernel)
     const int seg = blockIdx.x % nseg, part = blockIdx.x / nseg;
-    const int n = a.seg_counts[2 * seg + 1];
+    const int n = a.seg_counts[SEG_SLOTS * seg + SEG_FIX];
     if (n == 0) return;                                                 // block-uniform
     const unsigned long long* list = a.hfix + (int64_t)seg * a.seg_rows;
     const int LK = a.LK, LKpad = a.LKpad;
@@ -269,7 +269,9 @@ __global__ __launch_bounds__(64 * HF_WAVES) void hash_fixup_kernel(FusedArgs a) 
     }
 }
 
-void launch_hash_fixup(hipStream_t s, unsigned nseg, bool cosine, const FusedArgs& a) {
+void launch_hash_fixup(hipStream_t s, const RecList& l, bool cosine, FusedArgs a) {
+    a.hfix = l.p; a.seg_counts = l.counts; a.seg_rows = l.seg_rows;
+    const unsigned nseg = (unsigned)l.nseg;
     const dim3 grid(nseg * HF_SPLIT), block(64 * HF_WAVES);
     if (cosine) hipLaunchKernelGGL(hash_fixup_kernel<true>, grid, block, HF_LDS, s, a);
     else hipLaunchKernelGGL(hash_fixup_kernel<false>, grid, block, HF_LDS, s, a);
@@ -388,27 +390,12 @@ __global__ void fused_centroid_prep(const double* __restrict__ C, int K, int Kpa
     }
 }
 
-int launch_fused_prep(hipStream_t s, const double* C, int K, int Kpad, _Float16* Ch, _Float16* Cl, float* cnh,
-                      float* cbound, int metric, double* nbv, float* C32, float* rn32, int d, double* C64p) {
-    if (d < 1 || d > FU_D || (d != FU_D && metric == 0 && !C64p)) {
-        set_error("launch_fused_prep: d <= 128, and d < 128 needs the padded centroid copy");
-        return -1;
-    }
-    if (metric == 1 && !nbv) {
-        set_error("launch_fused_prep: cosine needs the norm array");
-        return -1;
-    }
-    if ((C32 == nullptr) != (rn32 == nullptr)) {
-        set_error("launch_fused_prep: the fast-distance image needs both arrays");
-        return -1;
-    }
-    (void)hipMemsetAsync(cbound, 0, 32, s);
-    if (Kpad % FP_PREP_WAVES) {
-        set_error("launch_fused_prep: Kpad must be a multiple of 8");
-        return -1;
-    }
-    hipLaunchKernelGGL(fused_centroid_prep, dim3((unsigned)(Kpad / FP_PREP_WAVES)), dim3(64 * FP_PREP_WAVES), 0, s, C, K, Kpad, Ch, Cl, cnh,
-                       reinterpret_cast<unsigned int*>(cbound), metric, nbv, C32, rn32, d, C64p);
+int launch_fused_prep(hipStream_t s, const double* C, int K, int d, int metric, const FusedWorkspace& w) {
+    const int Kpad = (K + 63) / 64 * 64;
+    static_assert(64 % FP_PREP_WAVES == 0, "Kpad is a multiple of 64");
+    (void)hipMemsetAsync(w.cbound, 0, 32, s);
+    hipLaunchKernelGGL(fused_centroid_prep, dim3((unsigned)(Kpad / FP_PREP_WAVES)), dim3(64 * FP_PREP_WAVES), 0, s, C, K, Kpad, w.Ch, w.Cl, w.cnh,
+                       reinterpret_cast<unsigned int*>(w.cbound), metric, w.nbv, w.C32, w.rn32, d, w.C64p);
     return kstatus("fused_centroid_prep");
 }
 
@@ -435,7 +422,7 @@ __global__ __launch_bounds__(256) void cos_fix_seg_kernel(const TX* __restrict__
     const int per_list = nseg * CF_SPLIT;
     const int li = blockIdx.x / per_list, b = blockIdx.x % per_list;
     const int seg = b % nseg, part = b / nseg;
-    const int n = cl.counts[li][2 * seg + 1];
+    const int n = cl.counts[li][SEG_SLOTS * seg + SEG_FIX];
     const unsigned long long* l = cl.list[li] + (int64_t)seg * seg_rows;
     const bool vec = sizeof(TX) == 4 && d % 8 == 0 && ((uintptr_t)X & 15) == 0 && ((uintptr_t)C & 15) == 0;
     __shared__ double sqs[4][64 * 16];                   // gp_sq_wave: 64 * NV per wave
@@ -551,13 +538,19 @@ int launch_row_sumsq(hipStream_t s, const double* X, int64_t N, int d, double* o
     return kstatus("row_sumsq_kernel");
 }
 
-int launch_cos_fix_seg(hipStream_t s, Pts X, int d, const double* C, int nlists, const unsigned long long* const* lists,
-                       const int32_t* const* counts, int64_t seg_rows, int nseg, const int32_t* assign, double* dist,
-                       int metric, const double* xn2, const double* nbv) {
-    if (nseg <= 0 || nlists <= 0) return 0;
+int launch_cos_fix_seg(hipStream_t s, const AssignJob& q, int nlists, const RecList* lists, const double* xn2,
+                       const double* nbv) {
+    const int nseg = nlists > 0 ? lists[0].nseg : 0;
+    if (nseg <= 0) return 0;
     if (nlists > 2) return -1;                       // LSHKM_ERR_ARG
+    const Pts X = q.X;
+    const int d = q.d, metric = q.metric;
+    const double* C = q.C;
+    const int32_t* assign = q.assign;
+    double* dist = q.dist;
+    const int64_t seg_rows = lists[0].seg_rows;
     CosLists cl{};
-    for (int i = 0; i < nlists; i++) { cl.list[i] = lists[i]; cl.counts[i] = counts[i]; }
+    for (int i = 0; i < nlists; i++) { cl.list[i] = lists[i].p; cl.counts[i] = lists[i].counts; }
     const dim3 grid((unsigned)(nlists * nseg * CF_SPLIT));
 #define CF_LAUNCH(TX, M, XP) hipLaunchKernelGGL((cos_fix_seg_kernel<TX, M>), grid, dim3(256), 0, s, XP, d, C, cl, nseg, seg_rows, assign, dist, xn2, nbv)
     if (metric == 1) {

@@ -20,12 +20,11 @@
 
 namespace lshkm {
 
-constexpr int HMF_W = 4;        // waves per block
-// blocks per CU: 2 (~160 VGPRs) so a wave's 16 row loads can all be in flight
-// before its first MFMA (at 4 blocks the 128-VGPR cap made the scheduler issue
-// them pair by pair next to each step: 8 serial trips per tile; C4 build 1.87
-// -> 1.76 ms, C2 0.353 -> 0.337 ms)
-constexpr int HMF_BPC = 2;
+// HMF_W waves per block, HMF_BPC blocks per CU (fused_layout.h): 2 (~160 VGPRs)
+// so a wave's 16 row loads can all be in flight before its first MFMA (at 4
+// blocks the 128-VGPR cap made the scheduler issue them pair by pair next to
+// each step: 8 serial trips per tile; C4 build 1.87 -> 1.76 ms, C2 0.353 ->
+// 0.337 ms)
 constexpr int HMF_VS = 33;      // per-wave value tile [32 points][33] int32
 constexpr int hmf_lds_bytes() {
     return 2 * 32 * FU_RS * 2 + 4 * 32 * 4 + HMF_W * 32 * HMF_VS * 4 + 16;
@@ -353,24 +352,23 @@ __global__ __launch_bounds__(HMF_FIX_THREADS) void hash_mfma_fix_kernel(HashMfma
 }
 
 int launch_hash_mfma(hipStream_t s, int mode, const float* X, int64_t N, const HashMfmaParams& p, int32_t* out_h,
-                     int32_t* out_phi, int32_t* out_bucket, int32_t* mm, unsigned long long* list, int64_t list_cap,
-                     int32_t* seg_counts, int seg_cap, unsigned long long* stats, int h16) {
+                     int32_t* out_phi, int32_t* out_bucket, int32_t* mm, const RecList& list,
+                     unsigned long long* stats, int h16) {
     if (N <= 0) return 0;
-    if (p.d != FU_D || p.LK > 32 || p.LK < 1 || !p.Vh || !p.Vl || !list || !seg_counts) {
+    if (p.d != FU_D || p.LK > 32 || p.LK < 1 || !p.Vh || !p.Vl || !list.p || !list.counts) {
         set_error("launch_hash_mfma: needs d = 128, 1 <= L*k <= 32 and the split image");
         return -1;
     }
     int ncu = 0;
     if (device_cu_count(&ncu)) return -2;
-    const int64_t ntiles = (N + 31) / 32;
-    const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)ncu * HMF_BPC, (ntiles + HMF_W - 1) / HMF_W));
+    const int nblk = hash_mfma_grid(N, ncu);
     HashMfmaArgs a;
     a.X = X; a.N = N; a.Vh = p.Vh; a.Vl = p.Vl; a.tv = p.t; a.pnorm = p.pnorm; a.v1 = p.v1; a.rv = p.r; a.PT = p.PT;
     a.w = p.w; a.L = p.L; a.k = p.k; a.LK = p.LK; a.LKpad = p.LKpad; a.bdiv = make_bucket_div(p.nb);
     a.out_h = out_h; a.h16 = mode == HM_CUBE_EUCLID_H && h16; a.out_phi = out_phi; a.out_bucket = out_bucket; a.mm = mm;
-    a.list = list; a.seg_counts = seg_counts; a.stats = stats;
-    a.seg_rows = (int64_t)HMF_W * 32 * ((ntiles + (int64_t)nblk * HMF_W - 1) / ((int64_t)nblk * HMF_W));
-    if (nblk > seg_cap || (int64_t)nblk * a.seg_rows > list_cap) {
+    a.list = list.p; a.seg_counts = list.counts; a.stats = stats;
+    a.seg_rows = hash_mfma_seg_rows(N, nblk);
+    if (nblk > FUSED_MAX_SEGS || (int64_t)nblk * a.seg_rows > list.bound) {
         set_error("launch_hash_mfma: list workspace too small");
         return -1;
     }

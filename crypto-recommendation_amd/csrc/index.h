@@ -43,6 +43,7 @@ struct ProjTable {
 }  // namespace lshkm
 
 struct lshkm_ctx_s;
+struct lshkm_lsh_s;
 namespace lshkm {
 // Hashing of a batch on the split-f16 MFMA kernel where it applies, else the
 // fp64 kernel (api_index.cpp).
@@ -50,6 +51,24 @@ namespace lshkm {
 // (only the MFMA kernel writes it).
 int hash_rows(lshkm_ctx_s* ctx, int mode, Pts X, int64_t N, const ProjTable& pj, int64_t nb, int32_t* out_h,
               int32_t* out_phi, int32_t* out_bucket, int32_t* mm, bool* h16 = nullptr);
+// The listed rows' exact pass (api.cpp): reference-order distances over the
+// rows of l, pruned to the candidates an f32 bound leaves where that applies.
+// exact_listed_prep: its centroid-only part, ahead of the pass that fills l;
+// then prepped. exact_dist: false = a winner distance may come from the x*x
+// chain (LSHKM_DIST_CERTIFIED). xn2 / nbv: cosine, the rows' / centroids' sums
+// of squares where the caller has them (else NULL).
+bool exact_pruned(Pts X, int d, int K, int metric);
+int exact_listed_prep(lshkm_ctx_s* ctx, const AssignJob& q);
+int exact_listed(lshkm_ctx_s* ctx, const AssignJob& q, const RowList& l, bool exact_dist, bool prepped,
+                 const double* xn2, const double* nbv);
+// One pass over the rows on the split-f16 kernels (fused.hip): assignment and,
+// with lsh, the LSH outputs. The shapes fused_route (fused_layout.h) takes.
+struct AssignRequest : AssignJob {
+    const ::lshkm_lsh_s* lsh = nullptr;          // hash in this pass (NULL: assignment alone)
+    int32_t *tuples = nullptr, *phi = nullptr, *bucket = nullptr;
+    bool force_exact = false;                    // exact distances whatever the context's mode
+};
+int fused_assign(lshkm_ctx_s* ctx, const AssignRequest& q);
 
 }  // namespace lshkm
 
@@ -60,13 +79,13 @@ struct lshkm_ctx_s {
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
     lshkm::Buf stats;            // STAT_COUNT x u64
-    // assignment workspace
+    // assignment workspace. The fused pass's sizes and regions: fused_layout.h
+    // (FusedLayout's c16, cconst, list1, counter, fix, seg1, tuples, part)
     lshkm::Buf ws_c32, ws_cconst, ws_ambig, ws_counter, ws_src, ws_hfix, ws_ct, ws_seg, ws_tuples, ws_part;
-    lshkm::Buf ws_cf32;     // fast distances: f32(c) [Kpad][128] + |c - f32(c)| [Kpad]
-    lshkm::Buf ws_c64p;     // general rows (d < 128): the zero-padded fp64 centroids [Kpad][128]
-    lshkm::Buf ws_ambig2, ws_seg2;   // the hi-only form's refinement output list
-    lshkm::Buf ws_seg3;              // hi-only cosine: segment counts of the declined winner distances (euclidean exact: of the pow fix-ups)
-    lshkm::Buf ws_xn2;               // cosine on fp64 rows: [N] sum_j pow(x_j, 2)
+    lshkm::Buf ws_cf32, ws_c64p;     // FusedLayout::cf32, c64p
+    lshkm::Buf ws_ambig2, ws_seg2;   // FusedLayout::list2, seg2
+    lshkm::Buf ws_seg3;              // FusedLayout::seg3
+    lshkm::Buf ws_xn2;               // FusedLayout::xn2
     // scatter / query / update workspace (see api_index.cpp for the slot map)
     lshkm::Buf ws[16];
     // range assignment workspace (lshkm_range_assign)

@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fused_args.h"
+#include "fused_layout.h"
 
 namespace lshkm {
 
@@ -29,6 +29,39 @@ struct Pts {
         return q;
     }
 };
+
+// One assignment: rows, centroids, metric and the two outputs.
+struct AssignJob {
+    Pts X;
+    int64_t N = 0;
+    int d = 0;
+    const double* C = nullptr;       // [K][d]
+    int K = 0;
+    int metric = 0;
+    int32_t* assign = nullptr;       // [N]
+    double* dist = nullptr;          // [N]
+};
+
+// A list on the device as the launchers take it: int32 rows, or u64 records
+// (row in the low or high half, per list). Flat (nseg == 0): entries
+// [0, min(*count, bound)). Segmented (the fused kernels' lists,
+// fused_layout.h): segment b = p[b * seg_rows ..], its length
+// counts[SEG_SLOTS * b + slot], rows in slot SEG_ROWS and records in SEG_FIX;
+// count then holds the segments' total.
+// bound <= 0: nothing to launch. p == NULL (flat): every row below bound.
+template <typename T>
+struct DevList {
+    static constexpr int slot = sizeof(T) == 4 ? SEG_ROWS : SEG_FIX;
+    T* p = nullptr;
+    unsigned long long* count = nullptr;
+    int64_t bound = 0;
+    int32_t* counts = nullptr;
+    int64_t seg_rows = 0;
+    int nseg = 0;
+    const int32_t* seg_counts() const { return nseg > 0 ? counts : nullptr; }
+};
+using RowList = DevList<int32_t>;
+using RecList = DevList<unsigned long long>;
 
 // Projection families, one launcher (hash.hip).
 enum HashMode {
@@ -69,18 +102,13 @@ struct HashMfmaParams {
 };
 // out_h: LSH euclidean tuples [N][L*k] / cube euclidean h [N][k] / cube cosine
 // vertex [N]; mm: cube euclidean h range (atomicMin/Max into a pre-set pair).
-// list / seg_counts: per-block lists of the uncertified rows (workspace).
+// list: the workspace for the uncertified rows (p, counts, bound = the entries
+// p holds); the launch splits it in per-block segments (hash_mfma_seg_rows).
 int launch_hash_mfma(hipStream_t s, int mode, const float* X, int64_t N, const HashMfmaParams& p, int32_t* out_h,
-                     int32_t* out_phi, int32_t* out_bucket, int32_t* mm, unsigned long long* list, int64_t list_cap,
-                     int32_t* seg_counts, int seg_cap, unsigned long long* stats, int h16 = 0);
+                     int32_t* out_phi, int32_t* out_bucket, int32_t* mm, const RecList& list,
+                     unsigned long long* stats, int h16 = 0);
 
 // Lloyd assignment (assign.hip).
-struct AssignWorkspace {
-    float* C32;          // [Kpad][DP]
-    float* cconst;       // [3][Kpad]  cn2, ecoef, eb
-    int32_t* ambig;      // [N] list of uncertified rows
-    unsigned long long* counters;  // [0] = ambiguous count (device)
-};
 int assign_dp(int d);    // padded dimension used by the MFMA kernel (0 = unsupported)
 int launch_centroid_prep(hipStream_t s, const double* C, int K, int Kpad, int d, int DP, int metric, bool xf64,
                          float* C32, float* cconst);
@@ -91,25 +119,19 @@ int launch_assign_mfma(hipStream_t s, Pts X, int64_t N, int d, int DP, const dou
 // rows[0..*count), written by assign_mfma_kernel<., 1>): soft-x87 distances.
 int launch_cos_fix(hipStream_t s, Pts X, int64_t N, int d, const double* C, const int32_t* rows,
                    const unsigned long long* count, const int32_t* assign, double* dist);
-int launch_assign_exact(hipStream_t s, Pts X, int64_t N, int d, const double* C, int K,
-                        int metric, const int32_t* rows, const unsigned long long* row_count,
-                        int64_t max_rows, int32_t* assign, double* dist, const int32_t* seg_counts = nullptr,
-                        int64_t seg_rows = 0, int nseg = 0, const double* xn2 = nullptr, const double* nbv = nullptr);
+// Every centroid in the reference's order, over the rows of l (cosine: xn2 /
+// nbv, the rows' and centroids' sums of squares, where the caller has them).
+int launch_assign_exact(hipStream_t s, const AssignJob& q, const RowList& l, const double* xn2 = nullptr,
+                        const double* nbv = nullptr);
 // Euclidean, listed rows, batched (CT: d * ceil64(K) doubles of workspace).
-// Segmented form (seg_counts != NULL): segment b = rows[b * seg_rows ...], count seg_counts[2b].
-int launch_assign_exact_list(hipStream_t s, Pts X, int d, const double* C, int K, double* CT,
-                             const int32_t* rows, const unsigned long long* row_count, int64_t max_rows,
-                             int32_t* assign, double* dist, const int32_t* seg_counts = nullptr,
-                             int64_t seg_rows = 0, int nseg = 0);
-// Euclidean, listed rows, K <= 1024: f32 candidate pruning, then exact order on
+int launch_assign_exact_list(hipStream_t s, const AssignJob& q, double* CT, const RowList& l);
+// Listed rows, K <= 1024: f32 candidate pruning, then exact order on
 // the candidates only (ws: d * ceil64(K) + ceil64(K) + ceil64(K)/32 floats).
 // exact_dist = 0 (LSHKM_DIST_CERTIFIED): a winner distance may come from the
 // x*x chain (<= 2^-44 relative); cluster IDs are the reference's either way.
-int launch_assign_pruned_list(hipStream_t s, Pts X, int d, const double* C, int K, float* ws,
-                              const int32_t* rows, const unsigned long long* row_count, int64_t max_rows,
-                              int32_t* assign, double* dist, const int32_t* seg_counts = nullptr,
-                              int64_t seg_rows = 0, int nseg = 0, int metric = 0, int exact_dist = 1,
-                              bool prepped = false);
+// prepped: launch_assign_pruned_prep ran for these centroids on this stream.
+int launch_assign_pruned_list(hipStream_t s, const AssignJob& q, float* ws, const RowList& l, int exact_dist,
+                              bool prepped);
 // The centroid-only part of the pruned pass (f32 transposed centroids, |c|^2,
 // the chunk bounds into ws): launched before the fused pass, off its tail;
 // then launch_assign_pruned_list(..., prepped = true).
@@ -320,83 +342,6 @@ int launch_cv_predict(hipStream_t s, const double* X, const double* x_mean, int 
                       const double* nb_sim, const int32_t* nb_cnt, int P, double* pred);
 int launch_cv_fold_sum(hipStream_t s, int64_t F, const int32_t* hide_idx, const double* old, const double* pred,
                        const int64_t* nb_ptr, double* err, double* k_sum_out, int64_t* cnt_out, bool carry);
-
-// Fused hash + assign on split-f16 MFMA (fused.hip), d = 128.
-struct FusedLaunch {
-    // optional side stream (+ fork / join events): the hash fix-up runs there
-    // beside the LIST refinement; joined before launch_fused returns, or, with
-    // defer_join, left to the caller (out: join_pending = the main stream must
-    // still wait on `join` -- the caller's exact pass then also overlaps it)
-    hipStream_t side = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    bool defer_join = false;
-    bool join_pending = false;
-    hipEvent_t side_timing = nullptr;            // recorded on the side stream after the fix-up (timing)
-    bool side_timed = false;                     // out: side_timing was recorded by this launch
-    // The kernels' argument block (fused_args.h). The caller sets what passes
-    // through unchanged: the rows (X or X64, N, d), the prepared centroids (Ch,
-    // Cl, cnh, cbound, C64, Kpad, nbv, C32 / rn32, Cd), the hash family and
-    // its outputs, assign / dist, the lists with their device counters (ambig,
-    // hfix, cfix) and stats. launch_fused sets the per-pass fields itself.
-    //   ambig / ambig_count: the rows left for the caller's exact pass
-    //   hfix / hfix_count: (row << 32 | fn mask) of uncertified hashes
-    //   cfix / cfix_counts / cfix_count: winners listed for their distance alone
-    //     by the hi-only pass (cosine declines, or, with exact euclidean
-    //     distances, pow fix-ups): [list_cap] entries, counts in cfix_counts[2b + 1]
-    //   fast_dist: the euclidean winner's distance from f32(c) in f32, certified
-    //     to 2^-20 relative (else the row is refined exactly); needs C32
-    //     [Kpad][128] = f32(c) and rn32 [Kpad] = |c - f32(c)|_2 rounded up
-    //   xn2: cosine, fp64 rows: [N] sum_j pow(x_j, 2) (launch_row_sumsq)
-    FusedArgs a = [] { FusedArgs v{}; v.nb = 1; v.d = 128; return v; }();
-    // ambig / hfix / cfix are split in per-block segments
-    int64_t list_cap = 0;                        // entries available in ambig and in hfix
-    int32_t* seg_counts = nullptr;               // [2 * seg_cap]
-    int seg_cap = 0;
-    // out: nseg > 0 when the lists are segmented (segment b = [b * seg_rows, ...))
-    int nseg = 0;
-    int64_t seg_rows = 0;
-    // metric 1: cosine Lloyd; a.nbv[c] = the reference's sequential sum of c_j^2
-    int metric = 0;
-    // general rows (no hashing, Kpad <= 512): rows = 1: fp32 rows of a.d <= 128
-    // dims (a.X); rows = 2: fp64 rows of a.d <= 128 dims (a.X64). a.C64 is then
-    // the prep's [Kpad][128] zero-padded copy, a.Cd the caller's [K][d] centroids
-    int rows = 0;
-    // K > 256: passes over centroid slices carry each lane's (best, runner-up,
-    // tile) in part[] (32 B per point)
-    void* part = nullptr;
-    int64_t part_bytes = 0;
-    // the refinement's own output list (list2 / seg_counts2: [list_cap] /
-    // [2 * seg_cap]); out: refined = rows the hi-only passes left to it (device)
-    int32_t* list2 = nullptr;
-    int32_t* seg_counts2 = nullptr;
-    unsigned long long* refined = nullptr;
-    // cosine: the refinement's declined winner distances go to a second fix-up
-    // list (hfix2: [list_cap] entries); out: the lists for cos_fix_seg, (list,
-    // segment counts) pairs
-    unsigned long long* hfix2 = nullptr;
-    int ncos_lists = 0;
-    const unsigned long long* cos_list[2] = {nullptr, nullptr};
-    const int32_t* cos_counts[2] = {nullptr, nullptr};
-    // out: the list of rows still uncertified for the exact pass
-    const int32_t* final_list = nullptr;
-    const int32_t* final_counts = nullptr;
-};
-constexpr int64_t FUSED_PART_BYTES_PER_ROW = 32;
-// List capacity the persistent form may need beyond N entries (grid <= 1024 blocks).
-constexpr int64_t FUSED_LIST_SLACK = 32 + 1024 * 12 * 32;
-constexpr int FUSED_MAX_SEGS = 1024;
-int launch_fused_prep(hipStream_t s, const double* C, int K, int Kpad, _Float16* Ch, _Float16* Cl, float* cnh,
-                      float* cbound, int metric = 0, double* nbv = nullptr, float* C32 = nullptr,
-                      float* rn32 = nullptr, int d = 128, double* C64p = nullptr);
-int launch_fused(hipStream_t s, bool hash, FusedLaunch& f);
-// out[i] = sum_j pow(x_ij, 2) in j order (glibc's pow, gpow2.h), fp64 rows
-int launch_row_sumsq(hipStream_t s, const double* X, int64_t N, int d, double* out);
-// Winners listed by the fused kernels for their distance alone (segment b:
-// list[b * seg_rows ..], count counts[2b + 1]): metric 1 the soft-x87 cosine,
-// metric 0 the euclidean chain with glibc's pow(x, 2) (gpow2.h).
-int launch_cos_fix_seg(hipStream_t s, Pts X, int d, const double* C, int nlists, const unsigned long long* const* lists,
-                       const int32_t* const* counts, int64_t seg_rows, int nseg, const int32_t* assign, double* dist,
-                       int metric, const double* xn2 = nullptr, const double* nbv = nullptr);
 
 // Range assignment (range.hip).
 int launch_range_radius(hipStream_t s, const double* C, int K, int d, int metric, double* r0,

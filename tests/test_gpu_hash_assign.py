@@ -514,3 +514,142 @@ def test_override_rows_change_between_calls(ctx, dist_mode):
         oa, od = oracle.lloyd_assign(X.cpu().numpy(), Cc.cpu().numpy(), "euclidean", src)
         assert np.array_equal(a.cpu().numpy(), oa)
         assert_dist(dist.cpu().numpy(), od, dist_mode)
+
+
+# ---- one context through every form of the fused assignment, forth and back
+_CH_NS = (0, 1, 65, 4099)
+_CH_SHAPES = [
+    # name, metric, rows, d, K, (L, k) or None, dist mode, Ns
+    ("eu_h256_cert", "euclidean", "f32", 128, 256, (8, 4), "certified", _CH_NS),
+    ("eu_h256_exact", "euclidean", "f32", 128, 256, (8, 4), "exact", _CH_NS),      # the pow fix-up region
+    ("eu_h300", "euclidean", "f32", 128, 300, (8, 4), "certified", _CH_NS),        # two refinement passes
+    ("eu_k1000", "euclidean", "f32", 128, 1000, None, "certified", (4099,)),       # two hi-only passes
+    ("cos_h300", "cosine", "f32", 128, 300, (5, 4), "certified", _CH_NS),
+    ("eu_f32_d100", "euclidean", "f32", 100, 64, (3, 4), "certified", _CH_NS),     # general rows; hashed apart
+    ("cos_f64_d100", "cosine", "f64", 100, 64, None, "certified", _CH_NS),         # the rows' sums of squares
+    ("eu_h_k3", "euclidean", "f32", 128, 64, (3, 3), "exact", _CH_NS),             # the chunked route
+]
+_CH_CACHE = {}
+
+
+def _characterisation_calls():
+    """The calls of test_fused_assign_characterisation with the oracle's outputs,
+    computed once. Rows: the synthetic grid with every 11th row past the f16
+    range guard (test_pruned_exact_pass); centroids: rows x 1.0001, so runner-ups
+    stay close (test_refinement_reached), the second a copy of the first (an
+    exact tie: the first index must win)."""
+    if "calls" in _CH_CACHE:
+        return _CH_CACHE["calls"]
+    calls = []
+    for name, metric, rows, d, K, lk, mode, Ns in _CH_SHAPES:
+        Xf = oracle.synth(0x3F1 + d, 4099, d).copy()
+        Xf[7::11, 5] = 4.0e4
+        Xf = Xf.astype(np.float64) if rows == "f64" else Xf
+        Ch = oracle.synth(0x3F1 + d, 4099, d)[(np.arange(K) * 4) % 4099].astype(np.float64) * 1.0001
+        Ch[1] = Ch[0]
+        # the inputs hold what the lists are for: rows whose two nearest
+        # centroids tie exactly, and rows whose runner-up is within 2^-10
+        Xd = Xf.astype(np.float64)
+        if metric == "euclidean":
+            D = (Xd * Xd).sum(1)[:, None] + (Ch * Ch).sum(1)[None, :] - 2.0 * Xd @ Ch.T
+        else:
+            D = 1.0 - (Xd @ Ch.T) / np.sqrt((Xd * Xd).sum(1)[:, None] * (Ch * Ch).sum(1)[None, :])
+        two = np.partition(D, 1, axis=1)[:, :2]
+        gap = (two[:, 1] - two[:, 0]) / np.maximum(np.abs(two[:, 1]), 1e-300)
+        assert np.count_nonzero(gap < 2.0 ** -10) >= 1, name
+        assert np.count_nonzero(np.abs(Xd).max(1) > 2.0 ** 15) > 300, name
+        hp = None
+        if lk is not None:
+            L, k = lk
+            if metric == "euclidean":
+                V, t, r, _ = lshkm.params_lsh_euclidean(7 + L, L, k, d, 0.5)
+                hp = dict(L=L, k=k, nb=409, w=0.5, V=V, t=t, r=r)
+            else:
+                R, _ = lshkm.params_lsh_cosine(21, L, k, d)
+                hp = dict(L=L, k=k, R=R)
+        for N in Ns:
+            Xh = np.ascontiguousarray(Xf[:N])
+            exp = {}
+            if N:
+                key = (metric, rows, d, K, N)       # the two distance modes share their inputs
+                if key not in _CH_CACHE:
+                    _CH_CACHE[key] = oracle.lloyd_assign(Xh, Ch, metric, None)
+                exp["assign"], exp["dist"] = _CH_CACHE[key]
+                if N == 4099:
+                    assert np.count_nonzero(exp["assign"] == 0) > 0, name      # the tied pair wins rows
+                if hp and metric == "euclidean":
+                    exp["tuples"], exp["phi"], exp["bucket"] = oracle.lsh_hash_euclid(
+                        Xh, hp["V"], hp["t"], np.float32(hp["w"]), hp["r"], hp["nb"])
+                elif hp:
+                    exp["phi"] = exp["bucket"] = oracle.lsh_hash_cosine(Xh, hp["R"].reshape(hp["L"], hp["k"], d))
+            calls.append(dict(name=name, metric=metric, rows=rows, d=d, K=K, hp=hp, mode=mode, N=N, X=Xh, C=Ch, exp=exp))
+    _CH_CACHE["calls"] = calls
+    return calls
+
+
+def test_fused_assign_characterisation(ctx):
+    # Every route of the assignment through ONE context, in order and then in
+    # reverse: the workspace buffers grow, their regions change meaning (hash
+    # fix-ups / cosine declines / pow fix-ups) and every pointer is derived
+    # again between calls. Each call bit-exact against the oracle (distances per
+    # the call's distance mode), the lists non-empty where the inputs are built
+    # for them. N = 0: returns 0, writes nothing, counts nothing.
+    calls = _characterisation_calls()
+    lshs = {}
+    torch = ctx.torch
+    stats = (lshkm.STAT_ASSIGN_AMBIG, lshkm.STAT_REFINED, lshkm.STAT_HASH_FIX, lshkm.STAT_POW_FIX)
+    try:
+        for c in calls + calls[::-1]:
+            tag = (c["name"], c["N"])
+            ctx.set_dist_mode(c["mode"])
+            N, d, hp, metric = c["N"], c["d"], c["hp"], c["metric"]
+            # N = 0 still gets real output buffers (8 sentinel entries each)
+            M = max(N, 8)
+            X = to_dev(ctx, c["X"]) if N else ctx.empty((0, d), torch.float64 if c["rows"] == "f64" else torch.float32)
+            C = to_dev(ctx, c["C"])
+            a = torch.full((M,), -7, dtype=torch.int32, device=ctx.dev)
+            dist = torch.full((M,), -7.0, dtype=torch.float64, device=ctx.dev)
+            tu = ph = bu = None
+            ctx.reset_stats()
+            if hp is None:
+                lshkm.lloyd_assign(ctx, X, C, metric, None, a, dist)
+            else:
+                if c["name"] not in lshs:
+                    kw = {n: hp[n] for n in ("V", "t", "r", "R") if n in hp}
+                    lshs[c["name"]] = lshkm.LSH(ctx, metric, d, hp["k"], hp["L"], hp.get("nb", 0), hp.get("w", 0.0), **kw)
+                lsh = lshs[c["name"]]
+                if metric == "euclidean":
+                    tu = torch.full((M, hp["L"], hp["k"]), -7, dtype=torch.int32, device=ctx.dev)
+                ph = torch.full((M, hp["L"]), -7, dtype=torch.int32, device=ctx.dev)
+                bu = torch.full((M, hp["L"]), -7, dtype=torch.int32, device=ctx.dev)
+                fn = lshkm._fn("lshkm_hash_assign_metric", X)
+                rc = fn(lsh.h, lshkm._t_ptr(X), N, lshkm._t_ptr(C), c["K"], lshkm._METRIC[metric], None,
+                        lshkm._t_ptr(tu), lshkm._t_ptr(ph), lshkm._t_ptr(bu), lshkm._t_ptr(a), lshkm._t_ptr(dist))
+                assert rc == 0, tag
+            ctx.sync()
+            got = {"assign": a, "dist": dist, "tuples": tu, "phi": ph, "bucket": bu}
+            got = {n: v.cpu().numpy() for n, v in got.items() if v is not None}
+            for n, v in got.items():            # nothing past the N rows (N = 0: nothing at all)
+                assert np.all(v[N:] == -7), (tag, n)
+            counted = {s: ctx.stat(s) for s in stats}
+            if N == 0:
+                assert not any(counted.values()), (tag, counted)
+                continue
+            exp = c["exp"]
+            for n in ("assign", "tuples", "phi", "bucket"):
+                if n in got:
+                    assert np.array_equal(got[n][:N], exp[n]), (tag, n)
+            fast = c["mode"] == "certified" and metric == "euclidean" and c["rows"] == "f32"
+            assert_dist(got["dist"][:N], exp["dist"], "certified" if fast else "exact")
+            print(f"characterisation {tag}: {counted}")
+            if N == 4099:
+                assert counted[lshkm.STAT_ASSIGN_AMBIG] > 0, tag     # the tied pair, the rows past the range guard
+                assert counted[lshkm.STAT_REFINED] > 0 or c["name"] == "eu_h_k3", tag     # (the chunked form has no refinement)
+                if hp and d == 128 and hp["k"] == 4:
+                    assert counted[lshkm.STAT_HASH_FIX] > 0, tag     # rows past the range guard: every floor uncertified
+                if c["name"] == "eu_h256_exact":
+                    assert counted[lshkm.STAT_POW_FIX] > 0, tag
+    finally:
+        ctx.set_dist_mode("certified")
+        for l in lshs.values():
+            l.close()

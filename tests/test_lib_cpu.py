@@ -106,6 +106,19 @@ def test_hash_certificates_match_long_double(tmp_path):
     assert "bad=0" in out.stdout
 
 
+def test_fused_layout(tmp_path):
+    # csrc/fused_layout.h on the host: regions of a buffer disjoint, the u64 lists
+    # and the pass state aligned, every grid's segments within the list capacity
+    # (N up to 2^31 - 1, every block count and wave count), the pass state
+    # covering both its users, and the form rules
+    exe = tmp_path / "fused_layout_check"
+    subprocess.run(["g++", "-O1", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tests", "fused_layout_check.cpp")],
+                   check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "bad=0" in out.stdout
+
+
 def test_kmseg_matches_chain(tmp_path):
     # the binade-segment evaluation of the fp64 chain (csrc/kmseg.h) vs the plain chain
     exe = tmp_path / "kmseg_check"
