@@ -20,25 +20,15 @@ static int read_i64(lshkm_ctx ctx, const int64_t* dev, int64_t* host) {
 
 // Host vectors handed to hipMemcpyAsync must outlive the copy: declared after
 // them, this waits for the stream on every exit path (its destructor runs
-// before theirs).
+// before theirs); with only_if, on the exit paths that left *only_if nonzero
+// (a failed call leaves nothing of its own running).
 struct StreamSyncOnExit {
     hipStream_t s;
-    ~StreamSyncOnExit() { (void)hipStreamSynchronize(s); }
+    const int* only_if = nullptr;
+    ~StreamSyncOnExit() {
+        if (!only_if || *only_if) (void)hipStreamSynchronize(s);
+    }
 };
-
-// The users' clusters on the host, each in [0, K): the reference indexes
-// clusters[user.getCluster()] (main.cpp:261, :366), so an ID outside the
-// clusters is a caller error here, not an empty neighbourhood.
-static int read_ucl(lshkm_ctx ctx, const int32_t* ucl, int64_t nq, int K, std::vector<int32_t>& hu) {
-    hu.resize((size_t)nq);
-    if (nq == 0) return 0;
-    const D2H r{hu.data(), ucl, sizeof(int32_t) * nq};
-    int rc;
-    if ((rc = d2h_batch(ctx, &r, 1))) return rc;
-    for (int64_t q = 0; q < nq; q++)
-        LSHKM_CHECK(hu[q] >= 0 && hu[q] < K, LSHKM_ERR_ARG, "ucl holds a cluster ID outside [0, K)");
-    return 0;
-}
 
 // get_P_closest's launches for candidate lists of `total` rows (at least the
 // lists' real total), on the stream, in the ws_call workspace; no host wait.
@@ -106,394 +96,295 @@ int lshkm_top_n_recom(lshkm_ctx ctx, const double* X, const double* x_mean, int6
 
 }  // extern "C"
 
-static int terms_offsets(lshkm_ctx ctx, const int64_t* crow, int K, int64_t N, const int32_t* ucl, int64_t nq,
-                         const int64_t* unk_ptr, std::vector<int64_t>& soff, std::vector<int64_t>& hup,
-                         std::vector<int64_t>& toff, std::vector<int32_t>* hu_out = nullptr);
-static int cluster_terms_impl(lshkm_ctx ctx, Pts X, const double* x_mean, int64_t N, int d, const int64_t* crow,
-                              const int32_t* crows, int K, Pts U, int64_t nq, const int32_t* ucl,
-                              const int64_t* unk_ptr, const int32_t* unk_idx, int64_t* soff_dev, int64_t* toff_dev,
-                              double* sims, double* terms, int64_t cap, int64_t tcap, int64_t* total_host,
-                              int64_t* tterms_host);
-static int chain_terms_impl(lshkm_ctx ctx, int64_t nq, const double* u_mean, const int64_t* unk_ptr,
-                            const int32_t* unk_idx, const int64_t* soff, const int64_t* toff, const double* sims,
-                            const double* terms, const double* carry_main, const double* carry_abs,
-                            const int64_t* carry_cnt, double* main_out, double* abs_out, int64_t* cnt_out, int n_top,
-                            int32_t* out);
-
+// ------------------------------------------------ clustering recommender
 // get_top_N_recom(neighbors, user, N), crypto_rec.hpp:327-345, over whole
-// clusters (main.cpp:260-269, :353-373). The cluster sizes come to the host
-// once to size the per-wave similarity scratch (waves x largest cluster).
-static int cluster_top_n_impl(lshkm_ctx ctx, Pts X, const double* x_mean, int64_t N, int d, const int64_t* crow,
-                              const int32_t* crows, int K, Pts U, const double* u_mean, int64_t nq,
-                              const int32_t* ucl, const int64_t* unk_ptr, const int32_t* unk_idx, int n_top,
-                              int32_t* out) {
-    LSHKM_CHECK(ctx && X.p && x_mean && crow && U.p && u_mean && ucl && unk_ptr && out && N >= 1 && d >= 1 &&
-                    K >= 1 && nq >= 0 && n_top >= 0,
-                LSHKM_ERR_ARG, "bad arguments");
-    if (nq == 0 || n_top == 0) return 0;
+// clusters (main.cpp:260-269, :353-373): lshkm_cluster_top_n, and its sharded
+// phases (_sims + _chain, _terms + _chain_terms). recom_layout.h states the
+// form rule and every workspace.
+//
+// Host view of one call's CSRs, read and validated once: hu = the users'
+// clusters, each in [0, K) (the reference indexes clusters[user.getCluster()],
+// main.cpp:261, :366: an ID outside the clusters is a caller error, not an
+// empty neighbourhood); soff = the prefix of each user's member count on this
+// shard; hup = the unknown-index CSR offsets; toff = the prefix of each user's
+// term count (members x unknown indexes).
+struct RecomOffsets {
+    std::vector<int32_t> hu;
+    std::vector<int64_t> soff, hup, toff;
+    int64_t max_members = 0;          // the largest cluster
+};
+
+static int check_unknowns(const RecomJob& j, const RecomOffsets& o) {
+    bool ok = o.hup[0] == 0;
+    for (int64_t q = 0; q < j.nq && ok; q++) ok = o.hup[q + 1] >= o.hup[q];
+    LSHKM_CHECK(ok, LSHKM_ERR_ARG, "bad unknown-index lists (unk_ptr must start at 0 and not decrease)");
+    LSHKM_CHECK(o.hup[j.nq] == 0 || j.unk_idx, LSHKM_ERR_ARG, "unk_idx is NULL");
+    return 0;
+}
+
+static int check_clusters(const RecomJob& j, const RecomOffsets& o) {
+    for (int64_t q = 0; q < j.nq; q++)
+        LSHKM_CHECK(o.hu[q] >= 0 && o.hu[q] < j.K, LSHKM_ERR_ARG, "ucl holds a cluster ID outside [0, K)");
+    return 0;
+}
+
+// From the cluster CSR and the users' clusters on the device: one batch of
+// copies, one synchronisation. unknowns = false (lshkm_cluster_sims): the
+// unknown-index lists are not read.
+static int recom_offsets(lshkm_ctx ctx, const RecomJob& j, bool unknowns, RecomOffsets& o) {
+    const int64_t nq = j.nq;
+    std::vector<int64_t> hc((size_t)j.K + 1);
+    o.hu.resize((size_t)nq);
+    o.hup.assign((size_t)nq + 1, 0);
+    const D2H rd[3] = {{hc.data(), j.crow, sizeof(int64_t) * (j.K + 1)},
+                       {o.hu.data(), j.ucl, sizeof(int32_t) * nq},
+                       {o.hup.data(), j.unk_ptr, unknowns ? sizeof(int64_t) * (nq + 1) : 0}};
+    int rc;
+    if ((rc = d2h_batch(ctx, rd, 3)) || (rc = check_clusters(j, o))) return rc;
+    bool ok = hc[0] == 0;
+    for (int c = 0; c < j.K && ok; c++) {
+        ok = hc[c + 1] >= hc[c];
+        o.max_members = std::max<int64_t>(o.max_members, hc[c + 1] - hc[c]);
+    }
+    LSHKM_CHECK(ok && hc[j.K] <= j.N, LSHKM_ERR_ARG,
+                "bad cluster CSR (crow must start at 0, not decrease, and hold at most N members)");
+    LSHKM_CHECK(hc[j.K] == 0 || j.crows, LSHKM_ERR_ARG, "crows is NULL");
+    LSHKM_CHECK(o.max_members < (1ll << 31), LSHKM_ERR_ARG, "a cluster of 2^31 members or more");
+    if ((rc = check_unknowns(j, o))) return rc;
+    o.soff.assign((size_t)nq + 1, 0);
+    o.toff.assign((size_t)nq + 1, 0);
+    for (int64_t q = 0; q < nq; q++) {
+        const int64_t n = hc[o.hu[q] + 1] - hc[o.hu[q]];
+        o.soff[q + 1] = o.soff[q] + n;
+        o.toff[q + 1] = o.toff[q] + n * (o.hup[q + 1] - o.hup[q]);
+    }
+    return 0;
+}
+
+// Read back from the device, for the public chain phases (their callers hold
+// only device arrays): ucl where the job has one, soff / toff where given.
+static int recom_offsets_device(lshkm_ctx ctx, const RecomJob& j, const int64_t* soff, const int64_t* toff,
+                                RecomOffsets& o) {
+    const size_t n1 = (size_t)j.nq + 1;
+    o.hu.resize(j.ucl ? (size_t)j.nq : 0);
+    o.hup.resize(n1);
+    o.soff.resize(toff ? n1 : 0);
+    o.toff.resize(toff ? n1 : 0);
+    const D2H rd[4] = {{o.hu.data(), j.ucl, sizeof(int32_t) * o.hu.size()},
+                       {o.soff.data(), soff, sizeof(int64_t) * o.soff.size()},
+                       {o.toff.data(), toff, sizeof(int64_t) * o.toff.size()},
+                       {o.hup.data(), j.unk_ptr, sizeof(int64_t) * n1}};
+    int rc;
+    if ((rc = d2h_batch(ctx, rd, 4)) || (j.ucl && (rc = check_clusters(j, o)))) return rc;
+    return check_unknowns(j, o);
+}
+
+// What one entry point asks of recom_cluster. soff / toff / sims / terms: the
+// caller's device arrays, written by SIMS / TERMS (when the totals fit cap /
+// tcap; the totals go to *total / *tterms either way) and only read by CHAIN /
+// CHAIN_TERMS, as carry_in is. out != NULL: the final step; else the running
+// sums go to carry_out.
+struct RecomRequest {
+    enum Op { TOP_N, SIMS, TERMS, CHAIN, CHAIN_TERMS } op;
+    int64_t *soff, *toff;
+    double *sims, *terms;
+    int64_t cap, tcap;
+    int64_t *total, *tterms;
+    RecomCarry carry_in, carry_out;
+    int n_top;
+    int32_t* out;
+};
+template <typename T> static T* read_only(const T* p) { return const_cast<T*>(p); }
+template <typename T> static T* at(const Buf& b, size_t off) { return reinterpret_cast<T*>(b.as<char>() + off); }
+
+// Phase 1 of the terms form: the offsets up, then, when the caller's arrays
+// hold them, every similarity and term of this shard.
+static int recom_terms(lshkm_ctx ctx, const RecomJob& j, const RecomOffsets& o, const RecomRequest& r,
+                       unsigned long long* soft) {
+    const int64_t nq = j.nq, S = o.soff[nq];
+    const H2D offs[2] = {{r.soff, o.soff.data(), sizeof(int64_t) * (nq + 1)},
+                         {r.toff, o.toff.data(), sizeof(int64_t) * (nq + 1)}};
+    if (!(r.sims && r.terms && S <= r.cap && o.toff[nq] <= r.tcap && S > 0)) return h2d_batch(ctx, offs, 2);
+    Buf &map = ctx->ws_call[8], &gb = ctx->ws_call[9];
+    const RcWorkList w = rc_work_list(o.hu, o.soff);         // staged by h2d_batch
+    const RcPackLayout pl = rc_pack_layout(w.pack.size(), w.nitems, w.nusers);
+    int rc;
+    if ((rc = map.reserve(rc_map_layout(S, nq).bytes)) || (rc = gb.reserve(pl.bytes))) return rc;
+    int32_t* dp = at<int32_t>(gb, pl.pack);
+    const H2D up[3] = {offs[0], offs[1], {dp, w.pack.data(), 4 * w.pack.size()}};
+    if ((rc = h2d_batch(ctx, up, 3))) return rc;
+    const RcGroups groups{dp, w.ngroups, w.nitems, dp + w.gcl(), dp + w.gptr(), dp + w.gusr(),
+                          at<char>(gb, pl.items), w.nusers, at<char>(gb, pl.users)};
+    // no host synchronisation: the uploads are staged (h2d_batch), the outputs
+    // and the workspaces are ordered on the stream
+    return launch_rc_terms(ctx->stream, j, RcTermsOut{r.soff, r.toff, S, r.sims, r.terms}, map.as<char>(), groups, soft);
+}
+
+// Phase 2 of the terms form: the chains from the stored terms, continued from
+// `in`, into `carry_to` or (the final step) `out`.
+static int recom_chain_terms(lshkm_ctx ctx, const RecomJob& j, const RecomOffsets& o, const RcTermsOut& t,
+                             const RecomCarry& in, const RecomCarry& carry_to, const RecomOut& out) {
+    // users whose cluster holds >= RC_LONG_MIN members here: their chains by
+    // binade segments, in batches (rc_long_batches)
+    std::vector<RcLongUser> lus;
+    for (int64_t q = 0; q < j.nq; q++) {
+        const int64_t n = o.soff[q + 1] - o.soff[q];
+        if (n >= RC_LONG_MIN)
+            lus.push_back(RcLongUser{q, n, o.soff[q], o.toff[q], o.hup[q], o.hup[q + 1] - o.hup[q], 0, 0});
+    }
+    std::vector<int64_t> hcrow;                         // staged by h2d_batch with the user table
+    const std::vector<RcLongBatch> batches = rc_long_batches(lus);
+    int rc;
+    for (const RcLongBatch& b : batches) {
+        const int64_t nl = (int64_t)(b.k1 - b.k0);
+        hcrow.assign(1, 0);
+        for (size_t k = b.k0; k < b.k1; k++) {
+            lus[k].off = hcrow.back();
+            hcrow.push_back(hcrow.back() + lus[k].n);
+        }
+        const RcLongLayout ll = rc_long_layout(b.rows, nl, b.D, seg_columns_ws_bytes(b.rows, (int)nl, (int)b.D));
+        Buf& wl = ctx->ws_long;
+        if ((rc = wl.reserve(ll.bytes))) return rc;
+        RcLongUser* tab = at<RcLongUser>(wl, ll.tab);
+        int64_t* crow = at<int64_t>(wl, ll.crow);
+        const H2D up[2] = {{tab, lus.data() + b.k0, (size_t)nl * sizeof(RcLongUser)},
+                           {crow, hcrow.data(), (size_t)(nl + 1) * 8}};
+        if ((rc = h2d_batch(ctx, up, 2))) return rc;
+        const RcLong L{tab, nl, b.rows, (int)b.D, crow, at<double>(wl, ll.V), at<double>(wl, ll.carry),
+                       at<double>(wl, ll.sums), at<int32_t>(wl, ll.iota), at<char>(wl, ll.ws)};
+        if ((rc = launch_rc_long(ctx->stream, t, in, j.u_mean, carry_to, out.pred, L))) return rc;
+        // a further batch may grow ws_long: not while this one's kernels run
+        if (&b != &batches.back()) LSHKM_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if ((rc = launch_rc_chain_terms(ctx->stream, j, t, in, carry_to, out.pred, lus.empty() ? INT64_MAX : RC_LONG_MIN)))
+        return rc;
+    // no host synchronisation: the pred / pidx workspace's next user is ordered
+    // on the same stream (a reserve that grows it frees through hipFree)
+    return out.out ? launch_rc_top(ctx->stream, j, t.soff, in.cnt, out) : 0;
+}
+
+// The one owner of a clustering-recommender call: the route (recom_route), the
+// reservations of ws_call[0, 1, 2, 5 .. 9] and ws_long, the uploads, the
+// launches and the end-of-call ordering.
+static int recom_cluster(lshkm_ctx ctx, const RecomJob& j, const RecomRequest& r) {
+    using R = RecomRequest;
+    const bool chain = r.op == R::CHAIN || r.op == R::CHAIN_TERMS;
+    const bool rows_ok = j.X.p && j.crow && j.ucl && j.N >= 1 && j.d >= 1 && j.K >= 1;
+    bool ok = ctx && j.unk_ptr && j.nq >= 0 && r.n_top >= 0 && (r.op == R::CHAIN_TERMS || rows_ok);
+    switch (r.op) {
+        case R::TOP_N: ok = ok && j.x_mean && j.U.p && j.u_mean && r.out; break;
+        case R::SIMS: ok = ok && j.U.p && r.soff && r.total && r.cap >= 0; break;
+        case R::TERMS:
+            ok = ok && j.x_mean && j.U.p && r.soff && r.toff && r.total && r.tterms && r.cap >= 0 && r.tcap >= 0;
+            break;
+        case R::CHAIN: ok = ok && j.x_mean && j.u_mean && r.soff; break;
+        case R::CHAIN_TERMS: ok = ok && j.u_mean && r.soff && r.toff; break;
+    }
+    LSHKM_CHECK(ok, LSHKM_ERR_ARG, "bad arguments");
+    if (chain) {
+        const RecomCarry &ci = r.carry_in, &co = r.carry_out;
+        LSHKM_CHECK((ci.main == nullptr) == (ci.abs == nullptr) && (ci.abs == nullptr) == (ci.cnt == nullptr),
+                    LSHKM_ERR_ARG, "carry_main / carry_abs / carry_cnt: all or none");
+        LSHKM_CHECK(r.out || (co.main && co.abs && co.cnt), LSHKM_ERR_ARG, "either the carry outputs or out");
+    }
+    LSHKM_CHECK(r.op != R::TERMS || recom_route(j.d, j.X.f64, 0) == RecomRoute::terms, LSHKM_ERR_ARG,
+                "the terms form stages rows of a multiple of 8 B up to " + std::to_string(RC_ROW_MAX) +
+                    " B (use lshkm_cluster_sims)");
+    if ((r.op == R::TOP_N && (j.nq == 0 || r.n_top == 0)) || (chain && j.nq == 0)) return 0;
     LSHKM_HIP(hipSetDevice(ctx->device));
-    {   // the terms form (recom.hip) when the rows stage and the terms fit 2 GiB
-        const int64_t rb = (int64_t)d * (X.f64 ? 8 : 4);
-        if (rb % 8 == 0 && rb <= 1016) {
-            std::vector<int64_t> soff, hup, toff;
-            int rc;
-            if ((rc = terms_offsets(ctx, crow, K, N, ucl, nq, unk_ptr, soff, hup, toff))) return rc;
-            if (toff[nq] <= (1ll << 28)) {
+
+    int rc = 0;
+    const StreamSyncOnExit sync_guard{ctx->stream, &rc};     // a failed call leaves nothing running
+    RecomOffsets o;
+    if ((rc = chain ? recom_offsets_device(ctx, j, r.op == R::CHAIN_TERMS ? r.soff : nullptr,
+                                           r.op == R::CHAIN_TERMS ? r.toff : nullptr, o)
+                    : recom_offsets(ctx, j, r.op != R::SIMS, o)))
+        return rc;
+    const int64_t nq = j.nq, S = chain ? 0 : o.soff[nq], T = chain ? 0 : o.toff[nq];
+    // the final step's predictions, or the running sums carried on: one or the other
+    const bool final_step = r.out != nullptr;
+    const RecomCarry carry_to = final_step ? RecomCarry{} : r.carry_out;
+    RecomOut out{};
+    if (final_step) {
+        Buf &pred = ctx->ws_call[1], &pidx = ctx->ws_call[2];
+        const size_t M = (size_t)std::max<int64_t>(o.hup[nq], 1);
+        if ((rc = pred.reserve(sizeof(double) * M)) || (rc = pidx.reserve(sizeof(int32_t) * M))) return rc;
+        out = RecomOut{pred.as<double>(), pidx.as<int32_t>(), r.n_top, r.out};
+    }
+    unsigned long long* soft = (unsigned long long*)ctx->stats.p + STAT_REC_SOFT;
+    switch (r.op) {
+        case R::TOP_N: {
+            if (recom_route(j.d, j.X.f64, T) == RecomRoute::terms) {
                 Buf &bs = ctx->ws_call[0], &bt = ctx->ws_call[5], &bso = ctx->ws_call[6], &bto = ctx->ws_call[7];
-                if ((rc = bs.reserve(8 * (size_t)std::max<int64_t>(soff[nq], 1))) ||
-                    (rc = bt.reserve(8 * (size_t)std::max<int64_t>(toff[nq], 1))) ||
+                if ((rc = bs.reserve(8 * (size_t)std::max<int64_t>(S, 1))) ||
+                    (rc = bt.reserve(8 * (size_t)std::max<int64_t>(T, 1))) ||
                     (rc = bso.reserve(8 * (size_t)(nq + 1))) || (rc = bto.reserve(8 * (size_t)(nq + 1))))
                     return rc;
-                int64_t tot = 0, tt = 0;
-                if ((rc = cluster_terms_impl(ctx, X, x_mean, N, d, crow, crows, K, U, nq, ucl, unk_ptr, unk_idx,
-                                             bso.as<int64_t>(), bto.as<int64_t>(), bs.as<double>(), bt.as<double>(),
-                                             soff[nq], toff[nq], &tot, &tt)))
-                    return rc;
-                return chain_terms_impl(ctx, nq, u_mean, unk_ptr, unk_idx, bso.as<int64_t>(), bto.as<int64_t>(),
-                                        bs.as<double>(), bt.as<double>(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                                        nullptr, n_top, out);
+                R t = r;
+                t.soff = bso.as<int64_t>(), t.toff = bto.as<int64_t>();
+                t.sims = bs.as<double>(), t.terms = bt.as<double>();
+                t.cap = S, t.tcap = T;
+                if ((rc = recom_terms(ctx, j, o, t, soft))) return rc;
+                return rc = recom_chain_terms(ctx, j, o, RcTermsOut{t.soff, t.toff, S, t.sims, t.terms}, RecomCarry{},
+                                              carry_to, out);
             }
+            // one wave per user; ws_call[0] is the terms form's similarities otherwise
+            const RcWaveScratch ws = rc_wave_scratch(nq, o.max_members);
+            Buf& scratch = ctx->ws_call[0];
+            if ((rc = scratch.reserve(ws.bytes)) ||
+                (rc = launch_rc_cluster_top_n(ctx->stream, j, scratch.as<double>(), ws, out, soft)))
+                return rc;
+            break;
         }
-    }
-    std::vector<int64_t> hc((size_t)K + 1);
-    std::vector<int32_t> hu;
-    int64_t total = 0;
-    {
-        int rc;
-        if ((rc = read_ucl(ctx, ucl, nq, K, hu))) return rc;
-    }
-    {
-        const D2H rd[2] = {{hc.data(), crow, sizeof(int64_t) * (K + 1)}, {&total, unk_ptr + nq, sizeof(int64_t)}};
-        int rc;
-        if ((rc = d2h_batch(ctx, rd, 2))) return rc;
-    }
-    int64_t maxn = 0;
-    bool ok = hc[0] == 0;
-    for (int c = 0; c < K && ok; c++) {
-        ok = hc[c + 1] >= hc[c];
-        maxn = std::max<int64_t>(maxn, hc[c + 1] - hc[c]);
-    }
-    LSHKM_CHECK(ok && hc[K] <= N && (hc[K] == 0 || crows), LSHKM_ERR_ARG,
-                "bad cluster CSR (crow must start at 0, not decrease, and hold at most N members)");
-    LSHKM_CHECK(maxn < (1ll << 31), LSHKM_ERR_ARG, "a cluster of 2^31 members or more");
-    LSHKM_CHECK(total >= 0 && (total == 0 || unk_idx), LSHKM_ERR_ARG, "bad unknown-index lists");
-    // one wave per user in flight; the scratch row of a wave holds one cluster's
-    // similarities (at most 1 GiB of scratch: fewer waves for huge clusters)
-    const int64_t row = std::max<int64_t>(maxn, 1);
-    int64_t nw = std::min<int64_t>(nq, 8192);
-    nw = std::min<int64_t>(nw, std::max<int64_t>((int64_t)RC_CLUSTER_WAVES_PER_BLOCK, (1ll << 30) / (row * 8)));
-    nw = (nw + RC_CLUSTER_WAVES_PER_BLOCK - 1) / RC_CLUSTER_WAVES_PER_BLOCK * RC_CLUSTER_WAVES_PER_BLOCK;
-    Buf &scratch = ctx->ws_call[0], &pred = ctx->ws_call[1], &pidx = ctx->ws_call[2];
-    const size_t M = (size_t)(total > 0 ? total : 1);
-    int rc;
-    if ((rc = scratch.reserve(sizeof(double) * (size_t)nw * row)) || (rc = pred.reserve(sizeof(double) * M)) ||
-        (rc = pidx.reserve(sizeof(int32_t) * M)))
-        return rc;
-    if ((rc = launch_rc_cluster_top_n(ctx->stream, X, x_mean, d, crow, crows, K, U, u_mean, nq, ucl, unk_ptr, unk_idx,
-                                      n_top, scratch.as<double>(), row, (int)nw, pred.as<double>(), pidx.as<int32_t>(),
-                                      out, (unsigned long long*)ctx->stats.p + STAT_REC_SOFT))) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
+        case R::SIMS: {
+            *r.total = S;
+            const H2D up{r.soff, o.soff.data(), sizeof(int64_t) * (nq + 1)};
+            if ((rc = h2d_batch(ctx, &up, 1))) return rc;
+            if (r.sims && S <= r.cap && S > 0 && (rc = launch_rc_shard_sims(ctx->stream, j, r.soff, r.sims, soft)))
+                return rc;
+            break;
+        }
+        case R::TERMS:
+            *r.total = S;
+            *r.tterms = T;
+            return rc = recom_terms(ctx, j, o, r, soft);
+        case R::CHAIN:
+            if ((rc = launch_rc_shard_chain(ctx->stream, j, r.soff, r.sims, r.carry_in, carry_to, out))) return rc;
+            if (!final_step) return 0;
+            break;
+        case R::CHAIN_TERMS:
+            return rc = recom_chain_terms(ctx, j, o, RcTermsOut{r.soff, r.toff, o.soff[nq], r.sims, r.terms},
+                                          r.carry_in, carry_to, out);
     }
     LSHKM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is reused by the next call
     return 0;
 }
 
-// Host view of the cluster CSR: every user's member count on this shard and
-// the prefix offsets of its similarities.
-// unk_ptr / hup (optional): the unknown-index CSR offsets, read in the same
-// batch of copies (one stream synchronisation for all three)
-static int shard_offsets(lshkm_ctx ctx, const int64_t* crow, int K, int64_t N, const int32_t* ucl, int64_t nq,
-                         std::vector<int64_t>& soff, std::vector<int32_t>* hu_out = nullptr,
-                         const int64_t* unk_ptr = nullptr, std::vector<int64_t>* hup = nullptr) {
-    std::vector<int64_t> hc((size_t)K + 1);
-    std::vector<int32_t> hu((size_t)nq);
-    if (hup) hup->assign((size_t)nq + 1, 0);
-    const D2H rd[3] = {{hc.data(), crow, sizeof(int64_t) * (K + 1)},
-                       {hu.data(), ucl, sizeof(int32_t) * nq},
-                       {hup ? hup->data() : nullptr, unk_ptr, hup ? sizeof(int64_t) * (nq + 1) : 0}};
-    int rc;
-    if ((rc = d2h_batch(ctx, rd, 3))) return rc;
-    for (int64_t q = 0; q < nq; q++)
-        LSHKM_CHECK(hu[q] >= 0 && hu[q] < K, LSHKM_ERR_ARG, "ucl holds a cluster ID outside [0, K)");
-    bool ok = hc[0] == 0;
-    for (int c = 0; c < K && ok; c++) ok = hc[c + 1] >= hc[c];
-    LSHKM_CHECK(ok && hc[K] <= N, LSHKM_ERR_ARG, "bad cluster CSR");
-    soff.assign((size_t)nq + 1, 0);
-    for (int64_t q = 0; q < nq; q++) {
-        const int64_t n = hc[hu[q] + 1] - hc[hu[q]];
-        LSHKM_CHECK(n < (1ll << 31), LSHKM_ERR_ARG, "a cluster of 2^31 members or more");
-        soff[q + 1] = soff[q] + n;
-    }
-    if (hu_out) hu_out->swap(hu);
-    return 0;
-}
-
-static int cluster_sims_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const int64_t* crow, const int32_t* crows, int K,
-                             Pts U, int64_t nq, const int32_t* ucl, const int64_t* unk_ptr, int64_t* soff_dev,
-                             double* sims, int64_t cap, int64_t* total_host) {
-    LSHKM_CHECK(ctx && X.p && crow && U.p && ucl && unk_ptr && soff_dev && total_host && N >= 1 && d >= 1 && K >= 1 &&
-                    nq >= 0 && cap >= 0,
-                LSHKM_ERR_ARG, "bad arguments");
-    LSHKM_HIP(hipSetDevice(ctx->device));
-    std::vector<int64_t> soff;
-    const StreamSyncOnExit sync_guard{ctx->stream};   // soff is copied before return
-    int rc;
-    if ((rc = shard_offsets(ctx, crow, K, N, ucl, nq, soff))) return rc;
-    *total_host = soff[nq];
-    const H2D up{soff_dev, soff.data(), sizeof(int64_t) * (nq + 1)};
-    if ((rc = h2d_batch(ctx, &up, 1))) return rc;
-    if (sims && soff[nq] <= cap && soff[nq] > 0) {
-        LSHKM_CHECK(crows, LSHKM_ERR_ARG, "crows is NULL");
-        if ((rc = launch_rc_shard_sims(ctx->stream, X, d, crow, crows, K, U, nq, ucl, unk_ptr, soff_dev, sims,
-                                       (unsigned long long*)ctx->stats.p + STAT_REC_SOFT)))
-            return rc;
-    }
-    LSHKM_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-static int cluster_chain_impl(lshkm_ctx ctx, Pts X, const double* x_mean, int64_t N, int d, const int64_t* crow,
-                              const int32_t* crows, int K, int64_t nq, const int32_t* ucl, const double* u_mean,
-                              const int64_t* unk_ptr, const int32_t* unk_idx, const int64_t* soff, const double* sims,
-                              const double* carry_main, const double* carry_abs, const int64_t* carry_cnt,
-                              double* main_out, double* abs_out, int64_t* cnt_out, int n_top, int32_t* out) {
-    LSHKM_CHECK(ctx && X.p && x_mean && crow && ucl && u_mean && unk_ptr && soff && N >= 1 && d >= 1 && K >= 1 &&
-                    nq >= 0 && n_top >= 0,
-                LSHKM_ERR_ARG, "bad arguments");
-    LSHKM_CHECK((carry_main == nullptr) == (carry_abs == nullptr) && (carry_abs == nullptr) == (carry_cnt == nullptr),
-                LSHKM_ERR_ARG, "carry_main / carry_abs / carry_cnt: all or none");
-    LSHKM_CHECK(out || (main_out && abs_out && cnt_out), LSHKM_ERR_ARG, "either the carry outputs or out");
-    if (nq == 0) return 0;
-    LSHKM_HIP(hipSetDevice(ctx->device));
-    int64_t total = 0;
-    int rc;
-    std::vector<int32_t> hu;
-    if ((rc = read_ucl(ctx, ucl, nq, K, hu))) return rc;
-    if ((rc = read_i64(ctx, unk_ptr + nq, &total))) return rc;
-    LSHKM_CHECK(total >= 0 && (total == 0 || unk_idx), LSHKM_ERR_ARG, "bad unknown-index lists");
-    Buf &pred = ctx->ws_call[1], &pidx = ctx->ws_call[2];
-    const size_t M = (size_t)(total > 0 ? total : 1);
-    if (out && ((rc = pred.reserve(sizeof(double) * M)) || (rc = pidx.reserve(sizeof(int32_t) * M)))) return rc;
-    if ((rc = launch_rc_shard_chain(ctx->stream, X, x_mean, d, crow, crows, K, nq, ucl, u_mean, unk_ptr, unk_idx, soff,
-                                    sims, carry_main, carry_abs, carry_cnt, out ? nullptr : main_out,
-                                    out ? nullptr : abs_out, out ? nullptr : cnt_out, n_top, pred.as<double>(),
-                                    pidx.as<int32_t>(), out))) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    if (out) LSHKM_HIP(hipStreamSynchronize(ctx->stream));   // pred / pidx workspace reused by the next call
-    return 0;
-}
-
-// ----------------------------------------------------------- terms form
-// Host offsets of the terms form: soff (members per user on this shard), the
-// unknown-index CSR (hup) and toff (terms per user: members x unknown indexes).
-static int terms_offsets(lshkm_ctx ctx, const int64_t* crow, int K, int64_t N, const int32_t* ucl, int64_t nq,
-                         const int64_t* unk_ptr, std::vector<int64_t>& soff, std::vector<int64_t>& hup,
-                         std::vector<int64_t>& toff, std::vector<int32_t>* hu_out) {
-    int rc;
-    if ((rc = shard_offsets(ctx, crow, K, N, ucl, nq, soff, hu_out, unk_ptr, &hup))) return rc;
-    toff.assign((size_t)nq + 1, 0);
-    bool ok = hup[0] == 0;
-    for (int64_t q = 0; q < nq && ok; q++) {
-        ok = hup[q + 1] >= hup[q];
-        toff[q + 1] = toff[q] + (soff[q + 1] - soff[q]) * (hup[q + 1] - hup[q]);
-    }
-    LSHKM_CHECK(ok, LSHKM_ERR_ARG, "bad unknown-index lists (unk_ptr must start at 0 and not decrease)");
-    return 0;
-}
-
-static int cluster_terms_impl(lshkm_ctx ctx, Pts X, const double* x_mean, int64_t N, int d, const int64_t* crow,
-                              const int32_t* crows, int K, Pts U, int64_t nq, const int32_t* ucl,
-                              const int64_t* unk_ptr, const int32_t* unk_idx, int64_t* soff_dev, int64_t* toff_dev,
-                              double* sims, double* terms, int64_t cap, int64_t tcap, int64_t* total_host,
-                              int64_t* tterms_host) {
-    LSHKM_CHECK(ctx && X.p && x_mean && crow && U.p && ucl && unk_ptr && soff_dev && toff_dev && total_host &&
-                    tterms_host && N >= 1 && d >= 1 && K >= 1 && nq >= 0 && cap >= 0 && tcap >= 0,
-                LSHKM_ERR_ARG, "bad arguments");
-    LSHKM_CHECK(((int64_t)d * (X.f64 ? 8 : 4)) % 8 == 0 && (int64_t)d * (X.f64 ? 8 : 4) <= 1016, LSHKM_ERR_ARG,
-                "the terms form stages rows of a multiple of 8 B up to 1016 B (use lshkm_cluster_sims)");
-    LSHKM_HIP(hipSetDevice(ctx->device));
-    std::vector<int64_t> soff, hup, toff;
-    std::vector<int32_t> hu;                       // the users' clusters (host)
-    std::vector<int32_t> pack;                     // the cluster-major work list (staged by h2d_batch)
-    int rc;
-    if ((rc = terms_offsets(ctx, crow, K, N, ucl, nq, unk_ptr, soff, hup, toff, &hu))) return rc;
-    *total_host = soff[nq];
-    *tterms_host = toff[nq];
-    LSHKM_CHECK(toff[nq] == 0 || unk_idx, LSHKM_ERR_ARG, "unk_idx is NULL");
-    const H2D offs[2] = {{soff_dev, soff.data(), sizeof(int64_t) * (nq + 1)},
-                         {toff_dev, toff.data(), sizeof(int64_t) * (nq + 1)}};
-    if (!(sims && terms && soff[nq] <= cap && toff[nq] <= tcap && soff[nq] > 0)) {
-        if ((rc = h2d_batch(ctx, offs, 2))) return rc;
-    } else {
-        LSHKM_CHECK(crows, LSHKM_ERR_ARG, "crows is NULL");
-        Buf& map = ctx->ws_call[8];                  // member -> (user, row); the declined-member list + count
-        // mq | mr | the declined list | its count | unorm | the blocks' private lists | their capacities and counts
-        if ((rc = map.reserve(24 * (size_t)soff[nq] + 16 + 8 * (size_t)nq + 16 * (size_t)RC_TERMS_GMAX))) return rc;
-        int32_t* mq = map.as<int32_t>();
-        int64_t* fl = reinterpret_cast<int64_t*>(map.as<char>() + 8 * (size_t)soff[nq]);
-        double* unorm = reinterpret_cast<double*>(fl + soff[nq] + 1);     // the users' |u|^2
-        int64_t* fregion = reinterpret_cast<int64_t*>(unorm + nq);
-        int64_t* faux = fregion + soff[nq];
-        // cluster-major work list: the users of each cluster (ascending) and the
-        // 64-member chunks of the cluster's rows on this shard, each staged once
-        // for all of them (rc_terms_cl_kernel)
-        std::vector<int32_t> byc;
-        byc.reserve((size_t)nq);
-        for (int64_t q = 0; q < nq; q++)
-            if (soff[q + 1] > soff[q]) byc.push_back((int32_t)q);
-        std::stable_sort(byc.begin(), byc.end(), [&](int32_t a, int32_t b) { return hu[a] < hu[b]; });
-        // one host buffer, one copy: ioff [G + 1] | gcl [G] | gptr [G + 1] | gusr
-        std::vector<int32_t> gcl, gptr(1, 0), ioff(1, 0);
-        for (size_t k = 0; k < byc.size(); k++) {
-            const int32_t q = byc[k];
-            if (k == 0 || hu[q] != hu[byc[k - 1]]) {
-                if (k) gptr.push_back((int32_t)k);
-                gcl.push_back(hu[q]);
-                const int64_t n = soff[q + 1] - soff[q];
-                ioff.push_back(ioff.back() + (int32_t)((n + 63) / 64));
-            }
-        }
-        gptr.push_back((int32_t)byc.size());
-        const size_t nG = gcl.size();
-        pack.reserve(3 * nG + 2 + byc.size());
-        pack.insert(pack.end(), ioff.begin(), ioff.end());
-        pack.insert(pack.end(), gcl.begin(), gcl.end());
-        pack.insert(pack.end(), gptr.begin(), gptr.end());
-        pack.insert(pack.end(), byc.begin(), byc.end());
-        Buf& gb = ctx->ws_call[9];
-        const int64_t nitems = nG ? (int64_t)ioff.back() : 0;
-        // the item and user records after the list
-        const size_t item_off = (4 * std::max<size_t>(pack.size(), 1) + 255) / 256 * 256;
-        const size_t user_off = item_off + (RC_ITEM_BYTES * (size_t)std::max<int64_t>(nitems, 1) + 255) / 256 * 256;
-        if ((rc = gb.reserve(user_off + RC_USER_BYTES * std::max<size_t>(byc.size(), 1)))) return rc;
-        int32_t* dp = gb.as<int32_t>();
-        const H2D up[3] = {offs[0], offs[1], {dp, pack.data(), 4 * pack.size()}};
-        if ((rc = h2d_batch(ctx, up, 3))) return rc;
-        const RcGroups groups{dp, (int)nG, nitems, dp + nG + 1, dp + 2 * nG + 1, dp + 3 * nG + 2, gb.as<char>() + item_off,
-                              (int64_t)byc.size(), gb.as<char>() + user_off};
-        if ((rc = launch_rc_terms(ctx->stream, X, x_mean, d, crow, crows, K, U, nq, ucl, soff_dev, soff[nq], unk_ptr,
-                                  unk_idx, toff_dev, sims, terms, mq, mq + soff[nq], fl,
-                                  reinterpret_cast<unsigned long long*>(fl + soff[nq]),
-                                  (unsigned long long*)ctx->stats.p + STAT_REC_SOFT, unorm, &groups, fregion, faux)))
-            return rc;
-    }
-    // no host synchronisation: the uploads are staged (h2d_batch), the outputs
-    // and the workspaces are ordered on the stream
-    return 0;
-}
-
-static int chain_terms_impl(lshkm_ctx ctx, int64_t nq, const double* u_mean, const int64_t* unk_ptr,
-                            const int32_t* unk_idx, const int64_t* soff, const int64_t* toff, const double* sims,
-                            const double* terms, const double* carry_main, const double* carry_abs,
-                            const int64_t* carry_cnt, double* main_out, double* abs_out, int64_t* cnt_out, int n_top,
-                            int32_t* out) {
-    LSHKM_CHECK(ctx && u_mean && unk_ptr && soff && toff && nq >= 0 && n_top >= 0, LSHKM_ERR_ARG, "bad arguments");
-    LSHKM_CHECK((carry_main == nullptr) == (carry_abs == nullptr) && (carry_abs == nullptr) == (carry_cnt == nullptr),
-                LSHKM_ERR_ARG, "carry_main / carry_abs / carry_cnt: all or none");
-    LSHKM_CHECK(out || (main_out && abs_out && cnt_out), LSHKM_ERR_ARG, "either the carry outputs or out");
-    if (nq == 0) return 0;
-    LSHKM_HIP(hipSetDevice(ctx->device));
-    int rc;
-    // users whose cluster holds >= RC_LONG_MIN members here: their chains by
-    // binade segments (the offsets come to the host to find them), in batches of
-    // at most ~1 GiB of packed values; the unknown-index total is hu[nq] (one
-    // batch of copies, one synchronisation)
-    std::vector<int64_t> hs((size_t)nq + 1), ht((size_t)nq + 1), hu((size_t)nq + 1);
-    {
-        const D2H rd[3] = {{hs.data(), soff, sizeof(int64_t) * (nq + 1)},
-                           {ht.data(), toff, sizeof(int64_t) * (nq + 1)},
-                           {hu.data(), unk_ptr, sizeof(int64_t) * (nq + 1)}};
-        if ((rc = d2h_batch(ctx, rd, 3))) return rc;
-    }
-    const int64_t total = hu[nq];
-    LSHKM_CHECK(total == 0 || unk_idx, LSHKM_ERR_ARG, "unk_idx is NULL");
-    Buf &pred = ctx->ws_call[1], &pidx = ctx->ws_call[2];
-    const size_t M = (size_t)(total > 0 ? total : 1);
-    if (out && ((rc = pred.reserve(sizeof(double) * M)) || (rc = pidx.reserve(sizeof(int32_t) * M)))) return rc;
-    std::vector<RcLongUser> lus;
-    for (int64_t q = 0; q < nq; q++) {
-        const int64_t n = hs[q + 1] - hs[q];
-        if (n >= RC_LONG_MIN) lus.push_back(RcLongUser{q, n, hs[q], ht[q], hu[q], hu[q + 1] - hu[q], 0, 0});
-    }
-    std::vector<int64_t> hcrow;                         // staged by h2d_batch with the user table
-    const int64_t long_min = lus.empty() ? INT64_MAX : RC_LONG_MIN;
-    for (size_t k0 = 0; k0 < lus.size();) {
-        // a batch: users k0 .. k1-1, D = their max m + 1, rows * D * 8 <= 1 GiB (one user at least)
-        size_t k1 = k0;
-        int64_t rows = 0, D = 1;
-        while (k1 < lus.size()) {
-            const int64_t D2 = std::max<int64_t>(D, lus[k1].m + 1), rows2 = rows + lus[k1].n;
-            if (k1 > k0 && (rows2 * D2 * 8 > (1ll << 30) || rows2 >= (1ll << 31))) break;
-            D = D2;
-            rows = rows2;
-            k1++;
-        }
-        const int64_t nl = (int64_t)(k1 - k0);
-        hcrow.assign(1, 0);
-        for (size_t k = k0; k < k1; k++) {
-            lus[k].off = hcrow.back();
-            hcrow.push_back(hcrow.back() + lus[k].n);
-        }
-        const size_t wsb = (seg_columns_ws_bytes(rows, (int)nl, (int)D) + 255) / 256 * 256;
-        const size_t vb = (size_t)rows * D * 8, cb = (size_t)nl * D * 8;
-        const size_t tb = (size_t)nl * sizeof(RcLongUser), rb = (size_t)(nl + 1) * 8;
-        const size_t nb = wsb + vb + 2 * cb + tb + rb + (size_t)rows * 4 + 256;
-        if ((rc = ctx->ws_long.reserve(nb))) return rc;
-        char* b = ctx->ws_long.as<char>();
-        RcLong L{};
-        L.ws = b;
-        L.V = reinterpret_cast<double*>(b + wsb);
-        L.carry = L.V + (size_t)rows * D;
-        L.sums = L.carry + (size_t)nl * D;
-        RcLongUser* tab = reinterpret_cast<RcLongUser*>(L.sums + (size_t)nl * D);
-        int64_t* crow = reinterpret_cast<int64_t*>(tab + nl);
-        L.iota = reinterpret_cast<int32_t*>(crow + nl + 1);
-        L.tab = tab;
-        L.crow = crow;
-        L.nlong = nl;
-        L.rows = rows;
-        L.D = (int)D;
-        const H2D up[2] = {{tab, lus.data() + k0, tb}, {crow, hcrow.data(), rb}};
-        if ((rc = h2d_batch(ctx, up, 2))) return rc;
-        if ((rc = launch_rc_long(ctx->stream, sims, terms, carry_main, carry_abs, carry_cnt, u_mean,
-                                 out ? nullptr : main_out, out ? nullptr : abs_out, out ? nullptr : cnt_out,
-                                 out ? pred.as<double>() : nullptr, L)))
-            return rc;
-        // a further batch may grow ws_long: not while this one's kernels run
-        if (k1 < lus.size()) LSHKM_HIP(hipStreamSynchronize(ctx->stream));
-        k0 = k1;
-    }
-    if ((rc = launch_rc_chain_terms(ctx->stream, nq, soff, unk_ptr, toff, sims, terms, carry_main, carry_abs, carry_cnt, u_mean,
-                                    out ? nullptr : main_out, out ? nullptr : abs_out, out ? nullptr : cnt_out,
-                                    out ? pred.as<double>() : nullptr, long_min))) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    if (out && (rc = launch_rc_top(ctx->stream, nq, soff, carry_cnt, unk_ptr, unk_idx, pred.as<double>(),
-                                   pidx.as<int32_t>(), n_top, out))) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    // no host synchronisation: the pred / pidx workspace's next user is ordered
-    // on the same stream (a reserve that grows it frees through hipFree)
-    return 0;
+// The request of an entry point that ends in (or is) a chain phase: the arrays
+// it only reads, the carry in and out, the final step's n_top / out.
+static RecomRequest chain_request(RecomRequest::Op op, const int64_t* soff, const int64_t* toff, const double* sims,
+                                  const double* terms, const double* cm, const double* ca, const int64_t* cc,
+                                  double* mo, double* ao, int64_t* co, int n_top, int32_t* out) {
+    return {op, read_only(soff), read_only(toff), read_only(sims), read_only(terms), 0, 0, nullptr, nullptr,
+            {read_only(cm), read_only(ca), read_only(cc)}, {mo, ao, co}, n_top, out};
 }
 
 extern "C" {
 
+int lshkm_cluster_terms_supported(int d, int f64) { return recom_route(d, f64 != 0, 0) == RecomRoute::terms; }
+
 int lshkm_cluster_sims(lshkm_ctx ctx, const float* X, int64_t N, int d, const int64_t* crow, const int32_t* crows,
                        int K, const float* U, int64_t nq, const int32_t* ucl, const int64_t* unk_ptr,
                        int64_t* soff, double* sims, int64_t cap, int64_t* total) {
-    return cluster_sims_impl(ctx, X, N, d, crow, crows, K, U, nq, ucl, unk_ptr, soff, sims, cap, total);
+    return recom_cluster(ctx, {X, nullptr, N, d, crow, crows, K, U, nullptr, nq, ucl, unk_ptr, nullptr},
+                         {RecomRequest::SIMS, soff, nullptr, sims, nullptr, cap, 0, total});
 }
 
 int lshkm_cluster_sims_f64(lshkm_ctx ctx, const double* X, int64_t N, int d, const int64_t* crow,
                            const int32_t* crows, int K, const double* U, int64_t nq, const int32_t* ucl,
                            const int64_t* unk_ptr, int64_t* soff, double* sims, int64_t cap, int64_t* total) {
-    return cluster_sims_impl(ctx, X, N, d, crow, crows, K, U, nq, ucl, unk_ptr, soff, sims, cap, total);
+    return recom_cluster(ctx, {X, nullptr, N, d, crow, crows, K, U, nullptr, nq, ucl, unk_ptr, nullptr},
+                         {RecomRequest::SIMS, soff, nullptr, sims, nullptr, cap, 0, total});
 }
 
 int lshkm_cluster_chain(lshkm_ctx ctx, const float* X, const double* x_mean, int64_t N, int d, const int64_t* crow,
@@ -501,8 +392,9 @@ int lshkm_cluster_chain(lshkm_ctx ctx, const float* X, const double* x_mean, int
                         const int64_t* unk_ptr, const int32_t* unk_idx, const int64_t* soff, const double* sims,
                         const double* carry_main, const double* carry_abs, const int64_t* carry_cnt,
                         double* main_out, double* abs_out, int64_t* cnt_out, int n_top, int32_t* out) {
-    return cluster_chain_impl(ctx, X, x_mean, N, d, crow, crows, K, nq, ucl, u_mean, unk_ptr, unk_idx, soff, sims,
-                              carry_main, carry_abs, carry_cnt, main_out, abs_out, cnt_out, n_top, out);
+    return recom_cluster(ctx, {X, x_mean, N, d, crow, crows, K, Pts(), u_mean, nq, ucl, unk_ptr, unk_idx},
+                         chain_request(RecomRequest::CHAIN, soff, nullptr, sims, nullptr, carry_main, carry_abs, carry_cnt,
+                                       main_out, abs_out, cnt_out, n_top, out));
 }
 
 int lshkm_cluster_chain_f64(lshkm_ctx ctx, const double* X, const double* x_mean, int64_t N, int d,
@@ -511,16 +403,17 @@ int lshkm_cluster_chain_f64(lshkm_ctx ctx, const double* X, const double* x_mean
                             const double* sims, const double* carry_main, const double* carry_abs,
                             const int64_t* carry_cnt, double* main_out, double* abs_out, int64_t* cnt_out, int n_top,
                             int32_t* out) {
-    return cluster_chain_impl(ctx, X, x_mean, N, d, crow, crows, K, nq, ucl, u_mean, unk_ptr, unk_idx, soff, sims,
-                              carry_main, carry_abs, carry_cnt, main_out, abs_out, cnt_out, n_top, out);
+    return recom_cluster(ctx, {X, x_mean, N, d, crow, crows, K, Pts(), u_mean, nq, ucl, unk_ptr, unk_idx},
+                         chain_request(RecomRequest::CHAIN, soff, nullptr, sims, nullptr, carry_main, carry_abs, carry_cnt,
+                                       main_out, abs_out, cnt_out, n_top, out));
 }
 
 int lshkm_cluster_terms(lshkm_ctx ctx, const float* X, const double* x_mean, int64_t N, int d, const int64_t* crow,
                         const int32_t* crows, int K, const float* U, int64_t nq, const int32_t* ucl,
                         const int64_t* unk_ptr, const int32_t* unk_idx, int64_t* soff, int64_t* toff, double* sims,
                         double* terms, int64_t cap, int64_t tcap, int64_t* total, int64_t* tterms) {
-    return cluster_terms_impl(ctx, X, x_mean, N, d, crow, crows, K, U, nq, ucl, unk_ptr, unk_idx, soff, toff, sims,
-                              terms, cap, tcap, total, tterms);
+    return recom_cluster(ctx, {X, x_mean, N, d, crow, crows, K, U, nullptr, nq, ucl, unk_ptr, unk_idx},
+                         {RecomRequest::TERMS, soff, toff, sims, terms, cap, tcap, total, tterms});
 }
 
 int lshkm_cluster_terms_f64(lshkm_ctx ctx, const double* X, const double* x_mean, int64_t N, int d,
@@ -528,8 +421,8 @@ int lshkm_cluster_terms_f64(lshkm_ctx ctx, const double* X, const double* x_mean
                             const int32_t* ucl, const int64_t* unk_ptr, const int32_t* unk_idx, int64_t* soff,
                             int64_t* toff, double* sims, double* terms, int64_t cap, int64_t tcap, int64_t* total,
                             int64_t* tterms) {
-    return cluster_terms_impl(ctx, X, x_mean, N, d, crow, crows, K, U, nq, ucl, unk_ptr, unk_idx, soff, toff, sims,
-                              terms, cap, tcap, total, tterms);
+    return recom_cluster(ctx, {X, x_mean, N, d, crow, crows, K, U, nullptr, nq, ucl, unk_ptr, unk_idx},
+                         {RecomRequest::TERMS, soff, toff, sims, terms, cap, tcap, total, tterms});
 }
 
 int lshkm_cluster_chain_terms(lshkm_ctx ctx, int64_t nq, const double* u_mean, const int64_t* unk_ptr,
@@ -537,21 +430,26 @@ int lshkm_cluster_chain_terms(lshkm_ctx ctx, int64_t nq, const double* u_mean, c
                               const double* terms, const double* carry_main, const double* carry_abs,
                               const int64_t* carry_cnt, double* main_out, double* abs_out, int64_t* cnt_out,
                               int n_top, int32_t* out) {
-    return chain_terms_impl(ctx, nq, u_mean, unk_ptr, unk_idx, soff, toff, sims, terms, carry_main, carry_abs,
-                            carry_cnt, main_out, abs_out, cnt_out, n_top, out);
+    return recom_cluster(ctx, {Pts(), nullptr, 0, 0, nullptr, nullptr, 0, Pts(), u_mean, nq, nullptr, unk_ptr, unk_idx},
+                         chain_request(RecomRequest::CHAIN_TERMS, soff, toff, sims, terms, carry_main, carry_abs, carry_cnt,
+                                       main_out, abs_out, cnt_out, n_top, out));
 }
 
 int lshkm_cluster_top_n(lshkm_ctx ctx, const float* X, const double* x_mean, int64_t N, int d, const int64_t* crow,
                         const int32_t* crows, int K, const float* U, const double* u_mean, int64_t nq,
                         const int32_t* ucl, const int64_t* unk_ptr, const int32_t* unk_idx, int n_top, int32_t* out) {
-    return cluster_top_n_impl(ctx, X, x_mean, N, d, crow, crows, K, U, u_mean, nq, ucl, unk_ptr, unk_idx, n_top, out);
+    return recom_cluster(ctx, {X, x_mean, N, d, crow, crows, K, U, u_mean, nq, ucl, unk_ptr, unk_idx},
+                         chain_request(RecomRequest::TOP_N, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, nullptr, n_top, out));
 }
 
 int lshkm_cluster_top_n_f64(lshkm_ctx ctx, const double* X, const double* x_mean, int64_t N, int d,
                             const int64_t* crow, const int32_t* crows, int K, const double* U, const double* u_mean,
                             int64_t nq, const int32_t* ucl, const int64_t* unk_ptr, const int32_t* unk_idx, int n_top,
                             int32_t* out) {
-    return cluster_top_n_impl(ctx, X, x_mean, N, d, crow, crows, K, U, u_mean, nq, ucl, unk_ptr, unk_idx, n_top, out);
+    return recom_cluster(ctx, {X, x_mean, N, d, crow, crows, K, U, u_mean, nq, ucl, unk_ptr, unk_idx},
+                         chain_request(RecomRequest::TOP_N, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, nullptr, n_top, out));
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "fused_layout.h"
+#include "recom_layout.h"
 
 namespace lshkm {
 
@@ -250,49 +251,66 @@ int launch_kmeans_pp(hipStream_t s, Pts X, int64_t N, int d, int K, int metric, 
 
 // Recommend step (recom.hip): fp64 rows, per-user candidate CSR.
 int launch_rc_norms(hipStream_t s, const double* X, int64_t N, int d, double* xa);
-int launch_rc_cluster_top_n(hipStream_t s, Pts X, const double* x_mean, int d, const int64_t* crow,
-                            const int32_t* crows, int K, Pts U, const double* u_mean, int64_t nq, const int32_t* ucl,
-                            const int64_t* unk_ptr, const int32_t* unk_idx, int n_top, double* scratch,
-                            int64_t scratch_row, int nwaves, double* pred, int32_t* pidx, int32_t* out,
-                            unsigned long long* soft_count);
-// The terms form of the clustering recommender (recom.hip): similarities and
-// the per-(member, unknown index) terms of every user at once, then the chains
-// one wave per user (its chains lane by lane), then the quicksort per user.
-int rc_terms_stride8(int d, int elem);
-// Cluster-major work list of the terms form (rc_terms_cl_kernel): group g =
-// the users gusr[gptr[g] .. gptr[g + 1]) of cluster gcl[g]; its 64-member
-// chunks are the items ioff[g] .. ioff[g + 1] - 1 (nitems = ioff[ngroups]).
-struct RcGroups {
+// The clustering recommender (lshkm_cluster_*): recom_layout.h states its form
+// rule and workspaces. One call's inputs: rows X [N][d] with their means, the
+// cluster CSR (crow [K + 1], crows), the users U [nq][d] with their means and
+// clusters, the unknown-index CSR.
+struct RecomJob {
+    Pts X;
+    const double* x_mean;
+    int64_t N;
+    int d;
+    const int64_t* crow;
+    const int32_t* crows;
+    int K;
+    Pts U;
+    const double* u_mean;
+    int64_t nq;
+    const int32_t* ucl;
+    const int64_t* unk_ptr;
+    const int32_t* unk_idx;
+};
+// The running prediction sums between shards: main [total unknowns], abs / cnt
+// [nq]. As the carry in (only read; all NULL on the first shard) and as the
+// carry out (all NULL on the final step, which writes RecomOut instead).
+struct RecomCarry {
+    double *main, *abs;
+    int64_t* cnt;
+};
+// The final step: predictions (pred / pidx [total unknowns], workspace), then
+// out [nq][n_top]. All NULL when the running sums are carried on.
+struct RecomOut {
+    double* pred;
+    int32_t* pidx;
+    int n_top;
+    int32_t* out;
+};
+// one wave per user (rows of any size): scratch = rc_wave_scratch(nq, largest cluster)
+int launch_rc_cluster_top_n(hipStream_t s, const RecomJob& j, double* scratch, const RcWaveScratch& ws,
+                            const RecomOut& o, unsigned long long* soft_count);
+// The terms form (recom_route): similarities and the per-(member, unknown index)
+// terms of every user at once, then the chains one wave per user (its chains
+// lane by lane), then the quicksort per user.
+struct RcGroups {                // the device image of RcWorkList / RcPackLayout
     const int32_t* ioff;
     int ngroups;
     int64_t nitems;
     const int32_t* gcl;
     const int32_t* gptr;
     const int32_t* gusr;
-    void* items;              // nitems x 32 B (16-B aligned): the per-item records (rc_item_meta_kernel)
-    int64_t nusers;           // gptr[ngroups]: the work list's users
-    void* users;              // nusers x 48 B (16-B aligned): the per-user records (rc_user_meta_kernel)
+    void* items;              // nitems x RC_ITEM_BYTES
+    int64_t nusers;
+    void* users;              // nusers x RC_USER_BYTES
 };
-constexpr size_t RC_ITEM_BYTES = 32, RC_USER_BYTES = 48;
-int launch_rc_terms(hipStream_t s, Pts X, const double* x_mean, int d, const int64_t* crow, const int32_t* crows,
-                    int K, Pts U, int64_t nq, const int32_t* ucl, const int64_t* soff, int64_t total,
-                    const int64_t* unk_ptr, const int32_t* unk_idx, const int64_t* toff, double* sims, double* terms,
-                    int32_t* mem_q, int32_t* mem_r, int64_t* fix_list, unsigned long long* fix_count,
-                    unsigned long long* soft_count, double* unorm, const RcGroups* groups, int64_t* fix_region,
-                    int64_t* fix_aux);
-// fix_region: total entries (the terms blocks' private decline lists); fix_aux: 2 x RC_TERMS_GMAX
-constexpr int RC_TERMS_GMAX = 8192;
-// Users whose cluster holds >= RC_LONG_MIN members on this shard: their
-// prediction chains by binade segments (launch_seg_columns, all such users in
-// one set of launches) instead of one wave's sequential adds. Device
-// workspace: tab [nlong] RcLongUser, crow [nlong + 1] (row offsets in V), V
-// [rows][D] (D = max m + 1: each user's terms, zero-padded, then |sim|),
-// iota [rows], carry / sums [nlong][D], ws (seg_columns_ws_bytes).
-constexpr int64_t RC_LONG_MIN = 16384;
-struct RcLongUser {
-    int64_t q, n, b0, toff, u0, m, off, pad;
+struct RcTermsOut {              // soff / toff [nq + 1] on the device, total = soff[nq]
+    const int64_t *soff, *toff;
+    int64_t total;
+    double *sims, *terms;
 };
-struct RcLong {
+// map: the base of a buffer of rc_map_layout(total, nq)
+int launch_rc_terms(hipStream_t s, const RecomJob& j, const RcTermsOut& t, char* map, const RcGroups& groups,
+                    unsigned long long* soft_count);
+struct RcLong {                  // one batch of long users (RcLongBatch) in its RcLongLayout
     const RcLongUser* tab;
     int64_t nlong, rows;
     int D;
@@ -301,24 +319,16 @@ struct RcLong {
     int32_t* iota;
     void* ws;
 };
-int launch_rc_chain_terms(hipStream_t s, int64_t nq, const int64_t* soff, const int64_t* unk_ptr, const int64_t* toff,
-                          const double* sims, const double* terms, const double* carry_main, const double* carry_abs,
-                          const int64_t* carry_cnt, const double* u_mean, double* main_out, double* abs_out,
-                          int64_t* cnt_out, double* pred, int64_t long_min = INT64_MAX);
-int launch_rc_long(hipStream_t s, const double* sims, const double* terms, const double* carry_main,
-                   const double* carry_abs, const int64_t* carry_cnt, const double* u_mean, double* main_out,
-                   double* abs_out, int64_t* cnt_out, double* pred, const RcLong& lng);
-int launch_rc_top(hipStream_t s, int64_t nq, const int64_t* soff, const int64_t* carry_cnt, const int64_t* unk_ptr,
-                  const int32_t* unk_idx, double* pred, int32_t* pidx, int n_top, int32_t* out);
-constexpr int RC_CLUSTER_WAVES_PER_BLOCK = 4;     // rc_cluster_top_n_kernel: waves per block (RC_WAVES)
-int launch_rc_shard_sims(hipStream_t s, Pts X, int d, const int64_t* crow, const int32_t* crows, int K, Pts U,
-                         int64_t nq, const int32_t* ucl, const int64_t* unk_ptr, const int64_t* soff, double* sims,
+// users of fewer than long_min members (INT64_MAX: every user)
+int launch_rc_chain_terms(hipStream_t s, const RecomJob& j, const RcTermsOut& t, const RecomCarry& in,
+                          const RecomCarry& out, double* pred, int64_t long_min);
+int launch_rc_long(hipStream_t s, const RcTermsOut& t, const RecomCarry& in, const double* u_mean,
+                   const RecomCarry& out, double* pred, const RcLong& lng);
+int launch_rc_top(hipStream_t s, const RecomJob& j, const int64_t* soff, const int64_t* carry_cnt, const RecomOut& o);
+int launch_rc_shard_sims(hipStream_t s, const RecomJob& j, const int64_t* soff, double* sims,
                          unsigned long long* soft_count);
-int launch_rc_shard_chain(hipStream_t s, Pts X, const double* x_mean, int d, const int64_t* crow, const int32_t* crows,
-                          int K, int64_t nq, const int32_t* ucl, const double* u_mean, const int64_t* unk_ptr,
-                          const int32_t* unk_idx, const int64_t* soff, const double* sims, const double* carry_main,
-                          const double* carry_abs, const int64_t* carry_cnt, double* main_out, double* abs_out,
-                          int64_t* cnt_out, int n_top, double* pred, int32_t* pidx, int32_t* out);
+int launch_rc_shard_chain(hipStream_t s, const RecomJob& j, const int64_t* soff, const double* sims,
+                          const RecomCarry& in, const RecomCarry& out, const RecomOut& o);
 int launch_rc_p_closest(hipStream_t s, const double* X, const double* xa, int d, const double* U, int64_t nq,
                         const int64_t* cand_ptr, const int32_t* cand_idx, int P, double* sim, double* key,
                         int32_t* pos, int32_t* out_idx, double* out_sim, int32_t* out_cnt, int32_t* replay,

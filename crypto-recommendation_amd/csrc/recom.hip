@@ -24,7 +24,15 @@
 
 namespace lshkm {
 
-constexpr int RC_WAVES = 4;
+constexpr int RC_WAVES = RC_CLUSTER_WAVES_PER_BLOCK;
+
+// One launch of a kernel templated on the rows' element type: f(T{}) with T =
+// double or float, rows<T>(p) the typed pointer of a Pts.
+template <typename F> void for_rows(Pts X, F f) {
+    if (X.f64) f(double{});
+    else f(float{});
+}
+template <typename T> const T* rows(Pts p) { return static_cast<const T*>(p.p); }
 constexpr int RC_MAXV = 8;       // candidates per lane held in registers (n <= 512 per user)
 
 // CustVector::cosineSimilarity (cust_vector.hpp:158-174), this = neighbour x,
@@ -579,53 +587,41 @@ __global__ __launch_bounds__(64 * RC_WAVES) void rc_shard_chain_kernel(
     }
 }
 
-int launch_rc_cluster_top_n(hipStream_t s, Pts X, const double* x_mean, int d, const int64_t* crow,
-                            const int32_t* crows, int K, Pts U, const double* u_mean, int64_t nq, const int32_t* ucl,
-                            const int64_t* unk_ptr, const int32_t* unk_idx, int n_top, double* scratch,
-                            int64_t scratch_row, int nwaves, double* pred, int32_t* pidx, int32_t* out,
-                            unsigned long long* soft_count) {
-    if (nq <= 0) return 0;
-    const unsigned grid = (unsigned)((nwaves + RC_WAVES - 1) / RC_WAVES);
-    if (X.f64)
-        hipLaunchKernelGGL(rc_cluster_top_n_kernel<double>, dim3(grid), dim3(64 * RC_WAVES), 0, s, X.d(), x_mean, d,
-                           crow, crows, K, U.d(), u_mean, nq, ucl, unk_ptr, unk_idx, n_top, scratch, scratch_row, pred,
-                           pidx, out, soft_count);
-    else
-        hipLaunchKernelGGL(rc_cluster_top_n_kernel<float>, dim3(grid), dim3(64 * RC_WAVES), 0, s, X.f(), x_mean, d,
-                           crow, crows, K, U.f(), u_mean, nq, ucl, unk_ptr, unk_idx, n_top, scratch, scratch_row, pred,
-                           pidx, out, soft_count);
+int launch_rc_cluster_top_n(hipStream_t s, const RecomJob& j, double* scratch, const RcWaveScratch& ws,
+                            const RecomOut& o, unsigned long long* soft_count) {
+    if (j.nq <= 0) return 0;
+    const unsigned grid = (unsigned)((ws.nwaves + RC_WAVES - 1) / RC_WAVES);
+    for_rows(j.X, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(rc_cluster_top_n_kernel<T>, dim3(grid), dim3(64 * RC_WAVES), 0, s, rows<T>(j.X), j.x_mean,
+                           j.d, j.crow, j.crows, j.K, rows<T>(j.U), j.u_mean, j.nq, j.ucl, j.unk_ptr, j.unk_idx,
+                           o.n_top, scratch, ws.row, o.pred, o.pidx, o.out, soft_count);
+    });
     return kstatus("rc_cluster_top_n_kernel");
 }
 
-int launch_rc_shard_sims(hipStream_t s, Pts X, int d, const int64_t* crow, const int32_t* crows, int K, Pts U,
-                        int64_t nq, const int32_t* ucl, const int64_t* unk_ptr, const int64_t* soff, double* sims,
-                        unsigned long long* soft_count) {
-    if (nq <= 0) return 0;
-    const dim3 grid(gsz(nq, RC_WAVES, 2048));
-    if (X.f64)
-        hipLaunchKernelGGL(rc_shard_sims_kernel<double>, grid, dim3(64 * RC_WAVES), 0, s, X.d(), d, crow, crows, K,
-                           U.d(), nq, ucl, unk_ptr, soff, sims, soft_count);
-    else
-        hipLaunchKernelGGL(rc_shard_sims_kernel<float>, grid, dim3(64 * RC_WAVES), 0, s, X.f(), d, crow, crows, K,
-                           U.f(), nq, ucl, unk_ptr, soff, sims, soft_count);
+int launch_rc_shard_sims(hipStream_t s, const RecomJob& j, const int64_t* soff, double* sims,
+                         unsigned long long* soft_count) {
+    if (j.nq <= 0) return 0;
+    const dim3 grid(gsz(j.nq, RC_WAVES, 2048));
+    for_rows(j.X, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(rc_shard_sims_kernel<T>, grid, dim3(64 * RC_WAVES), 0, s, rows<T>(j.X), j.d, j.crow,
+                           j.crows, j.K, rows<T>(j.U), j.nq, j.ucl, j.unk_ptr, soff, sims, soft_count);
+    });
     return kstatus("rc_shard_sims_kernel");
 }
 
-int launch_rc_shard_chain(hipStream_t s, Pts X, const double* x_mean, int d, const int64_t* crow, const int32_t* crows,
-                          int K, int64_t nq, const int32_t* ucl, const double* u_mean, const int64_t* unk_ptr,
-                          const int32_t* unk_idx, const int64_t* soff, const double* sims, const double* carry_main,
-                          const double* carry_abs, const int64_t* carry_cnt, double* main_out, double* abs_out,
-                          int64_t* cnt_out, int n_top, double* pred, int32_t* pidx, int32_t* out) {
-    if (nq <= 0) return 0;
-    const dim3 grid(gsz(nq, RC_WAVES, 2048));
-    if (X.f64)
-        hipLaunchKernelGGL(rc_shard_chain_kernel<double>, grid, dim3(64 * RC_WAVES), 0, s, X.d(), x_mean, d, crow,
-                           crows, K, nq, ucl, u_mean, unk_ptr, unk_idx, soff, sims, carry_main, carry_abs, carry_cnt,
-                           main_out, abs_out, cnt_out, n_top, pred, pidx, out);
-    else
-        hipLaunchKernelGGL(rc_shard_chain_kernel<float>, grid, dim3(64 * RC_WAVES), 0, s, X.f(), x_mean, d, crow,
-                           crows, K, nq, ucl, u_mean, unk_ptr, unk_idx, soff, sims, carry_main, carry_abs, carry_cnt,
-                           main_out, abs_out, cnt_out, n_top, pred, pidx, out);
+int launch_rc_shard_chain(hipStream_t s, const RecomJob& j, const int64_t* soff, const double* sims,
+                          const RecomCarry& in, const RecomCarry& out, const RecomOut& o) {
+    if (j.nq <= 0) return 0;
+    const dim3 grid(gsz(j.nq, RC_WAVES, 2048));
+    for_rows(j.X, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(rc_shard_chain_kernel<T>, grid, dim3(64 * RC_WAVES), 0, s, rows<T>(j.X), j.x_mean, j.d,
+                           j.crow, j.crows, j.K, j.nq, j.ucl, j.u_mean, j.unk_ptr, j.unk_idx, soff, sims, in.main,
+                           in.abs, in.cnt, out.main, out.abs, out.cnt, o.n_top, o.pred, o.pidx, o.out);
+    });
     return kstatus("rc_shard_chain_kernel");
 }
 
@@ -640,7 +636,6 @@ int launch_rc_shard_chain(hipStream_t s, Pts X, const double* x_mean, int d, con
 //     :290-296), 64 values in flight, continued from / into the rank carry;
 //   rc_top_kernel: one thread per user, the division, the quicksort and the
 //     first N (:299-302, :341-343).
-constexpr int CT_STAGE = 64;      // member rows staged per wave
 
 // The certified similarity of the lane's staged row (8-B units, in dim order)
 // against user row u8 (LDS when the wave's members share one user, else the
@@ -732,7 +727,6 @@ __global__ __launch_bounds__(256) void rc_member_map_kernel(int64_t nq, const in
 // on those (45 % of its cycles waiting, profiles/round5_sq_c5_terms_v1.txt).
 // Users past the first CT_UMAX of a group, or with more than 64 unknown
 // indexes, take direct loads (correct, not pipelined).
-constexpr int CT_UMAX = 4;        // users per item staged ahead
 struct RcItem {
     int64_t mem0;      // crows index of the item's first member
     int32_t cnt;       // members in the item (1..64)
@@ -1351,120 +1345,107 @@ __global__ __launch_bounds__(64) void rc_top_kernel(int64_t nq, const int64_t* _
     for (int i = 0; i < n_top; i++) out[q * n_top + i] = i < m ? pidx[o + i] : 0;
 }
 
-int rc_terms_stride8(int d, int elem) { return (int)(((int64_t)d * elem + 7) / 8) + 1; }
-
-int launch_rc_terms(hipStream_t s, Pts X, const double* x_mean, int d, const int64_t* crow, const int32_t* crows,
-                    int K, Pts U, int64_t nq, const int32_t* ucl, const int64_t* soff, int64_t total,
-                    const int64_t* unk_ptr, const int32_t* unk_idx, const int64_t* toff, double* sims, double* terms,
-                    int32_t* mem_q, int32_t* mem_r, int64_t* fix_list, unsigned long long* fix_count,
-                    unsigned long long* soft_count, double* unorm, const RcGroups* groups, int64_t* fix_region,
-                    int64_t* fix_aux) {
-    if (nq <= 0 || total <= 0) return 0;
-    const int elem = X.f64 ? 8 : 4;
-    const int stride8 = rc_terms_stride8(d, elem);
-    const size_t lds = (size_t)(CT_STAGE + 1) * stride8 * 8;
-    const size_t lds_cl = (size_t)(CT_STAGE + CT_UMAX + 1) * stride8 * 8;   // rows | the users' rows | a spare
+int launch_rc_terms(hipStream_t s, const RecomJob& j, const RcTermsOut& t, char* map, const RcGroups& g,
+                    unsigned long long* soft_count) {
+    if (j.nq <= 0 || t.total <= 0) return 0;
     // every check before the first launch: a refused call enqueues nothing
-    if (((int64_t)d * elem) % 8 != 0 || 2 * lds > 160 * 1024 || lds_cl > 160 * 1024) {
+    if (recom_route(j.d, j.X.f64, 0) != RecomRoute::terms) {
         set_error("launch_rc_terms: rows must be a multiple of 8 B and stage in LDS");
         return LSHKM_ERR_ARG;
     }
-    if (!groups || groups->nitems <= 0 || groups->nusers <= 0 || !groups->items || !groups->users ||
-        ((uintptr_t)groups->items & 15) != 0 || ((uintptr_t)groups->users & 15) != 0 || !fix_region || !fix_aux) {
+    if (g.nitems <= 0 || g.nusers <= 0 || !g.items || !g.users || ((uintptr_t)g.items & 15) != 0 ||
+        ((uintptr_t)g.users & 15) != 0 || !map) {
         set_error("launch_rc_terms: empty cluster-major work list (or no 16-B aligned item records) for a nonzero member total");
         return LSHKM_ERR_ARG;
     }
-    hipLaunchKernelGGL(rc_member_map_kernel, dim3((unsigned)std::min<int64_t>(nq, 4096)), dim3(256), 0, s, nq, soff, ucl,
-                       crow, crows, mem_q, mem_r);
-    if (X.f64)
-        hipLaunchKernelGGL(rc_user_norm_kernel<double>, dim3(gsz(nq, 256, 1024)), dim3(256), 0, s, U.d(), nq, d, unorm);
-    else
-        hipLaunchKernelGGL(rc_user_norm_kernel<float>, dim3(gsz(nq, 256, 1024)), dim3(256), 0, s, U.f(), nq, d, unorm);
+    const int d = j.d, stride8 = rc_terms_stride8(d, j.X.f64 ? 8 : 4);
+    const size_t lds_cl = rc_terms_lds_cl(stride8);
+    const RcMapLayout ml = rc_map_layout(t.total, j.nq);
+    int32_t *mem_q = reinterpret_cast<int32_t*>(map + ml.mq), *mem_r = reinterpret_cast<int32_t*>(map + ml.mr);
+    int64_t* fix_list = reinterpret_cast<int64_t*>(map + ml.fix_list);
+    unsigned long long* fix_count = reinterpret_cast<unsigned long long*>(map + ml.fix_count);
+    double* unorm = reinterpret_cast<double*>(map + ml.unorm);
+    int64_t* fix_region = reinterpret_cast<int64_t*>(map + ml.fix_region);
+    int64_t *fcap = reinterpret_cast<int64_t*>(map + ml.fix_aux), *fcnt = fcap + RC_TERMS_GMAX;
+    hipLaunchKernelGGL(rc_member_map_kernel, dim3((unsigned)std::min<int64_t>(j.nq, 4096)), dim3(256), 0, s, j.nq,
+                       t.soff, j.ucl, j.crow, j.crows, mem_q, mem_r);
+    for_rows(j.X, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(rc_user_norm_kernel<T>, dim3(gsz(j.nq, 256, 1024)), dim3(256), 0, s, rows<T>(j.U), j.nq, d,
+                           unorm);
+    });
     // persistent: the resident waves (LDS-limited) times 2, each walking its
     // items as a pipeline (a grid of 65,536 one-item blocks would pay the
     // pipeline's fill per block)
     int ncu = 0;
     if (device_cu_count(&ncu)) return -2;
-    const int64_t per_cu = std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)lds_cl);
+    const int64_t per_cu = std::max<int64_t>(1, (int64_t)RC_LDS_BYTES / (int64_t)lds_cl);
     const int64_t resident = ncu * per_cu;
     const dim3 cgrid((unsigned)std::min<int64_t>(
-        {groups->nitems, (int64_t)RC_TERMS_GMAX, test_switch("LSHKM_TERMS_GRID", "r4") ? 4 * resident : 2 * resident}));
-    RcItem* items = reinterpret_cast<RcItem*>(groups->items);
-    RcUser* users = reinterpret_cast<RcUser*>(groups->users);
-    hipLaunchKernelGGL(rc_item_meta_kernel, dim3(gsz(groups->nitems, 256, 4096)), dim3(256), 0, s, groups->ioff,
-                       groups->ngroups, groups->nitems, groups->gcl, groups->gptr, crow, items);
-    if (X.f64)
-        hipLaunchKernelGGL(rc_user_meta_kernel<double>, dim3(gsz(groups->nusers, 256, 1024)), dim3(256), 0, s, U.d(), d,
-                           groups->gusr, groups->nusers, soff, toff, unk_ptr, unorm, users);
-    else
-        hipLaunchKernelGGL(rc_user_meta_kernel<float>, dim3(gsz(groups->nusers, 256, 1024)), dim3(256), 0, s, U.f(), d,
-                           groups->gusr, groups->nusers, soff, toff, unk_ptr, unorm, users);
+        {g.nitems, (int64_t)RC_TERMS_GMAX, test_switch("LSHKM_TERMS_GRID", "r4") ? 4 * resident : 2 * resident}));
+    RcItem* items = reinterpret_cast<RcItem*>(g.items);
+    RcUser* users = reinterpret_cast<RcUser*>(g.users);
+    hipLaunchKernelGGL(rc_item_meta_kernel, dim3(gsz(g.nitems, 256, 4096)), dim3(256), 0, s, g.ioff, g.ngroups,
+                       g.nitems, g.gcl, g.gptr, j.crow, items);
+    for_rows(j.X, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(rc_user_meta_kernel<T>, dim3(gsz(g.nusers, 256, 1024)), dim3(256), 0, s, rows<T>(j.U), d,
+                           g.gusr, g.nusers, t.soff, t.toff, j.unk_ptr, unorm, users);
+    });
     const int G = (int)cgrid.x;
-    int64_t* fcap = fix_aux;
-    int64_t* fcnt = fix_aux + RC_TERMS_GMAX;
-    hipLaunchKernelGGL(rc_block_cap_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, items, groups->nitems, G,
-                       fcap);
-    if (X.f64)
-        hipLaunchKernelGGL(rc_terms_cl_kernel<double>, cgrid, dim3(64), lds_cl, s, X.d(), x_mean, d, U.d(), items,
-                           groups->nitems, users, crows, unk_idx, sims, terms, stride8, fix_region, fcap, fcnt);
-    else
-        hipLaunchKernelGGL(rc_terms_cl_kernel<float>, cgrid, dim3(64), lds_cl, s, X.f(), x_mean, d, U.f(), items,
-                           groups->nitems, users, crows, unk_idx, sims, terms, stride8, fix_region, fcap, fcnt);
+    hipLaunchKernelGGL(rc_block_cap_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, items, g.nitems, G, fcap);
+    for_rows(j.X, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(rc_terms_cl_kernel<T>, cgrid, dim3(64), lds_cl, s, rows<T>(j.X), j.x_mean, d, rows<T>(j.U),
+                           items, g.nitems, users, j.crows, j.unk_idx, t.sims, t.terms, stride8, fix_region, fcap, fcnt);
+    });
     hipLaunchKernelGGL(rc_fix_gather_kernel, dim3((unsigned)G), dim3(64), 0, s, fcap, fcnt, G, fix_region, fix_list,
                        fix_count);
     // the list length is on the device: a grid for up to ~1/4 of the pairs, looping beyond
-    const dim3 fgrid(gsz(total / 4 + 1, CT_STAGE, 2048));
-    const size_t flds = 2 * lds;
-    if (X.f64)
-        hipLaunchKernelGGL(rc_terms_fix_kernel<double>, fgrid, dim3(64), flds, s, X.d(), x_mean, d, U.d(), mem_q, mem_r,
-                           soff, unk_ptr, unk_idx, toff, sims, terms, fix_list, fix_count, stride8, soft_count, unorm);
-    else
-        hipLaunchKernelGGL(rc_terms_fix_kernel<float>, fgrid, dim3(64), flds, s, X.f(), x_mean, d, U.f(), mem_q, mem_r,
-                           soff, unk_ptr, unk_idx, toff, sims, terms, fix_list, fix_count, stride8, soft_count, unorm);
+    const dim3 fgrid(gsz(t.total / 4 + 1, CT_STAGE, 2048));
+    for_rows(j.X, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(rc_terms_fix_kernel<T>, fgrid, dim3(64), rc_terms_lds_fix(stride8), s, rows<T>(j.X),
+                           j.x_mean, d, rows<T>(j.U), mem_q, mem_r, t.soff, j.unk_ptr, j.unk_idx, t.toff, t.sims,
+                           t.terms, fix_list, fix_count, stride8, soft_count, unorm);
+    });
     return kstatus("rc_terms_cl_kernel");
 }
 
-int launch_rc_chain_terms(hipStream_t s, int64_t nq, const int64_t* soff, const int64_t* unk_ptr, const int64_t* toff,
-                          const double* sims, const double* terms, const double* carry_main, const double* carry_abs,
-                          const int64_t* carry_cnt, const double* u_mean, double* main_out, double* abs_out,
-                          int64_t* cnt_out, double* pred, int64_t long_min) {
-    if (nq <= 0) return 0;
-    hipLaunchKernelGGL(rc_chain_user_kernel, dim3((unsigned)std::min<int64_t>(nq, 65536)), dim3(64), 0, s, nq, soff,
-                       unk_ptr, toff, sims, terms, carry_main, carry_abs, carry_cnt, u_mean, main_out, abs_out, cnt_out,
-                       pred, long_min);
+int launch_rc_chain_terms(hipStream_t s, const RecomJob& j, const RcTermsOut& t, const RecomCarry& in,
+                          const RecomCarry& out, double* pred, int64_t long_min) {
+    if (j.nq <= 0) return 0;
+    hipLaunchKernelGGL(rc_chain_user_kernel, dim3((unsigned)std::min<int64_t>(j.nq, 65536)), dim3(64), 0, s, j.nq,
+                       t.soff, j.unk_ptr, t.toff, t.sims, t.terms, in.main, in.abs, in.cnt, j.u_mean, out.main, out.abs,
+                       out.cnt, pred, long_min);
     return kstatus("rc_chain_user_kernel");
 }
 
 // The users of huge clusters (lng: one batch of them), by segments: their chain
 // would be one wave's ~n dependent adds (4.9 ms for the 206,926 members of the
 // first C5 iteration's largest cluster).
-int launch_rc_long(hipStream_t s, const double* sims, const double* terms, const double* carry_main,
-                   const double* carry_abs, const int64_t* carry_cnt, const double* u_mean, double* main_out,
-                   double* abs_out, int64_t* cnt_out, double* pred, const RcLong& L) {
-    const RcLong* lng = &L;
-    {
-        int rc;
-        const int D = lng->D;
-        hipLaunchKernelGGL(rc_long_pack_kernel, dim3(gsz(lng->rows * D / lng->nlong, 256, 2048), (unsigned)lng->nlong),
-                           dim3(256), 0, s, lng->tab, D, sims, terms, lng->V);
-        if (carry_main)
-            hipLaunchKernelGGL(rc_long_carry_kernel, dim3(gsz(lng->nlong * D, 256, 65535)), dim3(256), 0, s, lng->tab,
-                               lng->nlong, D, carry_main, carry_abs, lng->carry);
-        if ((rc = launch_seg_iota(s, lng->iota, lng->rows)) ||
-            (rc = launch_seg_columns(s, lng->V, lng->rows, (int)lng->nlong, D, lng->iota, lng->crow,
-                                     carry_main ? lng->carry : nullptr, lng->sums, lng->ws)))
-            return rc;
-        hipLaunchKernelGGL(rc_long_finish_kernel, dim3((unsigned)lng->nlong), dim3(64), 0, s, lng->tab, D, lng->sums,
-                           carry_cnt, u_mean, main_out, abs_out, cnt_out, pred);
-    }
+int launch_rc_long(hipStream_t s, const RcTermsOut& t, const RecomCarry& in, const double* u_mean,
+                   const RecomCarry& out, double* pred, const RcLong& lng) {
+    int rc;
+    const int D = lng.D;
+    hipLaunchKernelGGL(rc_long_pack_kernel, dim3(gsz(lng.rows * D / lng.nlong, 256, 2048), (unsigned)lng.nlong),
+                       dim3(256), 0, s, lng.tab, D, t.sims, t.terms, lng.V);
+    if (in.main)
+        hipLaunchKernelGGL(rc_long_carry_kernel, dim3(gsz(lng.nlong * D, 256, 65535)), dim3(256), 0, s, lng.tab,
+                           lng.nlong, D, in.main, in.abs, lng.carry);
+    if ((rc = launch_seg_iota(s, lng.iota, lng.rows)) ||
+        (rc = launch_seg_columns(s, lng.V, lng.rows, (int)lng.nlong, D, lng.iota, lng.crow,
+                                 in.main ? lng.carry : nullptr, lng.sums, lng.ws)))
+        return rc;
+    hipLaunchKernelGGL(rc_long_finish_kernel, dim3((unsigned)lng.nlong), dim3(64), 0, s, lng.tab, D, lng.sums, in.cnt,
+                       u_mean, out.main, out.abs, out.cnt, pred);
     return kstatus("rc_long");
 }
 
-int launch_rc_top(hipStream_t s, int64_t nq, const int64_t* soff, const int64_t* carry_cnt, const int64_t* unk_ptr,
-                  const int32_t* unk_idx, double* pred, int32_t* pidx, int n_top, int32_t* out) {
-    if (nq <= 0) return 0;
-    hipLaunchKernelGGL(rc_top_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, s, nq, soff, carry_cnt, unk_ptr,
-                       unk_idx, pred, pidx, n_top, out);
+int launch_rc_top(hipStream_t s, const RecomJob& j, const int64_t* soff, const int64_t* carry_cnt, const RecomOut& o) {
+    if (j.nq <= 0) return 0;
+    hipLaunchKernelGGL(rc_top_kernel, dim3((unsigned)((j.nq + 63) / 64)), dim3(64), 0, s, j.nq, soff, carry_cnt,
+                       j.unk_ptr, j.unk_idx, o.pred, o.pidx, o.n_top, o.out);
     return kstatus("rc_top_kernel");
 }
 

@@ -137,6 +137,7 @@ def lib():
                                           i64, i64, C.POINTER(i64), C.POINTER(i64)]),
             "lshkm_cluster_chain_terms": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32,
                                                 vp]),
+            "lshkm_cluster_terms_supported": (i32, [i32, i32]),
             "lshkm_cv_split10": (i32, [u64, i64, vp]),
             "lshkm_cv_draws": (i32, [vp, i64, i64, vp]),
             "lshkm_cv_hide": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
@@ -793,6 +794,12 @@ def cluster_chain(ctx, X, x_mean, crow, crows, ucl, u_mean, unk_ptr, unk_idx, so
                                       _t_ptr(cm), _t_ptr(ca), _t_ptr(cc), _t_ptr(om), _t_ptr(oa), _t_ptr(oc),
                                       0 if n_top is None else n_top, _t_ptr(out)))
     return outs if n_top is None else out
+
+
+def cluster_terms_supported(d, f64):
+    """Whether rows of d values (fp64 when f64, else fp32) take the terms form
+    (lshkm_cluster_terms_supported: the library's own route rule)."""
+    return bool(lib().lshkm_cluster_terms_supported(int(d), int(bool(f64))))
 
 
 def cluster_terms(ctx, X, x_mean, crow, crows, U, ucl, unk_ptr, unk_idx):

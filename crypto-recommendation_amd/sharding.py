@@ -247,11 +247,10 @@ def recommend_terms(lk, ctx, X, x_mean, assign, K, U, u_mean, ucl, unk_ptr, unk_
     and prediction terms, all ranks at once. Returns the state recommend_chain
     continues from."""
     crow, crows = csr if csr is not None else lk.clusters(ctx, assign, K)
-    # the terms form stages rows of <= 1016 B in 8-B units (lshkm_cluster_terms):
-    # other rows (fp32 of odd d, fp64 of d >= 128) take the sims form, the same
-    # rank-to-rank chain over lshkm_cluster_sims + lshkm_cluster_chain
-    rb = X.shape[1] * X.element_size()
-    if rb % 8 == 0 and rb <= 1016:
+    # rows the terms form does not stage (lshkm_cluster_terms_supported: fp32 of
+    # odd d, fp64 of d >= 128) take the sims form, the same rank-to-rank chain
+    # over lshkm_cluster_sims + lshkm_cluster_chain
+    if lk.cluster_terms_supported(X.shape[1], X.element_size() == 8):
         soff, toff, sims, terms = lk.cluster_terms(ctx, X, x_mean, crow, crows, U, ucl, unk_ptr, unk_idx)
         return (lk.cluster_chain_terms, (ctx, u_mean, unk_ptr, unk_idx, soff, toff, sims, terms), ucl, unk_idx)
     soff, sims = lk.cluster_sims(ctx, X, crow, crows, U, ucl, unk_ptr)

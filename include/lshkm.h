@@ -585,6 +585,11 @@ int lshkm_cluster_chain_terms(lshkm_ctx ctx, int64_t nq, const double* u_mean_de
                               const double* sims_dev, const double* terms_dev, const double* carry_main_dev,
                               const double* carry_abs_dev, const int64_t* carry_cnt_dev, double* main_out_dev,
                               double* abs_out_dev, int64_t* cnt_out_dev, int n_top, int32_t* out_dev);
+/* 1 when rows of d values (fp64 when f64 != 0, else fp32) take the terms form
+ * (lshkm_cluster_terms accepts them), else 0 (lshkm_cluster_sims +
+ * lshkm_cluster_chain): the rule lshkm_cluster_top_n itself routes by. Needs
+ * no context. */
+int lshkm_cluster_terms_supported(int d, int f64);
 
 /* ------------------------------------------------ recommender validation
  * lsh_rec_10_fold_validation_A (main.cpp:393-437, called at :180-183) and the

@@ -359,6 +359,91 @@ def test_huge_cluster_chains_by_segments(ctx, kind):
     assert np.array_equal(got, want), np.nonzero((got != want).any(1))[0][:10]
 
 
+# (kind, d): rows on both sides of every route rule -- 8 B and 1016 B rows (the
+# terms form's smallest and largest), 1024 B and odd rows (one wave per user)
+ROUTE_ROWS = [("f32", 2), ("f32", 254), ("f32", 256), ("f32", 37), ("f64", 127), ("f64", 128)]
+
+
+def route_case(kind, d, N, exact, seed):
+    """One input of test_routes_alternate_on_one_context: K = 6 clusters, cluster
+    5 empty, `exact` = {cluster: its member rows}, the other rows spread over
+    the clusters left; 40 users, user 0 an all-zero row, user 1 of the empty
+    cluster, users 2 .. 2 + 2 * len(exact) of the exact-size clusters."""
+    rng = np.random.default_rng(seed)
+    K, nq = 6, 40
+    X = rng.standard_normal((N, d))
+    X = X.astype(np.float32) if kind == "f32" else X * np.exp(rng.uniform(-1, 1, size=(N, 1)))
+    xm = rng.standard_normal(N) * 0.3
+    free = [c for c in range(K - 1) if c not in exact]
+    assign = rng.choice(free, size=N).astype(np.int32)
+    for c in exact:                                            # no other row of these clusters
+        assert not (assign == c).any()
+    for c, rows in exact.items():
+        assign[rows] = c
+    users = rng.choice(N, nq, replace=False)
+    U = X[users].copy()
+    U[0] = 0.0
+    um = rng.standard_normal(nq) * 0.2
+    ucl = assign[users].copy()
+    ucl[1] = K - 1
+    pinned = sorted(exact) * 2
+    ucl[2:2 + len(pinned)] = pinned
+    up, ui = unknown_sets(rng, nq, d)
+    assert (np.diff(up) == 0).any()                            # a user without unknown indexes
+    crow, crows = oracle.clusters_csr(assign, K)
+    for c, rows in exact.items():
+        assert crow[c + 1] - crow[c] == len(rows)
+    assert crow[K] - crow[K - 1] == 0
+    want = oracle.cluster_top_n(X, xm, crow, crows, U, um, ucl, up, ui, 3)
+    assert 1 <= (want[:, 0] == -1).sum() <= 3                  # the oracle skips user 1 alone (at most 3 of 40)
+    return dict(kind=kind, d=d, N=N, K=K, X=X, xm=xm, assign=assign, crow=crow, crows=crows, U=U, um=um, ucl=ucl,
+                up=up, ui=ui, want=want)
+
+
+def test_routes_alternate_on_one_context(ctx):
+    # the terms form and the one-wave-per-user form share the context's call
+    # workspaces (the terms form's similarities and the wave form's scratch are
+    # one buffer): every row shape in turn, then in reverse, on one context. Each
+    # visit: lshkm_cluster_top_n, and the two-shard carry chain (rows cut at
+    # N // 2) through the terms form where lshkm_cluster_terms_supported says so,
+    # else through lshkm_cluster_sims + lshkm_cluster_chain -- both bit for bit
+    # the oracle. Clusters of 64 and 65 members sit on both sides of the
+    # 64-member item chunk; the last shape's clusters of 16,384 (RC_LONG_MIN) and
+    # 16,383 members sit on both sides of the chains by segments, the first whole
+    # on shard 0, the second whole on shard 1.
+    NT = 3
+    shapes = []
+    for i, (kind, d) in enumerate(ROUTE_ROWS):
+        rows = np.random.default_rng(100 + i).permutation(3_000)
+        shapes.append(route_case(kind, d, 3_000, {3: rows[:64], 4: rows[64:129]}, 200 + i))
+    shapes.append(route_case("f32", 8, 40_000, {0: np.arange(16_384), 1: np.arange(20_000, 20_000 + 16_383)}, 300))
+    for c in shapes + shapes[::-1]:
+        f64 = c["kind"] == "f64"
+        terms = lshkm.cluster_terms_supported(c["d"], f64)
+        assert terms == ((c["d"] * (8 if f64 else 4)) % 8 == 0 and c["d"] * (8 if f64 else 4) <= 1016)
+        tag = (c["kind"], c["d"], c["N"])
+        Ud, umd, ucd, upd, uid = (dev(ctx, c[k]) for k in ("U", "um", "ucl", "up", "ui"))
+        got = lshkm.cluster_top_n(ctx, dev(ctx, c["X"]), dev(ctx, c["xm"]), dev(ctx, c["crow"]), dev(ctx, c["crows"]),
+                                  Ud, umd, ucd, upd, uid, NT).cpu().numpy()
+        assert np.array_equal(got, c["want"]), (tag, "single", np.nonzero((got != c["want"]).any(1))[0][:10])
+        carry, bounds = None, [0, c["N"] // 2, c["N"]]
+        for s in range(2):
+            lo, hi = bounds[s], bounds[s + 1]
+            Xs, xms = dev(ctx, c["X"][lo:hi]), dev(ctx, c["xm"][lo:hi])
+            lcrow, lrows = oracle.clusters_csr(c["assign"][lo:hi], c["K"])
+            lcrow, lrows = dev(ctx, lcrow), dev(ctx, lrows)
+            n_top = None if s == 0 else NT
+            if terms:
+                soff, toff, sims, tm = lshkm.cluster_terms(ctx, Xs, xms, lcrow, lrows, Ud, ucd, upd, uid)
+                carry = lshkm.cluster_chain_terms(ctx, umd, upd, uid, soff, toff, sims, tm, carry=carry, n_top=n_top)
+            else:
+                soff, sims = lshkm.cluster_sims(ctx, Xs, lcrow, lrows, Ud, ucd, upd)
+                carry = lshkm.cluster_chain(ctx, Xs, xms, lcrow, lrows, ucd, umd, upd, uid, soff, sims, carry=carry,
+                                            n_top=n_top)
+        got = carry.cpu().numpy()
+        assert np.array_equal(got, c["want"]), (tag, "chain", np.nonzero((got != c["want"]).any(1))[0][:10])
+
+
 @pytest.mark.parametrize("bad_cl", [-1, 12, 17])
 def test_cluster_ids_outside_k_are_refused(ctx, bad_cl):
     # the reference indexes clusters[user.getCluster()] unchecked (main.cpp:261,

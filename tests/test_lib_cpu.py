@@ -119,6 +119,20 @@ def test_fused_layout(tmp_path):
     assert "bad=0" in out.stdout
 
 
+def test_recom_layout(tmp_path):
+    # csrc/recom_layout.h on the host: the clustering recommender's three
+    # workspaces (regions in order, disjoint, aligned, inside the reservation;
+    # item and user records 16-B aligned), the terms / waves rule with its edges
+    # (1016 / 1024 B rows, 2^28 / 2^28 + 1 terms) and the LDS sizes it implies,
+    # the long-user batches, the wave form's scratch and the work list
+    exe = tmp_path / "recom_layout_check"
+    subprocess.run(["g++", "-O1", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tests", "recom_layout_check.cpp")],
+                   check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "bad=0" in out.stdout
+
+
 def test_kmseg_matches_chain(tmp_path):
     # the binade-segment evaluation of the fp64 chain (csrc/kmseg.h) vs the plain chain
     exe = tmp_path / "kmseg_check"
