@@ -285,6 +285,24 @@ int lshkm_rand_selection(uint64_t seed, int64_t N, int K, int32_t* rows) {
     return 0;
 }
 
+// Every engine draw of k_means_pp up front (initialization.hpp:75-79,132-133):
+// they do not depend on the data. uniform_real<double>(0, total) is
+// canon * (total - 0) + 0 with canon = uniform_real<double>(0, 1).
+int lshkm_kpp_draws(uint64_t seed, int64_t N_total, int K, int64_t* first_row, double* canon) {
+    LSHKM_CHECK(first_row && canon && N_total >= 1 && N_total <= INT32_MAX && K >= 1, LSHKM_ERR_ARG,
+                "bad arguments (need 1 <= N < 2^31, K >= 1)");
+    std::default_random_engine g;
+    g.seed((unsigned long)seed);
+    std::uniform_int_distribution<int> uni(0, (int)(N_total - 1));
+    *first_row = uni(g);
+    canon[0] = 0.0;
+    for (int i = 1; i < K; i++) {
+        std::uniform_real_distribution<double> unit(0.0, 1.0);
+        canon[i] = unit(g);
+    }
+    return 0;
+}
+
 }  // extern "C"
 
 static int kmeans_pp_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, int K, int metric, uint64_t seed, int32_t* rows) {
@@ -292,19 +310,11 @@ static int kmeans_pp_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, int K, int met
                 "bad arguments (need N < 2^31, 1 <= d <= 4096, K >= 1)");
     LSHKM_CHECK(metric == LSHKM_METRIC_EUCLIDEAN || metric == LSHKM_METRIC_COSINE, LSHKM_ERR_ARG, "unknown metric");
     LSHKM_HIP(hipSetDevice(ctx->device));
-    // every engine draw of k_means_pp up front (initialization.hpp:75-79,127-128):
-    // they do not depend on the data. uniform_real<double>(0, total) is
-    // canon * (total - 0) + 0 with canon = uniform_real<double>(0, 1).
-    std::default_random_engine g;
-    g.seed((unsigned long)seed);
-    std::uniform_int_distribution<int> uni(0, (int)(N - 1));
     std::vector<int32_t> chosen(K, 0);
     std::vector<double> canon(K, 0.0);
-    chosen[0] = uni(g);
-    for (int i = 1; i < K; i++) {
-        std::uniform_real_distribution<double> unit(0.0, 1.0);
-        canon[i] = unit(g);
-    }
+    int64_t first = 0;
+    if (const int rc = lshkm_kpp_draws(seed, N, K, &first, canon.data())) return rc;
+    chosen[0] = (int32_t)first;
     Buf &ws = ctx->ws_call[0], &dch = ctx->ws_call[1], &dcanon = ctx->ws_call[2];
     int rc;
     if ((rc = ws.reserve(kmeans_pp_ws_bytes(N))) || (rc = dch.reserve(sizeof(int32_t) * K)) ||
@@ -332,6 +342,110 @@ int lshkm_kmeans_pp(lshkm_ctx ctx, const float* X, int64_t N, int d, int K, int 
 int lshkm_kmeans_pp_f64(lshkm_ctx ctx, const double* X, int64_t N, int d, int K, int metric, uint64_t seed,
                         int32_t* rows) {
     return kmeans_pp_impl(ctx, X, N, d, K, metric, seed, rows);
+}
+
+}  // extern "C"
+
+// k_means_pp over row shards (lshkm_kpp_shard_*): one step of one iteration on
+// this rank's n rows; an empty shard touches no memory. `out` is what the step
+// leaves for the host behind the workspace's max word (kernels.h).
+struct KppShardHost {
+    uint64_t max_bits;
+    double sum, s_out;
+    int64_t pick;
+};
+
+static int kpp_shard_ws_check(lshkm_ctx ctx, int64_t n, const void* ws, int64_t ws_bytes) {
+    LSHKM_CHECK(ctx && n >= 0 && n <= INT32_MAX, LSHKM_ERR_ARG, "bad arguments (need 0 <= n < 2^31)");
+    LSHKM_CHECK(n == 0 || (ws && ws_bytes >= 0 && (size_t)ws_bytes >= kmeans_pp_ws_bytes(n)), LSHKM_ERR_ARG,
+                "workspace smaller than lshkm_kpp_shard_ws_bytes");
+    LSHKM_HIP(hipSetDevice(ctx->device));
+    return 0;
+}
+
+static int kpp_shard_read(lshkm_ctx ctx, int64_t n, const void* ws, KppShardHost* out) {
+    LSHKM_HIP(hipMemcpyAsync(out, (const char*)ws + kpp_shard_out_offset(n), sizeof(*out), hipMemcpyDeviceToHost,
+                             ctx->stream));
+    LSHKM_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+static int kpp_shard_dist_impl(lshkm_ctx ctx, Pts X, int64_t n, int d, int metric, const void* c, int it, void* ws,
+                               int64_t ws_bytes, uint64_t* max_bits, double* sum) {
+    if (const int rc = kpp_shard_ws_check(ctx, n, ws, ws_bytes)) return rc;
+    LSHKM_CHECK(max_bits && sum && d >= 1 && d <= 4096 && it >= 1, LSHKM_ERR_ARG,
+                "bad arguments (need 1 <= d <= 4096, it >= 1)");
+    LSHKM_CHECK(metric == LSHKM_METRIC_EUCLIDEAN || metric == LSHKM_METRIC_COSINE, LSHKM_ERR_ARG, "unknown metric");
+    *max_bits = 0;
+    *sum = 0.0;
+    if (n == 0) return 0;
+    LSHKM_CHECK(X.p && c, LSHKM_ERR_ARG, "rows or centroid row is NULL");
+    KppShardHost o;
+    int rc;
+    if ((rc = launch_kpp_shard_dist(ctx->stream, X, n, d, metric, c, it, ws)) || (rc = kpp_shard_read(ctx, n, ws, &o))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    *max_bits = o.max_bits;
+    *sum = o.sum;
+    return 0;
+}
+
+extern "C" {
+
+int lshkm_kpp_shard_ws_bytes(int64_t n, int64_t* bytes) {
+    LSHKM_CHECK(bytes && n >= 0 && n <= INT32_MAX, LSHKM_ERR_ARG, "bad arguments (need 0 <= n < 2^31)");
+    *bytes = (int64_t)kmeans_pp_ws_bytes(n);
+    return 0;
+}
+
+int lshkm_kpp_shard_dist(lshkm_ctx ctx, const float* X, int64_t n, int d, int metric, const float* c, int it, void* ws,
+                         int64_t ws_bytes, uint64_t* max_bits, double* sum) {
+    return kpp_shard_dist_impl(ctx, X, n, d, metric, c, it, ws, ws_bytes, max_bits, sum);
+}
+
+int lshkm_kpp_shard_dist_f64(lshkm_ctx ctx, const double* X, int64_t n, int d, int metric, const double* c, int it,
+                             void* ws, int64_t ws_bytes, uint64_t* max_bits, double* sum) {
+    return kpp_shard_dist_impl(ctx, X, n, d, metric, c, it, ws, ws_bytes, max_bits, sum);
+}
+
+int lshkm_kpp_shard_units(lshkm_ctx ctx, int64_t n, uint64_t gmax_bits, double start, void* ws, int64_t ws_bytes) {
+    if (const int rc = kpp_shard_ws_check(ctx, n, ws, ws_bytes)) return rc;
+    if (n == 0) return 0;
+    return launch_kpp_shard_units(ctx->stream, n, gmax_bits, start, ws);
+}
+
+int lshkm_kpp_shard_chain(lshkm_ctx ctx, int64_t n, double s_in, void* ws, int64_t ws_bytes, double* s_out) {
+    if (const int rc = kpp_shard_ws_check(ctx, n, ws, ws_bytes)) return rc;
+    LSHKM_CHECK(s_out, LSHKM_ERR_ARG, "s_out is NULL");
+    *s_out = s_in;
+    if (n == 0) return 0;
+    KppShardHost o;
+    int rc;
+    if ((rc = launch_kpp_shard_chain(ctx->stream, n, s_in, ws, (unsigned long long*)ctx->stats.p)) ||
+        (rc = kpp_shard_read(ctx, n, ws, &o))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    *s_out = o.s_out;
+    return 0;
+}
+
+int lshkm_kpp_shard_pick(lshkm_ctx ctx, int64_t n, double rd, int owns_row0, void* ws, int64_t ws_bytes,
+                         int64_t* row) {
+    if (const int rc = kpp_shard_ws_check(ctx, n, ws, ws_bytes)) return rc;
+    LSHKM_CHECK(row, LSHKM_ERR_ARG, "row is NULL");
+    *row = -1;
+    if (n == 0) return 0;
+    KppShardHost o;
+    int rc;
+    if ((rc = launch_kpp_shard_pick(ctx->stream, n, rd, owns_row0, ws)) || (rc = kpp_shard_read(ctx, n, ws, &o))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    LSHKM_CHECK(o.pick >= -1 && o.pick < n, LSHKM_ERR_STATE, "pick outside the shard (rd above the running sum?)");
+    *row = o.pick;
+    return 0;
 }
 
 int lshkm_params_cube_cosine(uint64_t seed, int k, int d, double* R, uint32_t* state) {

@@ -37,6 +37,15 @@
 //                           fp64 adds row by row. Then the draw and the
 //                           reference's binary search, the prefix sums formed
 //                           only for the chunk the draw lands in.
+//
+// Over contiguous row shards (lshkm_kpp_shard_*) the same device code runs per
+// shard with the host between the steps: a later row needs from the earlier
+// ones only the global max and the exact running s, and the chain's value does
+// not depend on where the chunks are cut. kpp_fold_kernel leaves the shard's max
+// and sum m^2 for the exchange; kpp_starts_kernel takes the global max and the
+// approximate sum before the shard; kpp_chain_shard_kernel is the walk from the
+// previous shard's s (no draw); kpp_pick_shard_kernel is the search for the
+// draw the host forms from the last shard's s.
 #include <climits>
 #include <cstdlib>
 #include <cstring>
@@ -98,9 +107,11 @@ __device__ inline int kpp_binade(double s) {
 }
 
 // ------------------------------------------------------------- (1) + (2)
-// Distances of every row to the newest centroid (row chosen[it-1]), the
-// running minimum, and the max of the minima (positive doubles order as their
-// bit patterns; the reference's max starts at 0 with '>', so only m > 0 count).
+// Distances of every row to the newest centroid (row chosen[it-1] of X, or the
+// [d] row cext of the rows' type when it is given: a shard, whose newest
+// centroid usually lies on another rank), the running minimum, and the max of
+// the minima (positive doubles order as their bit patterns; the reference's max
+// starts at 0 with '>', so only m > 0 count).
 // A block owns 256 rows (one per thread) and streams them through LDS in
 // slices of KPP_DJ dims, loaded coalesced (consecutive lanes, consecutive
 // floats of a row); each thread then accumulates its row in dim order, exactly
@@ -149,7 +160,8 @@ __device__ inline void kpp_group_sum(double v, double* __restrict__ gsum, int64_
 // TX: fp32 or fp64 rows (VEC only for fp32).
 template <int METRIC, bool VEC, typename TX>
 __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_kernel(const TX* __restrict__ X, int64_t N, int d,
-                                                               const int32_t* __restrict__ chosen, int it,
+                                                               const int32_t* __restrict__ chosen,
+                                                               const TX* __restrict__ cext, int it,
                                                                double* __restrict__ mind,
                                                                unsigned long long* __restrict__ bmax,
                                                                double* __restrict__ gsum) {
@@ -162,7 +174,7 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_kernel(const TX* __restr
     // reads in the chain instead of a uniform global load per dim)
     extern __shared__ __attribute__((aligned(8))) char kpp_dyn[];
     TX* cs = reinterpret_cast<TX*>(kpp_dyn);            // [d] (dynamic)
-    const TX* __restrict__ c = X + (int64_t)chosen[it - 1] * d;
+    const TX* __restrict__ c = cext ? cext : X + (int64_t)chosen[it - 1] * d;
     for (int j = threadIdx.x; j < d; j += KPP_THREADS) cs[j] = c[j];
     __syncthreads();
     double cb = 0.0;                                    // cosine: sum c^2 (uniform)
@@ -277,7 +289,8 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_kernel(const TX* __restr
 // wave). The centroid row is an LDS broadcast. Same exact-order chain as above.
 constexpr int KR_S = 20;                                 // LDS row stride of the transpose (floats)
 __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_reg_kernel(const float* __restrict__ X, int64_t N, int d,
-                                                                   const int32_t* __restrict__ chosen, int it,
+                                                                   const int32_t* __restrict__ chosen,
+                                                                   const float* __restrict__ cext, int it,
                                                                    double* __restrict__ mind,
                                                                    unsigned long long* __restrict__ bmax,
                                                                    double* __restrict__ gsum) {
@@ -285,7 +298,7 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_reg_kernel(const float* 
     float* cs = reinterpret_cast<float*>(kpp_dyn2);     // [d]
     __shared__ double sqs[KPP_THREADS / 64][64 * 16];   // gp_sq_wave: 64 * 16 per wave
     __shared__ __attribute__((aligned(16))) float trs[KPP_THREADS / 64][64 * KR_S];
-    const float* __restrict__ c = X + (int64_t)chosen[it - 1] * d;
+    const float* __restrict__ c = cext ? cext : X + (int64_t)chosen[it - 1] * d;
     for (int j = threadIdx.x; j < d; j += KPP_THREADS) cs[j] = c[j];
     __syncthreads();
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -358,12 +371,9 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_reg_kernel(const float* 
 constexpr int KPP_SCAN_THREADS = 1024;
 static_assert(KPP_CHUNK == 2 * KPP_THREADS, "two row groups per chunk");
 
-__global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_scan_kernel(const unsigned long long* __restrict__ bmax, int nb,
-                                                                    const double* __restrict__ gsum, int64_t ngroups,
-                                                                    int64_t nch, unsigned long long* __restrict__ mx_bits,
-                                                                    double* __restrict__ chunk_start) {
-    __shared__ unsigned long long redm[KPP_SCAN_THREADS];
-    __shared__ double part[KPP_SCAN_THREADS];
+// The block's fold of the per-block maxima (every thread gets it).
+__device__ inline unsigned long long kpp_fold_max(const unsigned long long* __restrict__ bmax, int nb,
+                                                  unsigned long long* redm) {
     unsigned long long mb = 0;
     for (int i = threadIdx.x; i < nb; i += KPP_SCAN_THREADS) mb = bmax[i] > mb ? bmax[i] : mb;
     redm[threadIdx.x] = mb;
@@ -372,9 +382,13 @@ __global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_scan_kernel(const unsign
         if ((int)threadIdx.x < off && redm[threadIdx.x + off] > redm[threadIdx.x]) redm[threadIdx.x] = redm[threadIdx.x + off];
         __syncthreads();
     }
-    const unsigned long long mxb = redm[0];
-    if (threadIdx.x == 0) *mx_bits = mxb;
-    const double mx = __longlong_as_double((long long)mxb);
+    return redm[0];
+}
+
+// Approximate chunk starts: start0 (the approximate sum before these rows; 0
+// on one device) + the exclusive scan of the chunk sums sum m^2 / mx^2.
+__device__ inline void kpp_chunk_starts(const double* __restrict__ gsum, int64_t ngroups, int64_t nch, double mx,
+                                        double start0, double* __restrict__ chunk_start, double* part) {
     const double inv = 1.0 / (mx * mx);
     auto csum = [&](int64_t c) { return (gsum[2 * c] + (2 * c + 1 < ngroups ? gsum[2 * c + 1] : 0.0)) * inv; };
     const int64_t per = (nch + KPP_SCAN_THREADS - 1) / KPP_SCAN_THREADS;
@@ -389,11 +403,65 @@ __global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_scan_kernel(const unsign
         part[threadIdx.x] += o;
         __syncthreads();
     }
-    double run = threadIdx.x ? part[threadIdx.x - 1] : 0.0;
+    double run = start0 + (threadIdx.x ? part[threadIdx.x - 1] : 0.0);
     for (int64_t c = lo; c < hi; c++) {
         chunk_start[c] = run;
         run += csum(c);
     }
+}
+
+__global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_scan_kernel(const unsigned long long* __restrict__ bmax, int nb,
+                                                                    const double* __restrict__ gsum, int64_t ngroups,
+                                                                    int64_t nch, unsigned long long* __restrict__ mx_bits,
+                                                                    double* __restrict__ chunk_start) {
+    __shared__ unsigned long long redm[KPP_SCAN_THREADS];
+    __shared__ double part[KPP_SCAN_THREADS];
+    const unsigned long long mxb = kpp_fold_max(bmax, nb, redm);
+    if (threadIdx.x == 0) *mx_bits = mxb;
+    kpp_chunk_starts(gsum, ngroups, nch, __longlong_as_double((long long)mxb), 0.0, chunk_start, part);
+}
+
+// What a shard's steps leave for the host (lshkm_kpp_shard_*), after the max
+// word of the workspace.
+struct KppShardOut {
+    unsigned long long max_bits;   // dist: the shard's max of minima (0 if none)
+    double sum;                    // dist: its approximate sum m^2
+    double s_out;                  // chain: the running sum after its rows
+    long long pick;                // pick: a local row, or -1
+};
+
+// A shard's half of kpp_scan_kernel before the exchange: its own max and its
+// sum m^2 (any order: guesses only), for the host.
+__global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_fold_kernel(const unsigned long long* __restrict__ bmax, int nb,
+                                                                    const double* __restrict__ gsum, int64_t ngroups,
+                                                                    KppShardOut* __restrict__ out) {
+    __shared__ unsigned long long redm[KPP_SCAN_THREADS];
+    __shared__ double part[KPP_SCAN_THREADS];
+    const unsigned long long mxb = kpp_fold_max(bmax, nb, redm);
+    double v = 0.0;
+    for (int64_t g = threadIdx.x; g < ngroups; g += KPP_SCAN_THREADS) v += gsum[g];
+    part[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = KPP_SCAN_THREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out->max_bits = mxb;
+        out->sum = part[0];
+    }
+}
+
+// ... and after it: the GLOBAL max (mx_bits, for the exact q_m) and the chunk
+// starts from the approximate sum of the rows before this shard.
+__global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_starts_kernel(const double* __restrict__ gsum, int64_t ngroups,
+                                                                      int64_t nch, unsigned long long gmax_bits,
+                                                                      double start0,
+                                                                      unsigned long long* __restrict__ mx_bits,
+                                                                      double* __restrict__ chunk_start) {
+    __shared__ double part[KPP_SCAN_THREADS];
+    if (threadIdx.x == 0) *mx_bits = gmax_bits;
+    kpp_chunk_starts(gsum, ngroups, nch, __longlong_as_double((long long)gmax_bits), start0, chunk_start, part);
 }
 
 // RN_u(q) in units of u = 2^(e-52), or -1 if q cannot be resolved in binade e
@@ -510,12 +578,15 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_chunk_units_kernel(const doub
 // The exact walk (one wave). s is uniform across the wave. A step covers
 // 64 lanes x CPL consecutive chunks (lane-local prefix, then a wave scan of
 // the lane totals); R < 2^53 per chunk keeps every prefix below 2^62.
-__global__ __launch_bounds__(64) void kpp_chain_kernel(const double* __restrict__ qbuf, int64_t N,
-                                                       const KppChunk* __restrict__ meta, int64_t nch,
-                                                       const int64_t* __restrict__ pa, const int64_t* __restrict__ pb,
-                                                       double* chunk_s, int32_t* chunk_mode,
-                                                       double* cum, const double* __restrict__ canon, int it,
-                                                       int32_t* __restrict__ chosen, unsigned long long* __restrict__ stats) {
+// Starts from s (0 on one device and on the shard of global row 0, else the
+// running sum after the earlier shards' rows: a chunk's result depends on the
+// rows before it through s alone) and returns s after row N - 1; nseq counts
+// the stop chunks.
+__device__ __forceinline__ double kpp_walk(const double* __restrict__ qbuf, int64_t N,
+                                           const KppChunk* __restrict__ meta, int64_t nch,
+                                           const int64_t* __restrict__ pa, const int64_t* __restrict__ pb,
+                                           double* chunk_s, int32_t* chunk_mode, double* cum, double s,
+                                           unsigned long long& nseq) {
     constexpr int CPL = 8;                         // chunks per lane per step
     constexpr int STEP = 64 * CPL;
     constexpr int WIN = 2 * STEP;                  // chunk metadata staged in LDS (16 KB)
@@ -523,9 +594,7 @@ __global__ __launch_bounds__(64) void kpp_chain_kernel(const double* __restrict_
     __shared__ double qs[KPP_CHUNK];
     __shared__ int64_t pas[KPP_CHUNK], pbs[KPP_CHUNK];
     const int lane = threadIdx.x;
-    double s = 0.0;
     int64_t base = 0, win0 = -2 * WIN;
-    unsigned long long nseq = 0;
 #if defined(KPP_PROF)
     unsigned long long tp[5] = {0, 0, 0, 0, 0}, npass = 0;
     unsigned long long tq = __builtin_amdgcn_s_memtime();
@@ -729,123 +798,207 @@ __global__ __launch_bounds__(64) void kpp_chain_kernel(const double* __restrict_
         base = c + 1;
         nseq++;
     }
-    // ---- (4) the draw (:127-149): rd = uniform_real(0, total) = canon * (total -
-    // 0) + 0, then the reference's binary search = the first row whose prefix
-    // sum reaches rd (the sums never decrease, rd <= total; a NaN total from
-    // degenerate minima gives rd NaN and row 0). The prefix sums are never
-    // materialised: the chunk by a 64-ary search over the chunk ends, then its
-    // rows (the walk wrote a stop chunk's; an integer chunk's are formed here).
-    {
-        __threadfence();                           // this wave's chunk_s / cum stores, visible to its loads
-        const double total = s;
-        const double rd = __dadd_rn(__dmul_rn(canon[it], __dsub_rn(total, 0.0)), 0.0);
-        int64_t pick = 0;
-        if (rd > qbuf[0]) {                        // cum[0] = 0 + q_0 = q_0
-            auto chunk_end = [&](int64_t cc) -> double { return cc + 1 < nch ? chunk_s[cc + 1] : total; };
-            int64_t lo = 0, hi = nch;              // the first chunk whose end reaches rd lies in [lo, hi)
-            while (hi - lo > 64) {
-                const int64_t step = (hi - lo + 63) / 64;
-                const int64_t p = lo + (int64_t)(lane + 1) * step - 1;
-                const bool ge = p >= hi - 1 || chunk_end(p) >= rd;
-                const unsigned long long b = __ballot(ge);
-                const int f = __ffsll((long long)b) - 1;          // lane 63 always qualifies
-                const int64_t nlo = f > 0 ? lo + (int64_t)f * step : lo;
-                const int64_t nhi = lo + (int64_t)(f + 1) * step;
-                lo = nlo;
-                hi = nhi < hi ? nhi : hi;
-            }
-            const bool ge = lo + lane >= hi - 1 || chunk_end(lo + lane) >= rd;
-            const int64_t cs_ = lo + (__ffsll((long long)__ballot(ge)) - 1);
-            // rows of chunk cs_
-            const int64_t r0 = cs_ * KPP_CHUNK;
-            const int n = (int)(N - r0 < KPP_CHUNK ? N - r0 : KPP_CHUNK);
-            constexpr int EPL = KPP_CHUNK / 64;
-            double v[EPL];
-            if (chunk_mode[cs_] != 0) {
-#pragma unroll
-                for (int t = 0; t < EPL; t++) {
-                    const int i = lane * EPL + t;
-                    v[t] = cum[r0 + (i < n ? i : n - 1)];
-                }
-            } else {
-                const int e = meta[cs_].e;
-                const int64_t su = (int64_t)ldexp(chunk_s[cs_], 52 - e);
-                int64_t r[EPL], own = 0;
-#pragma unroll
-                for (int t = 0; t < EPL; t++) {
-                    const int i = lane * EPL + t;
-                    r[t] = i < n ? kpp_units(qbuf[r0 + i], e) : 0;
-                    own += r[t];
-                }
-                int64_t run = su + wave_incl_scan64(own, lane) - own;
-#pragma unroll
-                for (int t = 0; t < EPL; t++) {
-                    run += r[t];
-                    v[t] = ldexp((double)run, e - 52);
-                }
-            }
-            int lf = EPL;
-#pragma unroll
-            for (int t = 0; t < EPL; t++)
-                if (lf == EPL && lane * EPL + t < n && v[t] >= rd) lf = t;
-            const unsigned long long b = __ballot(lf < EPL);
-            const int fl = b ? __ffsll((long long)b) - 1 : 63;      // b != 0: the chunk's end reaches rd
-            pick = r0 + fl * EPL + __builtin_amdgcn_readlane(lf, fl);
-        }
-        if (lane == 0) chosen[it] = (int32_t)pick;
-    }
 #if defined(KPP_PROF)
     if (lane == 0) printf("KPPPROF %llu %llu %llu %llu %llu %llu %llu\n", tp[0], tp[1], tp[2], tp[3], tp[4], nseq, npass);
 #endif
-    if (lane == 0 && stats) {
+    return s;
+}
+
+// The reference's binary search (:132-149) = the first row whose prefix sum
+// reaches rd, for rd <= total (the sum after row N - 1; the sums never
+// decrease). The prefix sums are never materialised: the chunk by a 64-ary
+// search over the chunk ends, then its rows (the walk wrote a stop chunk's; an
+// integer chunk's are formed here). One wave, after kpp_walk.
+__device__ __forceinline__ int64_t kpp_search(const double* __restrict__ qbuf, int64_t N,
+                                              const KppChunk* __restrict__ meta, int64_t nch, const double* chunk_s,
+                                              const int32_t* chunk_mode, const double* cum, double total, double rd) {
+    const int lane = threadIdx.x;
+    auto chunk_end = [&](int64_t cc) -> double { return cc + 1 < nch ? chunk_s[cc + 1] : total; };
+    int64_t lo = 0, hi = nch;              // the first chunk whose end reaches rd lies in [lo, hi)
+    while (hi - lo > 64) {
+        const int64_t step = (hi - lo + 63) / 64;
+        const int64_t p = lo + (int64_t)(lane + 1) * step - 1;
+        const bool ge = p >= hi - 1 || chunk_end(p) >= rd;
+        const unsigned long long b = __ballot(ge);
+        const int f = __ffsll((long long)b) - 1;          // lane 63 always qualifies
+        const int64_t nlo = f > 0 ? lo + (int64_t)f * step : lo;
+        const int64_t nhi = lo + (int64_t)(f + 1) * step;
+        lo = nlo;
+        hi = nhi < hi ? nhi : hi;
+    }
+    const bool ge = lo + lane >= hi - 1 || chunk_end(lo + lane) >= rd;
+    const int64_t cs_ = lo + (__ffsll((long long)__ballot(ge)) - 1);
+    // rows of chunk cs_
+    const int64_t r0 = cs_ * KPP_CHUNK;
+    const int n = (int)(N - r0 < KPP_CHUNK ? N - r0 : KPP_CHUNK);
+    constexpr int EPL = KPP_CHUNK / 64;
+    double v[EPL];
+    if (chunk_mode[cs_] != 0) {
+#pragma unroll
+        for (int t = 0; t < EPL; t++) {
+            const int i = lane * EPL + t;
+            v[t] = cum[r0 + (i < n ? i : n - 1)];
+        }
+    } else {
+        const int e = meta[cs_].e;
+        const int64_t su = (int64_t)ldexp(chunk_s[cs_], 52 - e);
+        int64_t r[EPL], own = 0;
+#pragma unroll
+        for (int t = 0; t < EPL; t++) {
+            const int i = lane * EPL + t;
+            r[t] = i < n ? kpp_units(qbuf[r0 + i], e) : 0;
+            own += r[t];
+        }
+        int64_t run = su + wave_incl_scan64(own, lane) - own;
+#pragma unroll
+        for (int t = 0; t < EPL; t++) {
+            run += r[t];
+            v[t] = ldexp((double)run, e - 52);
+        }
+    }
+    int lf = EPL;
+#pragma unroll
+    for (int t = 0; t < EPL; t++)
+        if (lf == EPL && lane * EPL + t < n && v[t] >= rd) lf = t;
+    const unsigned long long b = __ballot(lf < EPL);
+    const int fl = b ? __ffsll((long long)b) - 1 : 63;      // b != 0: the chunk's end reaches rd
+    return r0 + fl * EPL + __builtin_amdgcn_readlane(lf, fl);
+}
+
+__device__ inline void kpp_walk_stats(unsigned long long* __restrict__ stats, int64_t nch, unsigned long long nseq) {
+    if (threadIdx.x == 0 && stats) {
         atomicAdd(stats + STAT_KPP_CHUNKS, (unsigned long long)nch);
         atomicAdd(stats + STAT_KPP_SEQ, nseq);
     }
 }
 
+// One device: the walk from 0, then (4) the draw (:127-149): rd =
+// uniform_real(0, total) = canon * (total - 0) + 0 and the search (rd <=
+// total; a NaN total from degenerate minima gives rd NaN and row 0).
+__global__ __launch_bounds__(64) void kpp_chain_kernel(const double* __restrict__ qbuf, int64_t N,
+                                                       const KppChunk* __restrict__ meta, int64_t nch,
+                                                       const int64_t* __restrict__ pa, const int64_t* __restrict__ pb,
+                                                       double* chunk_s, int32_t* chunk_mode,
+                                                       double* cum, const double* __restrict__ canon, int it,
+                                                       int32_t* __restrict__ chosen, unsigned long long* __restrict__ stats) {
+    unsigned long long nseq = 0;
+    const double total = kpp_walk(qbuf, N, meta, nch, pa, pb, chunk_s, chunk_mode, cum, 0.0, nseq);
+    __threadfence();                               // this wave's chunk_s / cum stores, visible to its loads
+    const double rd = __dadd_rn(__dmul_rn(canon[it], __dsub_rn(total, 0.0)), 0.0);
+    int64_t pick = 0;
+    if (rd > qbuf[0])                              // cum[0] = 0 + q_0 = q_0
+        pick = kpp_search(qbuf, N, meta, nch, chunk_s, chunk_mode, cum, total, rd);
+    if (threadIdx.x == 0) chosen[it] = (int32_t)pick;
+    kpp_walk_stats(stats, nch, nseq);
+}
+
+// A shard's walk: from s_in (the sum after the earlier shards' rows; with
+// s_in > 0 its first chunk has a binade and takes the integer path like any
+// other) to s_out; the draw waits for the last shard's s_out, the total.
+__global__ __launch_bounds__(64) void kpp_chain_shard_kernel(const double* __restrict__ qbuf, int64_t N,
+                                                             const KppChunk* __restrict__ meta, int64_t nch,
+                                                             const int64_t* __restrict__ pa, const int64_t* __restrict__ pb,
+                                                             double* chunk_s, int32_t* chunk_mode, double* cum,
+                                                             double s_in, KppShardOut* __restrict__ out,
+                                                             unsigned long long* __restrict__ stats) {
+    unsigned long long nseq = 0;
+    const double s = kpp_walk(qbuf, N, meta, nch, pa, pb, chunk_s, chunk_mode, cum, s_in, nseq);
+    if (threadIdx.x == 0) out->s_out = s;
+    kpp_walk_stats(stats, nch, nseq);
+}
+
+// A shard's part of the search for the draw rd (formed on the host from the
+// total): its first row whose prefix sum reaches rd, or -1. The shard of
+// global row 0 answers row 0 unless rd > q_0 (:139; a NaN rd as well).
+__global__ __launch_bounds__(64) void kpp_pick_shard_kernel(const double* __restrict__ qbuf, int64_t N,
+                                                            const KppChunk* __restrict__ meta, int64_t nch,
+                                                            const double* chunk_s, const int32_t* chunk_mode,
+                                                            const double* cum, double rd, int owns_row0,
+                                                            KppShardOut* out) {
+    const double total = out->s_out;
+    int64_t pick = -1;
+    if (owns_row0 && !(rd > qbuf[0])) pick = 0;
+    else if (total >= rd) pick = kpp_search(qbuf, N, meta, nch, chunk_s, chunk_mode, cum, total, rd);
+    if (threadIdx.x == 0) out->pick = pick;
+}
+
+
+// The workspace of one device or one shard (kmeans_pp_ws_bytes(N) bytes):
+// mind[N] f64, cum[N] f64, then per 256-row group sum m^2, per chunk start f64,
+// meta, s_start f64, mode i32, the max word with the shard's host-read values
+// behind it, the per-block maxima, q[N] and the prefix arrays.
+struct KppWs {
+    int64_t nch, ngroups;
+    unsigned dgrid;
+    size_t out_off;                // of `out` in the workspace
+    double *mind, *cum, *gsum, *cstart, *cs, *qbuf;
+    KppChunk* meta;
+    int32_t* mode;
+    unsigned long long *mx, *bmax;
+    KppShardOut* out;
+    int64_t *pa, *pb;
+};
+static_assert(8 + sizeof(KppShardOut) <= 64, "the max word's 64 bytes hold the shard's outputs");
+
+static KppWs kpp_carve(void* ws, int64_t N) {
+    KppWs w;
+    w.nch = (N + KPP_CHUNK - 1) / KPP_CHUNK;
+    w.ngroups = (N + KPP_THREADS - 1) / KPP_THREADS;
+    w.dgrid = gsz(N, KPP_THREADS, 4096);
+    char* p = (char*)ws;
+    w.mind = (double*)p;                 p += sizeof(double) * N;
+    w.cum = (double*)p;                  p += sizeof(double) * N;
+    w.gsum = (double*)p;                 p += sizeof(double) * ((w.ngroups + 1) & ~1ll);   // per 256-row group sum m^2
+    w.cstart = (double*)p;               p += sizeof(double) * w.nch;
+    w.meta = (KppChunk*)p;               p += sizeof(KppChunk) * w.nch;
+    w.cs = (double*)p;                   p += sizeof(double) * w.nch;
+    w.mode = (int32_t*)p;                p += sizeof(int32_t) * ((w.nch + 1) & ~1ll);
+    w.mx = (unsigned long long*)p;
+    w.out = (KppShardOut*)(p + 8);
+    w.out_off = (size_t)(p + 8 - (char*)ws);
+    p += 64;
+    w.bmax = (unsigned long long*)p;     p += 4096 * 8;   // [<= 4096] per-block maxima
+    w.qbuf = (double*)p;                 p += sizeof(double) * N;   // [N] q_m
+    w.pa = (int64_t*)p;                  p += sizeof(int64_t) * N;  // crossing chunks' prefix arrays
+    w.pb = (int64_t*)p;
+    return w;
+}
+
+// The distance pass of iteration `it` against the newest centroid: row
+// chosen[it - 1] of X, or the [d] row cext of X's type (a shard: the row
+// usually lies on another rank).
+static void kpp_launch_dist(hipStream_t s, Pts X, int64_t N, int d, int metric, const int32_t* chosen, const void* cext,
+                            int it, const KppWs& w) {
+    const bool vec = d % KPP_DJ == 0 && !X.f64;
+    const dim3 g(w.dgrid), b(KPP_THREADS);
+    const size_t ld32 = (size_t)d * 4, ld64 = (size_t)d * 8;     // the centroid row in LDS
+    const float* cf = (const float*)cext;
+    const double* cd = (const double*)cext;
+    if (X.f64) {
+        if (metric == 0) hipLaunchKernelGGL((kpp_dist_kernel<0, false, double>), g, b, ld64, s, X.d(), N, d, chosen, cd, it, w.mind, w.bmax, w.gsum);
+        else hipLaunchKernelGGL((kpp_dist_kernel<1, false, double>), g, b, ld64, s, X.d(), N, d, chosen, cd, it, w.mind, w.bmax, w.gsum);
+    } else if (metric == 0 && vec)
+        hipLaunchKernelGGL(kpp_dist_reg_kernel, g, b, ld32, s, X.f(), N, d, chosen, cf, it, w.mind, w.bmax, w.gsum);
+    else if (metric == 0)
+        hipLaunchKernelGGL((kpp_dist_kernel<0, false, float>), g, b, ld32, s, X.f(), N, d, chosen, cf, it, w.mind, w.bmax, w.gsum);
+    else if (vec)
+        hipLaunchKernelGGL((kpp_dist_kernel<1, true, float>), g, b, ld32, s, X.f(), N, d, chosen, cf, it, w.mind, w.bmax, w.gsum);
+    else
+        hipLaunchKernelGGL((kpp_dist_kernel<1, false, float>), g, b, ld32, s, X.f(), N, d, chosen, cf, it, w.mind, w.bmax, w.gsum);
+}
+
 // Runs iterations 1..K-1; chosen[0] and canon[1..K-1] are already on the device.
-// ws: mind[N] f64, cum[N] f64, then per chunk sum/start f64, meta, s_start f64,
-// mode i32, and the max word.
 int launch_kmeans_pp(hipStream_t s, Pts X, int64_t N, int d, int K, int metric, const double* canon,
                      int32_t* chosen, void* ws, unsigned long long* stats) {
-
-    const int64_t nch = (N + KPP_CHUNK - 1) / KPP_CHUNK;
-    char* p = (char*)ws;
-    double* mind = (double*)p;                 p += sizeof(double) * N;
-    double* cum = (double*)p;                  p += sizeof(double) * N;
-    const int64_t ngroups = (N + KPP_THREADS - 1) / KPP_THREADS;
-    double* gsum = (double*)p;                 p += sizeof(double) * ((ngroups + 1) & ~1ll);   // per 256-row group sum m^2
-    double* cstart = (double*)p;               p += sizeof(double) * nch;
-    KppChunk* meta = (KppChunk*)p;             p += sizeof(KppChunk) * nch;
-    double* cs = (double*)p;                   p += sizeof(double) * nch;
-    int32_t* mode = (int32_t*)p;               p += sizeof(int32_t) * ((nch + 1) & ~1ll);
-    unsigned long long* mx = (unsigned long long*)p;   p += 64;
-    unsigned long long* bmax = (unsigned long long*)p;   p += 4096 * 8;   // [<= 4096] per-block maxima
-    double* qbuf = (double*)p;                 p += sizeof(double) * N;   // [N] q_m
-    int64_t* pa = (int64_t*)p;                 p += sizeof(int64_t) * N;  // crossing chunks' prefix arrays
-    int64_t* pb = (int64_t*)p;
-    const unsigned dgrid = gsz(N, KPP_THREADS, 4096);
+    const KppWs w = kpp_carve(ws, N);
     for (int it = 1; it < K; it++) {
-
-        const bool vec = d % KPP_DJ == 0 && !X.f64;
-        const dim3 g(dgrid), b(KPP_THREADS);
-        const size_t ld32 = (size_t)d * 4, ld64 = (size_t)d * 8;     // the centroid row in LDS
-        if (X.f64) {
-            if (metric == 0) hipLaunchKernelGGL((kpp_dist_kernel<0, false, double>), g, b, ld64, s, X.d(), N, d, chosen, it, mind, bmax, gsum);
-            else hipLaunchKernelGGL((kpp_dist_kernel<1, false, double>), g, b, ld64, s, X.d(), N, d, chosen, it, mind, bmax, gsum);
-        } else if (metric == 0 && vec)
-            hipLaunchKernelGGL(kpp_dist_reg_kernel, g, b, ld32, s, X.f(), N, d, chosen, it, mind, bmax, gsum);
-        else if (metric == 0)
-            hipLaunchKernelGGL((kpp_dist_kernel<0, false, float>), g, b, ld32, s, X.f(), N, d, chosen, it, mind, bmax, gsum);
-        else if (vec)
-            hipLaunchKernelGGL((kpp_dist_kernel<1, true, float>), g, b, ld32, s, X.f(), N, d, chosen, it, mind, bmax, gsum);
-        else
-            hipLaunchKernelGGL((kpp_dist_kernel<1, false, float>), g, b, ld32, s, X.f(), N, d, chosen, it, mind, bmax, gsum);
-        hipLaunchKernelGGL(kpp_scan_kernel, dim3(1), dim3(KPP_SCAN_THREADS), 0, s, bmax, (int)dgrid, gsum, ngroups, nch, mx, cstart);
-        hipLaunchKernelGGL(kpp_chunk_units_kernel, dim3((unsigned)nch), dim3(KPP_THREADS), 0, s, mind, N, mx, qbuf, cstart, nch, meta,
-                           pa, pb);
-        hipLaunchKernelGGL(kpp_chain_kernel, dim3(1), dim3(64), 0, s, qbuf, N, meta, nch, pa, pb, cs, mode, cum, canon, it,
-                           chosen, stats);
+        kpp_launch_dist(s, X, N, d, metric, chosen, nullptr, it, w);
+        hipLaunchKernelGGL(kpp_scan_kernel, dim3(1), dim3(KPP_SCAN_THREADS), 0, s, w.bmax, (int)w.dgrid, w.gsum, w.ngroups, w.nch,
+                           w.mx, w.cstart);
+        hipLaunchKernelGGL(kpp_chunk_units_kernel, dim3((unsigned)w.nch), dim3(KPP_THREADS), 0, s, w.mind, N, w.mx, w.qbuf,
+                           w.cstart, w.nch, w.meta, w.pa, w.pb);
+        hipLaunchKernelGGL(kpp_chain_kernel, dim3(1), dim3(64), 0, s, w.qbuf, N, w.meta, w.nch, w.pa, w.pb, w.cs, w.mode, w.cum,
+                           canon, it, chosen, stats);
         const int rc = kstatus("kmeanspp.hip");
         if (rc) return rc;
     }
@@ -859,6 +1012,47 @@ size_t kmeans_pp_ws_bytes(int64_t N) {
            (sizeof(double) * 2 + sizeof(KppChunk)) * (size_t)nch +
            sizeof(int32_t) * (size_t)((nch + 1) & ~1ll) + 64 + 4096 * 8 + sizeof(double) * (size_t)N +
            2 * sizeof(int64_t) * (size_t)N;
+}
+
+// ------------------------------------------------------------- row shards
+// One iteration over contiguous row shards (lshkm_kpp_shard_*): the same
+// kernels per shard, the same workspace (n >= 1 rows; the callers skip an empty
+// shard), with the host between the steps: dist -> (max, sum m^2) of the shard;
+// units with the global max and the approximate sum before the shard; chain
+// from the exact s after the previous shard; pick for the draw. Each step's
+// host-read values lie at kpp_shard_out (ws + kpp_shard_out_offset(n)).
+size_t kpp_shard_out_offset(int64_t n) {
+    return kpp_carve(nullptr, n).out_off;
+}
+
+int launch_kpp_shard_dist(hipStream_t s, Pts X, int64_t n, int d, int metric, const void* crow, int it, void* ws) {
+    const KppWs w = kpp_carve(ws, n);
+    kpp_launch_dist(s, X, n, d, metric, nullptr, crow, it, w);
+    hipLaunchKernelGGL(kpp_fold_kernel, dim3(1), dim3(KPP_SCAN_THREADS), 0, s, w.bmax, (int)w.dgrid, w.gsum, w.ngroups, w.out);
+    return kstatus("kmeanspp.hip (shard dist)");
+}
+
+int launch_kpp_shard_units(hipStream_t s, int64_t n, unsigned long long gmax_bits, double start, void* ws) {
+    const KppWs w = kpp_carve(ws, n);
+    hipLaunchKernelGGL(kpp_starts_kernel, dim3(1), dim3(KPP_SCAN_THREADS), 0, s, w.gsum, w.ngroups, w.nch, gmax_bits, start,
+                       w.mx, w.cstart);
+    hipLaunchKernelGGL(kpp_chunk_units_kernel, dim3((unsigned)w.nch), dim3(KPP_THREADS), 0, s, w.mind, n, w.mx, w.qbuf, w.cstart,
+                       w.nch, w.meta, w.pa, w.pb);
+    return kstatus("kmeanspp.hip (shard units)");
+}
+
+int launch_kpp_shard_chain(hipStream_t s, int64_t n, double s_in, void* ws, unsigned long long* stats) {
+    const KppWs w = kpp_carve(ws, n);
+    hipLaunchKernelGGL(kpp_chain_shard_kernel, dim3(1), dim3(64), 0, s, w.qbuf, n, w.meta, w.nch, w.pa, w.pb, w.cs, w.mode, w.cum,
+                       s_in, w.out, stats);
+    return kstatus("kmeanspp.hip (shard chain)");
+}
+
+int launch_kpp_shard_pick(hipStream_t s, int64_t n, double rd, int owns_row0, void* ws) {
+    const KppWs w = kpp_carve(ws, n);
+    hipLaunchKernelGGL(kpp_pick_shard_kernel, dim3(1), dim3(64), 0, s, w.qbuf, n, w.meta, w.nch, w.cs, w.mode, w.cum, rd,
+                       owns_row0, w.out);
+    return kstatus("kmeanspp.hip (shard pick)");
 }
 
 }  // namespace lshkm

@@ -125,6 +125,12 @@ def lib():
             "lshkm_kmeans_shard_prepare": (i32, [vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, vp, i64]),
             "lshkm_kmeans_shard_chain": (i32, [vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, vp, i64, vp]),
             "lshkm_kmeans_pp": (i32, [vp, vp, i64, i32, i32, i32, u64, vp]),
+            "lshkm_kpp_draws": (i32, [u64, i64, i32, C.POINTER(i64), vp]),
+            "lshkm_kpp_shard_ws_bytes": (i32, [i64, C.POINTER(i64)]),
+            "lshkm_kpp_shard_dist": (i32, [vp, vp, i64, i32, i32, vp, i32, vp, i64, C.POINTER(u64), C.POINTER(f64)]),
+            "lshkm_kpp_shard_units": (i32, [vp, i64, u64, f64, vp, i64]),
+            "lshkm_kpp_shard_chain": (i32, [vp, i64, f64, vp, i64, C.POINTER(f64)]),
+            "lshkm_kpp_shard_pick": (i32, [vp, i64, f64, i32, vp, i64, C.POINTER(i64)]),
             "lshkm_rand_selection": (i32, [u64, i64, i32, vp]),
             "lshkm_p_closest": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, i32, vp, vp, vp]),
             "lshkm_top_n_recom": (i32, [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i32, i32, vp]),
@@ -680,6 +686,63 @@ def kmeans_pp_rows(ctx, X, K, metric="euclidean", seed=1):
     rows = np.empty(K, np.int32)
     _ck(_fn("lshkm_kmeans_pp", X)(ctx.h, _t_ptr(X), N, d, K, _METRIC[metric], int(seed), _np_ptr(rows)))
     return rows
+
+
+def kpp_draws(seed, n_total, K):
+    """k_means_pp's engine draws (lshkm_kpp_draws; initialization.hpp:75-79,
+    132-133; host only): (first row, canon float64 [K], canon[0] = 0)."""
+    first, canon = C.c_int64(), np.empty(K, np.float64)
+    _ck(lib().lshkm_kpp_draws(int(seed), int(n_total), int(K), C.byref(first), _np_ptr(canon)))
+    return int(first.value), canon
+
+
+class KppShard:
+    """One rank's part of the sharded k-means++ seeding (lshkm_kpp_shard_*,
+    include/lshkm.h): X this rank's rows [n][d] (n may be 0), a device tensor.
+    sharding.kmeans_pp_sharded runs the exchange between the calls; the values
+    that cross it are host scalars, and the workspace keeps the running minima
+    through the K - 1 iterations."""
+
+    def __init__(self, ctx, X, metric="euclidean"):
+        self.ctx, self.X, self.metric = ctx, X, _METRIC[metric]
+        self.n, self.d = X.shape
+        nb = C.c_int64()
+        _ck(lib().lshkm_kpp_shard_ws_bytes(self.n, C.byref(nb)))
+        self.ws = ctx.empty((int(nb.value),), ctx.torch.uint8) if self.n else None
+        self.ws_bytes = int(nb.value) if self.n else 0
+
+    draws = staticmethod(kpp_draws)
+
+    def row(self, i):
+        """Local row i as float64 numpy [d] (exact for either row type)."""
+        return self.X[int(i)].double().cpu().numpy()
+
+    def dist(self, c, it):
+        """c: the newest centroid's row (float64 [d] holding values of the rows'
+        type) -> (max of the shard's minima as a bit pattern, approximate sum min^2)."""
+        mb, sm = C.c_uint64(), C.c_double()
+        cd = None
+        if self.n:
+            cd = self.ctx.torch.from_numpy(np.ascontiguousarray(c, np.float64)).to(self.X.dtype).to(self.ctx.dev)
+        _ck(_fn("lshkm_kpp_shard_dist", self.X)(self.ctx.h, _t_ptr(self.X) if self.n else None, self.n, self.d,
+                                                self.metric, _t_ptr(cd), int(it), _t_ptr(self.ws), self.ws_bytes,
+                                                C.byref(mb), C.byref(sm)))
+        return int(mb.value), float(sm.value)
+
+    def units(self, gmax_bits, start):
+        _ck(lib().lshkm_kpp_shard_units(self.ctx.h, self.n, int(gmax_bits), float(start), _t_ptr(self.ws),
+                                        self.ws_bytes))
+
+    def chain(self, s_in):
+        s = C.c_double()
+        _ck(lib().lshkm_kpp_shard_chain(self.ctx.h, self.n, float(s_in), _t_ptr(self.ws), self.ws_bytes, C.byref(s)))
+        return float(s.value)
+
+    def pick(self, rd, owns_row0):
+        r = C.c_int64()
+        _ck(lib().lshkm_kpp_shard_pick(self.ctx.h, self.n, float(rd), int(bool(owns_row0)), _t_ptr(self.ws),
+                                       self.ws_bytes, C.byref(r)))
+        return int(r.value)
 
 
 def clusters(ctx, assign, K):

@@ -12,7 +12,10 @@ row index. With contiguous row shards [row0, row0 + n) in rank order:
     sequential chain per (cluster, dim) in row order: kmeans_sums_sharded gets
     that chain's value bit for bit from one all-gather of the K x d partial sums
     plus three all-reduces, wherever the chain provably never rounds (the global
-    never-rounds test), and carries only the other chains rank to rank.
+    never-rounds test), and carries only the other chains rank to rank;
+  - k-means++ seeding needs the global max of the rows' minimum distances and
+    ONE sequential fp64 prefix sum over all rows in row order:
+    kmeans_pp_sharded carries that sum's one running double rank to rank.
 Host logic (numpy + torch.distributed); the compute is the HIP library.
 Collectives: RCCL ("nccl") on GPU tensors; with the gloo backend (CPU tests,
 or several ranks sharing one GPU) device tensors are staged through host
@@ -242,6 +245,167 @@ def allreduce_partials(sums, counts):
     return sums, counts
 
 
+class DistExchange:
+    """kmeans_pp_sharded's exchange over torch.distributed: this process is one
+    rank and holds one shard. The values are host scalars and one row, so the
+    collectives run on host tensors with gloo; with another backend (RCCL) they
+    are staged through `device`."""
+
+    def __init__(self, device=None):
+        import torch
+        import torch.distributed as dist
+        self.torch, self.dist = torch, dist
+        self.on = dist.is_available() and dist.is_initialized()
+        self.world = dist.get_world_size() if self.on else 1
+        self.rank = dist.get_rank() if self.on else 0
+        self.device = device if self.on and dist.get_backend() != "gloo" else None
+
+    def local(self, ops, row0, n):
+        return [(self.rank, ops, int(row0), int(n))]
+
+    def _t(self, a):
+        t = self.torch.from_numpy(np.ascontiguousarray(a))
+        return t.to(self.device) if self.device is not None else t
+
+    def all_gather(self, vals):
+        """vals: one numpy vector per local shard -> [world][m], in rank order."""
+        if self.world == 1:
+            return np.stack(vals)
+        t = self._t(vals[0])
+        parts = [self.torch.empty_like(t) for _ in range(self.world)]
+        self.dist.all_gather(parts, t)
+        return np.stack([p.cpu().numpy() for p in parts])
+
+    def chain(self, fns):
+        """s through the shards' fns (s_in -> s_out) in rank order from 0.0:
+        world - 1 point-to-point hops of one double, then the last rank's
+        broadcast of the total."""
+        s = self._t(np.zeros(1, np.float64))
+        if self.rank > 0:
+            self.dist.recv(s, src=self.rank - 1)
+        s = self._t(np.array([fns[0](float(s.cpu()[0]))], np.float64))
+        if self.world > 1:
+            if self.rank + 1 < self.world:
+                self.dist.send(s, dst=self.rank + 1)
+            self.dist.broadcast(s, src=self.world - 1)
+        return float(s.cpu()[0])
+
+    def all_min(self, vals):
+        t = self._t(np.array([min(vals)], np.int64))
+        if self.world > 1:
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.MIN)
+        return int(t.cpu()[0])
+
+    def bcast(self, owner, get, m):
+        """The float64 [m] vector get() returns on rank `owner`, on every rank."""
+        t = self._t(get() if self.rank == owner else np.zeros(m, np.float64))
+        if self.world > 1:
+            self.dist.broadcast(t, src=owner)
+        return t.cpu().numpy()
+
+
+class LocalExchange:
+    """The same exchange inside one process: every shard is local (ops, row0
+    and n are lists in rank order), e.g. several shards on one GPU."""
+
+    def local(self, ops, row0, n):
+        self.world = len(ops)
+        return [(r, o, int(a), int(b)) for r, (o, a, b) in enumerate(zip(ops, row0, n))]
+
+    def all_gather(self, vals):
+        return np.stack(vals)
+
+    def chain(self, fns):
+        s = 0.0
+        for f in fns:
+            s = f(s)
+        return s
+
+    def all_min(self, vals):
+        return int(min(vals))
+
+    def bcast(self, owner, get, m):
+        return np.asarray(get(), np.float64)
+
+
+def kmeans_pp_sharded(ops, row0, n, n_total, K, seed, exchange=None):
+    """k_means_pp (initialization.hpp:71-156; main.cpp:96, :340) over contiguous
+    row shards, bit for bit lshkm.kmeans_pp_rows / oracle.kmeans_pp on the
+    concatenated rows (lshkm_kpp_shard_*, include/lshkm.h). This rank holds rows
+    [row0, row0 + n) of n_total (n = 0 is fine); ops: lshkm.KppShard over them
+    (or a restatement with the same methods). Returns (rows int64 [K] of global
+    row indices, C0 float64 [K][d] numpy), identical on every rank.
+
+    exchange: DistExchange() (the default: torch.distributed, one shard per
+    process; without a process group, one shard) or LocalExchange() with ops,
+    row0 and n as lists in rank order (every shard in this process). The
+    engine's draws (ops.draws: host only) are formed on every rank.
+
+    A later row needs from the earlier ones only the max of the minima and the
+    running prefix sum, so per new centroid:
+      dist;  all-gather the (max bits, approximate sum min^2) pairs;  every rank
+      forms the global max (the largest bit pattern; 0 if none) and its
+      approximate start (the lower ranks' sums / max^2);  units;  chain, s
+      received from rank - 1 and sent to rank + 1;  the last rank broadcasts the
+      total;  rd = canon * (total - 0) + 0 in fp64 on the host;  pick;
+      all-reduce MIN of row0 + local row (a sentinel for "none");  the owner
+      broadcasts the chosen row.
+    Cost per new centroid: 4 collectives (an all-gather of 16 bytes per rank,
+    a broadcast of 8 bytes, an all-reduce of 8 bytes, a broadcast of d * 8
+    bytes) and world - 1 point-to-point hops of 8 bytes IN SERIES (rank r's walk
+    starts when rank r - 1's has ended), each step with its host round trip to
+    the device; K - 1 of them, after one all-gather of the layout and one
+    broadcast of the first row. Nothing overlaps the hops.
+
+    The rows feed ShardedLloyd as local_src_rows(rows, row0, n), C0 as its
+    centers (torch.from_numpy(C0).to(device))."""
+    ex = exchange if exchange is not None else DistExchange()
+    parts = ex.local(ops, row0, n)
+    first, canon = parts[0][1].draws(seed, n_total, K)
+    d = parts[0][1].d
+    # every rank's (row0, n): contiguous in rank order, so a global row's owner is known everywhere
+    lay = ex.all_gather([np.array([r0, nn], np.int64) for _, _, r0, nn in parts])
+    ends = lay[:, 0] + lay[:, 1]
+    if lay[0, 0] != 0 or ends[-1] != n_total or (lay[1:, 0] != ends[:-1]).any() or (lay[:, 1] < 0).any():
+        raise ValueError(f"shards are not contiguous rows of {n_total} in rank order: {lay.tolist()}")
+    by_rank = {r: (o, r0) for r, o, r0, _ in parts}
+
+    def fetch(g):
+        """Global row g's values, from its owner."""
+        owner = int(np.nonzero((lay[:, 0] <= g) & (g < ends))[0][0])
+        o, r0 = by_rank.get(owner, (None, 0))
+        return ex.bcast(owner, lambda: o.row(g - r0), d)
+
+    NONE = np.iinfo(np.int64).max
+    rows = np.empty(K, np.int64)
+    C0 = np.empty((K, d), np.float64)
+    rows[0], C0[0] = first, fetch(first)
+    for it in range(1, K):
+        pairs = []
+        for _, o, _, _ in parts:
+            mb, sm = o.dist(C0[it - 1], it)
+            pairs.append(np.array([mb], np.uint64).view(np.float64).tolist() + [sm])
+        g = ex.all_gather([np.array(p, np.float64) for p in pairs])
+        gmax_bits = int(np.ascontiguousarray(g[:, 0]).view(np.uint64).max())
+        gmax = float(np.array([gmax_bits], np.uint64).view(np.float64)[0])
+        with np.errstate(all="ignore"):
+            before = np.concatenate([[0.0], np.cumsum(g[:, 1])])[:-1] / np.float64(gmax * gmax)
+        for r, o, _, _ in parts:
+            o.units(gmax_bits, float(before[r]))
+        total = ex.chain([o.chain for _, o, _, _ in parts])
+        with np.errstate(all="ignore"):
+            rd = float(np.float64(canon[it]) * (np.float64(total) - np.float64(0.0)) + np.float64(0.0))
+        found = []
+        for _, o, r0, nn in parts:
+            loc = o.pick(rd, r0 == 0 and nn > 0)
+            found.append(r0 + loc if loc >= 0 else NONE)
+        row = ex.all_min(found)
+        if row == NONE:
+            raise RuntimeError(f"k-means++ iteration {it}: no shard holds a row for the draw {rd!r} of total {total!r}")
+        rows[it], C0[it] = row, fetch(row)
+    return rows, C0
+
+
 def recommend_terms(lk, ctx, X, x_mean, assign, K, U, u_mean, ucl, unk_ptr, unk_idx, csr=None):
     """Phase 1 of recommend_sharded (steps 1-2 below): this rank's similarities
     and prediction terms, all ranks at once. Returns the state recommend_chain
@@ -384,7 +548,10 @@ class ShardedLloyd:
         the shards' updates in series; kept as the cross-check)
       lshkm_kmeans_finalize -- means, the reference's continue test
     and the centers are replaced when k_means would replace them
-    (update.hpp:63-80). X: this rank's rows [row0, row0 + n) of N_total."""
+    (update.hpp:63-80). X: this rank's rows [row0, row0 + n) of N_total.
+    The reference's start (k_means_pp, main.cpp:96) needs nothing more here:
+    (rows, C0) = kmeans_pp_sharded(...) give src_rows = local_src_rows(rows,
+    row0, n) and the centers C0 (as a device tensor)."""
 
     MODES = ("certified", "carry")
 

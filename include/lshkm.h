@@ -460,6 +460,52 @@ int lshkm_kmeans_pp(lshkm_ctx ctx, const float* X_dev, int64_t N, int d, int K, 
                     int32_t* rows_host);
 int lshkm_kmeans_pp_f64(lshkm_ctx ctx, const double* X_dev, int64_t N, int d, int K, int metric, uint64_t seed,
                         int32_t* rows_host);
+/* k_means_pp over contiguous row shards in rank order (rank r holds rows
+ * [row0_r, row0_r + n_r) of N_total; n_r = 0 is legal in every call and
+ * touches no memory), bit for bit lshkm_kmeans_pp on the concatenated rows.
+ * lshkm_kpp_draws (host only, identical on every rank): the engine's draws in
+ * the reference's order -- *first_row_host (:75-79), then one canonical
+ * uniform_real<double>(0, 1) per new centroid, canon_host[1..K-1] (:132-133;
+ * canon_host[0] = 0): uniform_real(0, total) is canon * (total - 0) + 0.
+ * A later row needs from the earlier ones only the max of the minima
+ * (:117-118) and the running prefix sum (:123-129), so per new centroid
+ * i = 1..K-1 every rank runs, with the host and the exchange between the calls
+ * (sharding.kmeans_pp_sharded runs it over torch.distributed):
+ *  1. lshkm_kpp_shard_dist: the rows' distances to centroid i - 1 (c_dev: its
+ *     [d] row, of the rows' type; :93-119) folded into the running minima kept
+ *     in ws_dev; *max_bits_host = the shard's max of minima as a bit pattern
+ *     (0 if none is > 0), *sum_host = its approximate sum of min^2. it = i.
+ *  2. exchange: all-gather the pairs. The global max is the largest bit
+ *     pattern; start = (the lower ranks' sums) / max^2 approximates the prefix
+ *     sum before this shard.
+ *  3. lshkm_kpp_shard_units: (min / max)^2 of every row with the GLOBAL max
+ *     (:123-127) and the chunk guesses from `start` (a guess: a wrong one
+ *     costs time, never correctness).
+ *  4. in rank order lshkm_kpp_shard_chain: the sequential fp64 chain (:128)
+ *     continued from s_in (the previous rank's *s_out_host; 0 on the first)
+ *     over this rank's rows; send *s_out_host on. The last rank's is the total
+ *     (:132): broadcast it.
+ *  5. rd = canon[i] * (total - 0) + 0 in fp64 (:132-133, canon from
+ *     lshkm_kpp_draws), then lshkm_kpp_shard_pick: *row_host = the first local
+ *     row whose prefix sum is >= rd, or -1; with owns_row0 (the rank holding
+ *     global row 0) row 0 unless rd > its prefix sum (:139, a NaN rd
+ *     included). The chosen row (:134-149) is the minimum of row0 + *row_host
+ *     over the ranks that found one.
+ * ws_dev: at least lshkm_kpp_shard_ws_bytes(n) bytes, the same buffer through
+ * all K - 1 iterations (it holds the minima). The chain adds to the counters
+ * the single-device walk uses. n < 2^31, d <= 4096. */
+int lshkm_kpp_draws(uint64_t seed, int64_t N_total, int K, int64_t* first_row_host, double* canon_host);
+int lshkm_kpp_shard_ws_bytes(int64_t n, int64_t* bytes_host);
+int lshkm_kpp_shard_dist(lshkm_ctx ctx, const float* X_dev, int64_t n, int d, int metric, const float* c_dev, int it,
+                         void* ws_dev, int64_t ws_bytes, uint64_t* max_bits_host, double* sum_host);
+int lshkm_kpp_shard_dist_f64(lshkm_ctx ctx, const double* X_dev, int64_t n, int d, int metric, const double* c_dev,
+                             int it, void* ws_dev, int64_t ws_bytes, uint64_t* max_bits_host, double* sum_host);
+int lshkm_kpp_shard_units(lshkm_ctx ctx, int64_t n, uint64_t gmax_bits, double start, void* ws_dev,
+                          int64_t ws_bytes);
+int lshkm_kpp_shard_chain(lshkm_ctx ctx, int64_t n, double s_in, void* ws_dev, int64_t ws_bytes,
+                          double* s_out_host);
+int lshkm_kpp_shard_pick(lshkm_ctx ctx, int64_t n, double rd, int owns_row0, void* ws_dev, int64_t ws_bytes,
+                         int64_t* row_host);
 /* rand_selection (initialization.hpp:39-69): K distinct rows drawn uniformly,
  * redrawing on a repeat. Host only. 1 <= K <= N. */
 int lshkm_rand_selection(uint64_t seed, int64_t N, int K, int32_t* rows_host);
