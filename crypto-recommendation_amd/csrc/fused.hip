@@ -154,6 +154,8 @@ int fused_hi_passes(hipStream_t s, const FusedArgs& hi, const FusedPlan& p) {
             const bool small = a.Kpad <= FH_GATH_KMAX && gather_on;
             h.fast = small && a.fast_dist;
             h.gath = small && !a.fast_dist;
+            // the FAST form fetches its rows one tile ahead (LSHKM_ROW_PREFETCH=0: at the tile's top)
+            h.rowpf = h.fast && !test_switch("LSHKM_ROW_PREFETCH", "0");
         } else if (!p.cos) {
             h.fast = !h.hash && a.fast_dist && a.pass_last;
         }

@@ -220,6 +220,41 @@ __device__ inline void glds16(const void* gsrc, uint32_t lds_dst) {
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
+// Row prefetch (PF, the FAST single-pass form on fp32 rows of 128 dims): a
+// software pipeline one tile deep, per wave, with no barrier. Bit 1 (LDS half):
+// dims 0..63 of the next tile's 32 rows by LDS-DMA into the wave's own 8-KiB
+// buffer after the image (8 pieces of 1 KiB, four 256-B half rows each); the
+// tile's top reads xf[0..31] from it by ds_read_b128. Bit 0 (register half):
+// dims 64..127 by 16-B register loads into 32 registers the hash phase has left
+// free (the centroid loop needs bh, the accumulator and xf), taken over as
+// xf[32..63] at the top. Both are issued between the hash phase and the
+// centroid tiles (pf_next); either alone still waits for the other half at the
+// top (measurement variants, -DLSHKM_ROWPF=1 / 2). DESIGN.md §4 has the
+// ordering rules. Row p of the buffer holds its 16-B chunk c at position
+// c ^ (p & 15): the 16 rows of a ds_read_b128 group on 16 distinct 4-bank
+// groups; the DMA's destination is lane-linear, so the swizzle sits on the
+// per-lane source address (as the gather ring's).
+#ifndef LSHKM_ROWPF
+#define LSHKM_ROWPF 3
+#endif
+constexpr int FH_ROWPF = LSHKM_ROWPF;             // the form the library runs: 0 none, 1 register half, 2 LDS half, 3 both
+constexpr int FH_ROWPF_KMAX = 256;                // the FAST single-pass form's largest Kpad
+constexpr int FH_ROWPF_WAVE = 32 * 64 * 4;        // 32 rows x 64 dims x 4 B
+__host__ __device__ constexpr int fh_rowpf_off(int Kpad, bool hash) { return (fh_lds_bytes(Kpad, hash) + 255) & ~255; }
+static_assert(fh_rowpf_off(FH_ROWPF_KMAX, true) + FH_FAST_WAVES * FH_ROWPF_WAVE <= 160 * 1024,
+              "row prefetch buffers exceed 160 KiB");
+static_assert(FH_ROWPF_KMAX <= FH_GATH_KMAX, "the FAST single-pass form runs where the gather ring would (fused.hip)");
+
+// The same from a scalar base: each lane's 16 B at sbase + voff (an unsigned
+// 32-bit byte offset) land at lds_base + lds_off + 16 * lane. lds_off is an
+// immediate added into M0 here: eight hoisted base + offset values, one per
+// piece, cost eight scalar registers across the whole loop.
+__device__ inline void glds16s(const void* sbase, uint32_t voff, uint32_t lds_base, int lds_off) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_add_u32 m0, %3, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_base), "n"(lds_off) : "memory", "scc");
+}
+
 // ROWS = 0: fp32 rows of 128 dims (X); 1: fp32 rows of d <= 128 dims; 2: fp64
 // rows of d <= 128 dims (X64) -- euclidean Lloyd without hashing, one pass.
 // Dims d..127 are zero in the row and in the centroid images (the prep pads
@@ -230,7 +265,8 @@ __device__ inline void glds16(const void* gsrc, uint32_t lds_dst) {
 // compiled in (no fp64 chain state). Its f32 centroid rows are register loads:
 // through the gather ring (GATH) each 16-dim step waits on its DMA, and the
 // short f32 sum cannot hide that (fused pass 2.21 vs 2.14 ms at C3).
-template <bool HASH, bool MP = false, int MET = 0, int NIMG = 1, bool GATH = false, int ROWS = 0, bool FAST = false>
+template <bool HASH, bool MP = false, int MET = 0, int NIMG = 1, bool GATH = false, int ROWS = 0, bool FAST = false,
+          int PF = 0>
 __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fused_hi_kernel(FusedArgs a) {
     constexpr int FH_WAVES = fh_waves<HASH, MP, MET, FAST>();
     constexpr int FH_THREADS = 64 * FH_WAVES;
@@ -240,6 +276,8 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
     // the gather's explicit vmcnt waits assume no other vector loads in the chain
     static_assert(!(GATH && ROWS == 2), "fp64 rows re-read x in the chain: register loads of the winner rows");
     static_assert(!FAST || (MET == 0 && ROWS != 2 && NIMG == 1 && !GATH), "fast distance: euclidean, fp32 rows");
+    static_assert(PF == 0 || (FAST && !MP && ROWS == 0 && FH_WAVES == FH_FAST_WAVES), "row prefetch: the FAST single-pass form");
+    constexpr bool PFR = (PF & 1) != 0, PFL = (PF & 2) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int Kpad = a.Kpad;
     const bool fastd = FAST || a.fast_dist != 0;
@@ -296,7 +334,12 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
     }
     __syncthreads();
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // PF: the wave index as a scalar, so the tile index and "this wave has a next
+    // tile" are uniform to the compiler: its two cases are then the arms of one
+    // scalar branch, and no path exists that issues neither arm's loads (with
+    // exec-masked arms the join assumed one, and waited the prefetch out).
+    const int lane = threadIdx.x & 63;
+    const int wave = PF != 0 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
     const int col = lane & 31, h = lane >> 5;
     const float cmaxf = a.cbound[3], crf = a.cbound[4], chf = a.cbound[5], cnf = a.cbound[6];
     const bool c_ok = __float_as_uint(a.cbound[2]) == 0u;
@@ -317,12 +360,127 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
         if constexpr (ROWS != 0) load_row_gen<ROWS>(a, rc, h, dst);
         else load_row_b(a.X + rc * FU_D + 8 * h, dst);
     };
+    // half hf (dims 64 hf .. + 63) of load_row: 8 loads of 16 B
+    auto load_half = [&](int64_t tl, int hf, float* dst) {
+        const int64_t rr = tl * 32 + col, rc = rr < a.N ? rr : a.N - 1;
+        const float* xr = a.X + rc * FU_D + 64 * hf + 8 * h;
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const float4 p0 = *reinterpret_cast<const float4*>(xr + 16 * s);
+            const float4 p1 = *reinterpret_cast<const float4*>(xr + 16 * s + 4);
+            dst[8 * s + 0] = p0.x; dst[8 * s + 1] = p0.y; dst[8 * s + 2] = p0.z; dst[8 * s + 3] = p0.w;
+            dst[8 * s + 4] = p1.x; dst[8 * s + 5] = p1.y; dst[8 * s + 6] = p1.z; dst[8 * s + 7] = p1.w;
+        }
+    };
+    // the lower halves of tile tl's rows into this wave's buffer: piece u holds
+    // rows 4u..4u+3, lane L position L & 15 of row p = 4u + (L >> 4), that is
+    // chunk (L & 15) ^ (p & 15) of the row (clamped to N - 1 as load_row's)
+    uint32_t pfbase = 0;
+    if constexpr (PFL)
+        pfbase = (uint32_t)__builtin_amdgcn_readfirstlane(
+            (int)((uint32_t)(uintptr_t)(smem + fh_rowpf_off(Kpad, HASH)) + (uint32_t)wave * FH_ROWPF_WAVE));
+    // The tile's first row is a scalar base (tl is the same in every lane), the
+    // lane's part a 32-bit offset: no 64-bit address registers per piece.
+    auto pf_dma = [&](int64_t tl) {
+        const int64_t tls = ((int64_t)__builtin_amdgcn_readfirstlane((int)(tl >> 32)) << 32) |
+                            (uint32_t)__builtin_amdgcn_readfirstlane((int)tl);
+        const int64_t left = a.N - 1 - tls * 32;             // >= 0: tl < ntiles
+        const int pmax = left < 31 ? (int)left : 31;
+        const float* xt = a.X + tls * 32 * FU_D;
+        if (pmax == 31) {
+            // every row of the tile exists (a scalar test). With q = L >> 4 (< 4), c =
+            // L & 15: p & 15 = 4 (u & 3) | q, so piece u's lane offset is
+            // u * 2048 + (w0 ^ 64 (u & 3)), w0 = 512 q + 16 (c ^ q) the same for every
+            // tile (the xor touches bits 6..7, 512 q bits 9..10): one VALU instruction
+            // per piece, the piece's rows on the scalar base.
+            const uint32_t w0 = (uint32_t)((lane >> 4) * (FU_D * 4) + 16 * ((lane & 15) ^ (lane >> 4)));
+#pragma unroll
+            for (int u = 0; u < 8; u++) glds16s(xt + u * 4 * FU_D, w0 ^ (uint32_t)(64 * (u & 3)), pfbase, u * 1024);
+        } else {
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int p = 4 * u + (lane >> 4), pc = p < pmax ? p : pmax;
+                glds16s(xt, (uint32_t)(pc * (FU_D * 4) + 16 * ((lane & 15) ^ (p & 15))), pfbase, u * 1024);
+            }
+        }
+    };
+    // The next tile's fetch, issued between the hash phase and the centroid tiles
+    // (both halves: the centroid loop leaves 32 registers free beside xf and bh).
+    // WAR: the DMA refills the buffer only once this tile's reads of it have
+    // returned (lgkmcnt(0), as ring_advance). Over-waiting: the issue sits behind
+    // the last wait on the row registers -- a compiler wait for an older load
+    // would not count the DMA and so wait it out too.
+    float xn[32];                             // PFR: the upper halves of the wave's next tile
+    auto pf_next = [&](int64_t tl) {
+        if constexpr (PF != 0) {
+            if (tl + tstride < ntiles) {
+                if constexpr (PFL) {
+                    __builtin_amdgcn_s_waitcnt(0xC07F);                    // lgkmcnt(0)
+                    asm volatile("" ::: "memory");
+                    pf_dma(tl + tstride);
+                }
+                if constexpr (PFR) load_half(tl + tstride, 1, xn);
+            } else if constexpr (PFR) {       // the wave's last tile fetches nothing
+#pragma unroll
+                for (int j = 0; j < 32; j++) xn[j] = 0.f;
+            }
+        }
+    };
+    // Prologue: the wave's first tile both ways, waited out here (vmcnt(0), once
+    // per wave), so that at every loop top the fetch is either complete or has
+    // the winner distance's 16 centroid loads behind it (the top's wait below).
+    if constexpr (PF != 0) {
+        if (tfirst + wave < ntiles) {
+            if constexpr (PFL) pf_dma(tfirst + wave);
+            if constexpr (PFR) load_half(tfirst + wave, 1, xn);
+            if constexpr (PFL) {
+                __builtin_amdgcn_s_waitcnt(0x0F70);                        // vmcnt(0)
+                asm volatile("" ::: "memory");
+            }
+        }
+    }
     PT_DECL
     for (int64_t tile = tfirst + wave; NIMG == 2 ? rd < nround : tile < ntiles; tile += tstride, rd++) {
         const int64_t row = tile * 32 + col;
         const bool valid = row < a.N;
         float xf[64];
-        load_row(tile, xf);
+        if constexpr (PF == 0) {
+            load_row(tile, xf);
+        } else {
+            if constexpr (PFL) {
+                if constexpr (!PFR) {
+                    load_half(tile, 1, xf + 32);
+                    asm volatile("" ::: "memory");            // the 8 loads stay above the wait that counts them
+                }
+                // RAW: only this wave's covering vmcnt wait orders the reads behind the
+                // tile's DMA. vmcnt(n) waits for all but the n youngest vector-memory
+                // operations, so n may only be a lower bound, on every path from the
+                // DMA's issue to here, of those issued after it:
+                //  - from the prologue: none, and the prologue has waited the DMA out;
+                //  - from pf_next a tile ago: the 16 centroid-row loads of the winner
+                //    distance (fastd is compiled in: unconditional, 16 instructions of
+                //    16 B); rn32's load, the stores and the list appends are conditional
+                //    or may be moved, and are not counted;
+                //  - without the register half, the 8 loads just issued above instead.
+                // vmcnt(16) therefore leaves this tile's own stores in flight and waits
+                // for nothing younger than the centroid rows, which the distance has
+                // consumed: the wait is a guard, not a stall.
+                __builtin_amdgcn_s_waitcnt(PFR ? 0x4F70 : 0x0F78);                 // vmcnt(16) : vmcnt(8)
+                asm volatile("" ::: "memory");
+                const char* pb = smem + fh_rowpf_off(Kpad, HASH) + wave * FH_ROWPF_WAVE + col * 256;
+#pragma unroll
+                for (int c = 0; c < 8; c++) {
+                    const float4 v = *reinterpret_cast<const float4*>(pb + 16 * ((4 * (c >> 1) + 2 * h + (c & 1)) ^ (col & 15)));
+                    xf[4 * c] = v.x; xf[4 * c + 1] = v.y; xf[4 * c + 2] = v.z; xf[4 * c + 3] = v.w;
+                }
+            } else {
+                load_half(tile, 0, xf);
+            }
+            if constexpr (PFR) {
+#pragma unroll
+                for (int j = 0; j < 32; j++) xf[32 + j] = xn[j];
+            }
+        }
         half8 bh[8];
         float2v n2a = {0.f, 0.f}, n2b = {0.f, 0.f}, r2 = {0.f, 0.f};
         double xn2, nx, nxr, nxh;
@@ -347,6 +505,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
                 half8 unused;
                 split_norm_step<false>(xf + 8 * s, bh[s], unused, n2a, n2b, r2);
             }
+            pf_next(tile);
             finish_norms();
         }
 
@@ -435,6 +594,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
             }
         }
 
+        if (HASH) pf_next(tile);
         PT_MARK(0)
         // the certificate's bound E depends on the row only: formed before the
         // centroid tiles (its fp64 ops overlap the MFMAs). cosine: + 2^-43 |x| for the normalisation and the reference's own q
@@ -618,10 +778,27 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
             if (fastd) {
                 const float* c32 = a.C32 + (size_t)I1 * FU_D + 8 * h;
                 float2v q[4] = {};
+                // PF: the 16 loads issued together, as the form without the prefetch has
+                // them (with xn live the scheduler otherwise takes them two at a time,
+                // eight L2 round trips in a row)
+                float4 cc[16];
+                if constexpr (PF != 0) {
+#pragma unroll
+                    for (int s = 0; s < 8; s++) {
+                        cc[2 * s] = *reinterpret_cast<const float4*>(c32 + 16 * s);
+                        cc[2 * s + 1] = *reinterpret_cast<const float4*>(c32 + 16 * s + 4);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
 #pragma unroll
                 for (int s = 0; s < 8; s++) {
-                    const float4 c0 = *reinterpret_cast<const float4*>(c32 + 16 * s);
-                    const float4 c1 = *reinterpret_cast<const float4*>(c32 + 16 * s + 4);
+                    float4 c0, c1;
+                    if constexpr (PF != 0) {
+                        c0 = cc[2 * s]; c1 = cc[2 * s + 1];
+                    } else {
+                        c0 = *reinterpret_cast<const float4*>(c32 + 16 * s);
+                        c1 = *reinterpret_cast<const float4*>(c32 + 16 * s + 4);
+                    }
                     const float2v cv[4] = {{c0.x, c0.y}, {c0.z, c0.w}, {c1.x, c1.y}, {c1.z, c1.w}};
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
@@ -800,9 +977,9 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
     }
 }
 
-template <bool HASH, bool MP, int MET, int NIMG, bool GATH, int ROWS, bool FAST>
+template <bool HASH, bool MP, int MET, int NIMG, bool GATH, int ROWS, bool FAST, int PF>
 static void hi_launch(hipStream_t s, unsigned nblk, size_t lds, const FusedArgs& a) {
-    hipLaunchKernelGGL((fused_hi_kernel<HASH, MP, MET, NIMG, GATH, ROWS, FAST>), dim3(nblk),
+    hipLaunchKernelGGL((fused_hi_kernel<HASH, MP, MET, NIMG, GATH, ROWS, FAST, PF>), dim3(nblk),
                        dim3(64 * fh_waves<HASH, MP, MET, FAST>()), lds, s, a);
 }
 
@@ -825,16 +1002,26 @@ int launch_fused_hi_pass(hipStream_t s, unsigned nblk, const HiForm& f, FusedArg
             lds = off + PW_BYTES;
         }
     }
+    const int pf = f.rowpf ? FH_ROWPF : 0;
+    if (pf != 0 && !(f.fast && !f.mp && f.rows == 0 && !f.gath && a.Kpad <= FH_ROWPF_KMAX)) {
+        set_error("launch_fused_hi_pass: the row prefetch needs the fast single-pass form at K <= 256");
+        return -1;
+    }
+    // the waves' row buffers after the image
+    if (pf & 2) lds = (size_t)fh_rowpf_off(a.Kpad, f.hash) + FH_FAST_WAVES * FH_ROWPF_WAVE;
     const int nimg = f.two_image ? 2 : 1;
     // every instantiation the library builds, one line each
-#define HI_CASE(H, MP, MET, NIMG, GATH, ROWS, FAST)                                                         \
+#define HI_CASE_PF(H, MP, MET, NIMG, GATH, ROWS, FAST, PF)                                                  \
     if (f.hash == (bool)H && f.mp == (bool)MP && f.metric == MET && nimg == NIMG && f.gath == (bool)GATH && \
-        f.rows == ROWS && f.fast == (bool)FAST) {                                                           \
-        hi_launch<H, MP, MET, NIMG, GATH, ROWS, FAST>(s, nblk, lds, a);                                     \
+        f.rows == ROWS && f.fast == (bool)FAST && pf == PF) {                                               \
+        hi_launch<H, MP, MET, NIMG, GATH, ROWS, FAST, PF>(s, nblk, lds, a);                                 \
         return 0;                                                                                           \
     }
-    //      hash mp met nimg gath rows fast
-    HI_CASE(1, 0, 0, 1, 0, 0, 1)      // euclidean, fp32 d = 128, one pass: the certified f32 distance,
+#define HI_CASE(H, MP, MET, NIMG, GATH, ROWS, FAST) HI_CASE_PF(H, MP, MET, NIMG, GATH, ROWS, FAST, 0)
+    //      hash mp met nimg gath rows fast (rows fetched a tile ahead)
+    HI_CASE_PF(1, 0, 0, 1, 0, 0, 1, FH_ROWPF)   // euclidean, fp32 d = 128, one pass: the certified f32 distance
+    HI_CASE_PF(0, 0, 0, 1, 0, 0, 1, FH_ROWPF)   // with its rows fetched one tile ahead,
+    HI_CASE(1, 0, 0, 1, 0, 0, 1)      // or at the tile's top (the test build's LSHKM_ROW_PREFETCH=0),
     HI_CASE(0, 0, 0, 1, 0, 0, 1)
     HI_CASE(1, 0, 0, 1, 1, 0, 0)      // the exact chain through the gather ring,
     HI_CASE(0, 0, 0, 1, 1, 0, 0)
@@ -856,6 +1043,7 @@ int launch_fused_hi_pass(hipStream_t s, unsigned nblk, const HiForm& f, FusedArg
     HI_CASE(0, 0, 0, 1, 0, 2, 0)      // general rows: fp64 d <= 128
     HI_CASE(0, 0, 1, 1, 0, 2, 0)
 #undef HI_CASE
+#undef HI_CASE_PF
     set_error("launch_fused_hi_pass: no kernel was built for this form");
     return -1;
 }

@@ -67,6 +67,7 @@ struct HiForm {
     bool gath = false;       // winner rows through the LDS-DMA gather ring
     int rows = 0;            // 0: fp32 d = 128, 1: fp32 d <= 128, 2: fp64 d <= 128
     bool fast = false;       // the certified f32 winner distance compiled in
+    bool rowpf = false;      // the next tile's rows fetched one tile ahead (fast, one pass, fp32 d = 128)
 };
 int launch_fused_hi_pass(hipStream_t s, unsigned nblk, const HiForm& f, FusedArgs a);
 // One refinement pass over the rows of a.list_in; a.Kpad <= FP_KMAX centroids.
