@@ -10,6 +10,7 @@
 #include "common.h"
 #include "index.h"
 #include "kernels.h"
+#include "lshpc_layout.h"
 
 using namespace lshkm;
 
@@ -95,6 +96,162 @@ int lshkm_top_n_recom(lshkm_ctx ctx, const double* X, const double* x_mean, int6
 }
 
 }  // extern "C"
+
+template <typename T> static T* at(const Buf& b, size_t off) { return reinterpret_cast<T*>(b.as<char>() + off); }
+
+// ------------------------------------ LSH recommender: P closest from the index
+// lshkm_lsh_p_closest. lshpc_layout.h states the routing rule and every
+// workspace; lsh_closest.hip is the screen.
+//
+// The lists path: lshkm_lsh_query_f64(filtered) -> the exclusion ->
+// get_P_closest on the users of `list` (ascending), gathered, in chunks whose
+// candidate lists fit cand_cap rows; the results scattered to the users' slots.
+static int lshpc_lists(lshkm_lsh lsh, const double* X, const double* U, const std::vector<int32_t>& list,
+                       int32_t excl_lo, int32_t excl_hi, int P, int64_t cand_cap, int32_t* out_idx, double* out_sim,
+                       int32_t* out_cnt, int64_t* ncand) {
+    lshkm_ctx ctx = lsh->ctx;
+    hipStream_t s = ctx->stream;
+    const int64_t m_all = (int64_t)list.size(), N = lsh->N;
+    const int d = lsh->proj.d, L = lsh->proj.L, k = lsh->proj.k;
+    if (m_all == 0) return 0;
+    // first guess from the mean bucket load, as lshkm_lsh_validate10's; a chunk
+    // whose lists come out larger is cut down below
+    const int64_t buckets = lsh->metric == LSHKM_METRIC_EUCLIDEAN ? std::max<int64_t>(lsh->nb, 1)
+                                                                  : (int64_t)1 << std::min(k, 40);
+    int64_t chunk = std::max<int64_t>(
+        1, std::min<int64_t>(m_all, cand_cap / std::max<int64_t>(1, (int64_t)L * (N / buckets + 1))));
+    Buf &bu = ctx->ws_lshpc[4], &bq = ctx->ws_lshpc[5], &be = ctx->ws_lshpc[6];
+    int rc;
+    for (int64_t i0 = 0; i0 < m_all;) {
+        const int64_t n = std::min(m_all - i0, chunk);
+        // Ug | qptr | eptr | scr (int64) | gsim | list | ra | rb | gcnt | gidx
+        const size_t oUg = 0, oq = oUg + lshpc_round256(8 * (size_t)n * d), oe = oq + lshpc_round256(8 * (size_t)(n + 1)),
+                     osc = oe + lshpc_round256(8 * (size_t)(n + 1)), ogs = osc + lshpc_round256(8 * (size_t)n),
+                     oli = ogs + lshpc_round256(8 * (size_t)n * P), ora = oli + lshpc_round256(4 * (size_t)n),
+                     orb = ora + lshpc_round256(4 * (size_t)n), ogc = orb + lshpc_round256(4 * (size_t)n),
+                     ogi = ogc + lshpc_round256(4 * (size_t)n), bytes = ogi + lshpc_round256(4 * (size_t)n * P);
+        if ((rc = bu.reserve(bytes))) return rc;
+        double* Ug = at<double>(bu, oUg);
+        int64_t *qptr = at<int64_t>(bu, oq), *eptr = at<int64_t>(bu, oe);
+        int32_t* dlist = at<int32_t>(bu, oli);
+        const H2D up{dlist, list.data() + i0, 4 * (size_t)n};
+        if ((rc = h2d_batch(ctx, &up, 1)) || (rc = launch_lshpc_gather(s, U, d, dlist, n, Ug))) return rc;
+        int64_t total = 0;
+        if ((rc = lshkm_lsh_query_f64(lsh, Ug, n, nullptr, 1, qptr, nullptr, 0, &total))) return rc;
+        if (total > cand_cap && n > 1) {                 // size the chunk by this one's lists and ask again
+            chunk = std::max<int64_t>(1, (int64_t)((double)n * (double)cand_cap / (double)total));
+            continue;
+        }
+        const size_t T = (size_t)std::max<int64_t>(total, 1);
+        if ((rc = bq.reserve(4 * T)) || (rc = be.reserve(4 * T))) return rc;
+        if ((rc = lshkm_lsh_query_f64(lsh, Ug, n, nullptr, 1, qptr, bq.as<int32_t>(), total, &total))) return rc;
+        if ((rc = launch_cv_exclude(s, qptr, bq.as<int32_t>(), n, excl_lo, excl_hi, at<int64_t>(bu, osc),
+                                    at<int32_t>(bu, ora), at<int32_t>(bu, orb), eptr, be.as<int32_t>())))
+            return rc;
+        if ((rc = p_closest_launch(ctx, X, N, d, Ug, n, eptr, be.as<int32_t>(), total, P, at<int32_t>(bu, ogi),
+                                   at<double>(bu, ogs), at<int32_t>(bu, ogc))))
+            return rc;
+        if ((rc = launch_lshpc_scatter(s, dlist, n, P, at<int32_t>(bu, ogi), at<double>(bu, ogs), at<int32_t>(bu, ogc),
+                                       eptr, out_idx, out_sim, out_cnt, ncand)))
+            return rc;
+        i0 += n;
+    }
+    return 0;
+}
+
+extern "C" int lshkm_lsh_p_closest(lshkm_lsh lsh, const double* X, const double* U, int64_t nq, int32_t excl_lo,
+                                   int32_t excl_hi, int P, int32_t* out_idx, double* out_sim, int32_t* out_cnt,
+                                   int64_t* ncand) {
+    LSHKM_CHECK(lsh && lsh->built, LSHKM_ERR_STATE, "index not built (lshkm_lsh_build)");
+    LSHKM_CHECK(nq >= 0 && nq < (1ll << 31) && P >= 1 && excl_lo <= excl_hi, LSHKM_ERR_ARG,
+                "bad arguments (P >= 1, excl_lo <= excl_hi)");
+    if (nq == 0) return 0;
+    LSHKM_CHECK(U && out_idx && out_sim && out_cnt && (X || lsh->N == 0), LSHKM_ERR_ARG, "bad arguments");
+    lshkm_ctx ctx = lsh->ctx;
+    LSHKM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int64_t N = lsh->N;
+    const int d = lsh->proj.d, L = lsh->proj.L, k = lsh->proj.k;
+    const bool small_cap = test_switch("LSHKM_LSHPC_CAP", "small");
+    const int64_t cand_cap = small_cap ? (int64_t)1 << 16 : LSHPC_CAND_CAP;
+    unsigned long long* stats = (unsigned long long*)ctx->stats.p;
+    int rc = 0;
+    const StreamSyncOnExit sync_guard{s, &rc};           // a failed call leaves nothing running
+
+    std::vector<int32_t> handed;
+    if (lshpc_route(lsh->metric == LSHKM_METRIC_COSINE, d, L, k, P,
+                    N == 0 || test_switch("LSHKM_LSHPC_PATH", "lists")) == LshpcRoute::lists) {
+        handed.resize((size_t)nq);
+        for (int64_t q = 0; q < nq; q++) handed[q] = (int32_t)q;
+    } else {
+        int ncu = 0;
+        if ((rc = device_cu_count(&ncu))) return rc;
+        const LshpcPlan plan = lshpc_plan(N, nq, P, ncu, small_cap);
+        const int dp = lshpc_dp(d);
+        const LshpcImage ix = lshpc_image(N, dp, 0), iu = lshpc_image(nq, dp, L);
+        const LshpcChunk cmax = lshpc_chunk(plan.chunk, plan.cap, plan.segs);
+        Buf &bx = ctx->ws_lshpc[0], &bu = ctx->ws_lshpc[1], &bc = ctx->ws_lshpc[2], &bh = ctx->ws_lshpc[3];
+        if ((rc = bx.reserve(ix.bytes)) || (rc = bu.reserve(iu.bytes)) || (rc = bc.reserve(cmax.bytes)) ||
+            (rc = bh.reserve(256 + 4 * (size_t)nq)))
+            return rc;
+        const LshpcSide rows{at<float>(bx, ix.xh), at<uint32_t>(bx, ix.code), at<float>(bx, ix.inv),
+                             at<float>(bx, ix.rel), N};
+        const LshpcSide users{at<float>(bu, iu.xh), at<uint32_t>(bu, iu.code), at<float>(bu, iu.inv),
+                              at<float>(bu, iu.rel), nq};
+        double* xa = at<double>(bx, ix.xa);
+        int32_t* ubucket = at<int32_t>(bu, iu.bucket);
+        unsigned int* handed_count = bh.as<unsigned int>();
+        int32_t* handed_dev = at<int32_t>(bh, 256);
+        // one pass over X and one over U: the reference's sums of squares, the
+        // users' bucket IDs, the f32 images
+        if ((rc = launch_rc_norms(s, X, N, d, xa)) ||
+            (rc = launch_lshpc_prep(s, X, N, d, dp, xa, lsh->bucket.as<int32_t>(), L, k, rows)) ||
+            (rc = hash_rows(ctx, HM_LSH_COSINE, U, nq, lsh->proj, lsh->nb, nullptr, nullptr, ubucket, nullptr)) ||
+            (rc = launch_rc_norms(s, U, nq, d, at<double>(bu, iu.xa))) ||
+            (rc = launch_lshpc_prep(s, U, nq, d, dp, at<double>(bu, iu.xa), ubucket, L, k, users)))
+            return rc;
+        if (hipMemsetAsync(handed_count, 0, sizeof(unsigned int), s) != hipSuccess) {
+            set_error("lshkm_lsh_p_closest: hipMemsetAsync failed");
+            return rc = LSHKM_ERR_HIP;
+        }
+        for (int64_t u0 = 0; u0 < nq; u0 += plan.chunk) {
+            const int64_t n = std::min(plan.chunk, nq - u0);
+            const LshpcChunk c = lshpc_chunk(n, plan.cap, plan.segs);
+            const LshpcKept kept{at<float>(bc, c.klo), at<float>(bc, c.khi), at<int32_t>(bc, c.krow),
+                                 at<int32_t>(bc, c.state), c.np, plan.seg_rows, plan.cap, plan.segs};
+            const LshpcSide chunk_users{users.xh + (size_t)u0 * dp, users.code + u0, users.inv + u0, users.rel + u0, n};
+            unsigned int* replay_count = at<unsigned int>(bc, c.counts);
+            if ((rc = launch_lshpc_screen(s, dp, rows, chunk_users, excl_lo, excl_hi, P, L, k, kept)) ||
+                (rc = launch_lshpc_join(s, kept, n, P, at<int64_t>(bc, c.nkept), ncand ? ncand + u0 : nullptr,
+                                        at<int64_t>(bc, c.cptr), at<int32_t>(bc, c.cidx), stats)) ||
+                // the exact top-(P+1) over the kept rows; its replay list (a NaN,
+                // or a tie in the first P+1) is returned, not replayed: Lomuto's
+                // order depends on the whole list, which only the lists path has
+                (rc = launch_rc_p_closest(s, X, xa, d, U + (size_t)u0 * d, n, at<int64_t>(bc, c.cptr),
+                                          at<int32_t>(bc, c.cidx), P, at<double>(bc, c.sim), at<double>(bc, c.key),
+                                          nullptr, out_idx + (size_t)u0 * P, out_sim + (size_t)u0 * P, out_cnt + u0,
+                                          at<int32_t>(bc, c.replay), replay_count, false)) ||
+                (rc = launch_lshpc_collect(s, kept, n, u0, at<int32_t>(bc, c.replay), replay_count, handed_dev,
+                                           handed_count)))
+                return rc;
+        }
+        unsigned int nh = 0;
+        const D2H rd{&nh, handed_count, sizeof(nh)};
+        if ((rc = d2h_batch(ctx, &rd, 1))) return rc;
+        handed.resize(nh);
+        const D2H rl{handed.data(), handed_dev, 4 * (size_t)nh};
+        if (nh && (rc = d2h_batch(ctx, &rl, 1))) return rc;
+        std::sort(handed.begin(), handed.end());
+    }
+    if ((rc = launch_lshpc_stats(s, stats, nq - (int64_t)handed.size(), (int64_t)handed.size())) ||
+        (rc = lshpc_lists(lsh, X, U, handed, excl_lo, excl_hi, P, cand_cap, out_idx, out_sim, out_cnt, ncand)))
+        return rc;
+    if (hipStreamSynchronize(s) != hipSuccess) {             // the workspace is reused by the next call
+        set_error("lshkm_lsh_p_closest: hipStreamSynchronize failed");
+        return LSHKM_ERR_HIP;
+    }
+    return 0;
+}
 
 // ------------------------------------------------ clustering recommender
 // get_top_N_recom(neighbors, user, N), crypto_rec.hpp:327-345, over whole
@@ -195,7 +352,6 @@ struct RecomRequest {
     int32_t* out;
 };
 template <typename T> static T* read_only(const T* p) { return const_cast<T*>(p); }
-template <typename T> static T* at(const Buf& b, size_t off) { return reinterpret_cast<T*>(b.as<char>() + off); }
 
 // Phase 1 of the terms form: the offsets up, then, when the caller's arrays
 // hold them, every similarity and term of this shard.

@@ -97,6 +97,9 @@ struct lshkm_ctx_s {
     // workspaces of the entry points that synchronise their stream before
     // returning (kmeans_pp, p_closest, top_n_recom): reused across calls
     lshkm::Buf ws_call[10];
+    // lshkm_lsh_p_closest (lshpc_layout.h): the pool's image, the users' image,
+    // the chunk, the handed-back list, the lists path's users and its two lists
+    lshkm::Buf ws_lshpc[7];
     uint64_t ws_epoch = 0;       // bumped by every user of the ws[] slots (api_index.cpp reserve)
     // optional HIP-event timing of the dominant kernel launch (lshkm_last_kernel_ms)
     bool timing = false;

@@ -342,7 +342,7 @@ int launch_rc_shard_chain(hipStream_t s, const RecomJob& j, const int64_t* soff,
 int launch_rc_p_closest(hipStream_t s, const double* X, const double* xa, int d, const double* U, int64_t nq,
                         const int64_t* cand_ptr, const int32_t* cand_idx, int P, double* sim, double* key,
                         int32_t* pos, int32_t* out_idx, double* out_sim, int32_t* out_cnt, int32_t* replay,
-                        unsigned int* replay_count);
+                        unsigned int* replay_count, bool replay_pass = true);
 int launch_rc_top_n(hipStream_t s, const double* X, const double* x_mean, int d, const double* u_mean, int64_t nq,
                     const int64_t* unk_ptr, const int32_t* unk_idx, const int32_t* nb_idx, const double* nb_sim,
                     const int32_t* nb_cnt, int P, int n_top, double* pred, int32_t* pidx, int32_t* out);
@@ -425,6 +425,41 @@ int launch_pam_select(hipStream_t s, const int32_t* rows, const int32_t* cand, c
                       const double* sums, int32_t* med, double* csum);
 // C_new[c] = row med[c] widened to fp64, or C_old[c] for an empty cluster.
 int launch_pam_gather(hipStream_t s, Pts X, int d, const int32_t* med, int K, const double* C_old, double* C_new);
+
+// lshkm_lsh_p_closest's screen (lsh_closest.hip; lshpc_layout.h states the
+// routing rule and the workspaces). One side's f32 image: x^ [n][dp], the
+// packed bucket codes, 1 / |x^| (negative: poison), the bound's conversion term.
+struct LshpcSide {
+    const float* xh;
+    const uint32_t* code;
+    const float* inv;
+    const float* rel;
+    int64_t n;
+};
+// The kept-lists of one chunk of users: (lo, hi, row) [segs][np][cap] and the
+// states [4][segs][np] (count, candidates seen, T's bits, flag).
+struct LshpcKept {
+    float *klo, *khi;
+    int32_t *krow, *state;
+    int64_t np, seg_rows;
+    int cap, segs;
+};
+int launch_lshpc_prep(hipStream_t s, const double* X, int64_t n, int d, int dp, const double* xa, const int32_t* bucket,
+                      int L, int k, const LshpcSide& out);
+int launch_lshpc_screen(hipStream_t s, int dp, const LshpcSide& rows, const LshpcSide& users, int32_t excl_lo,
+                        int32_t excl_hi, int P, int L, int k, const LshpcKept& kept);
+// The segments joined: nkept [n], ncand [n] (or NULL), cptr [n + 1] = scan of
+// nkept, cidx = the unflagged users' kept rows, ascending; stats 14 / 15.
+int launch_lshpc_join(hipStream_t s, const LshpcKept& kept, int64_t n, int P, int64_t* nkept, int64_t* ncand,
+                      int64_t* cptr, int32_t* cidx, unsigned long long* stats);
+// handed += u0 + the chunk's flagged users and the settle's replay list.
+int launch_lshpc_collect(hipStream_t s, const LshpcKept& kept, int64_t n, int64_t u0, const int32_t* replay,
+                         const unsigned int* replay_count, int32_t* handed, unsigned int* handed_count);
+int launch_lshpc_stats(hipStream_t s, unsigned long long* stats, int64_t settled, int64_t lists);
+int launch_lshpc_gather(hipStream_t s, const double* U, int d, const int32_t* list, int64_t m, double* Ug);
+int launch_lshpc_scatter(hipStream_t s, const int32_t* list, int64_t m, int P, const int32_t* gidx, const double* gsim,
+                         const int32_t* gcnt, const int64_t* eptr, int32_t* out_idx, double* out_sim, int32_t* out_cnt,
+                         int64_t* ncand);
 
 // Synthetic data.
 int launch_synth(hipStream_t s, uint64_t seed, int64_t row0, int64_t rows, int d, float* X, int kind = 0);

@@ -42,8 +42,25 @@ __device__ inline double rc_cos_sim(const double* __restrict__ x, const double* 
                                     double ub) {
     X87acc ip;
     ip.init();
-    for (int j = 0; j < d; j++) ip.add(__dmul_rn(x[j], u[j]));
-    return x87_quot(ip.value(), __dmul_rn(sqrt(xa), sqrt(ub)));
+    const double denom = __dmul_rn(sqrt(xa), sqrt(ub));
+    // Infinite products or norms (an inf entry, a row whose squares overflow)
+    // are outside the soft chain: the x87's results for special operands, the
+    // default NaN being its "real indefinite" (sign set). inf: 1 = +, 2 = -.
+    int inf = 0;
+    bool nan = false;
+    for (int j = 0; j < d; j++) {
+        const double p = __dmul_rn(x[j], u[j]);
+        if (fabs(p) < __builtin_inf()) ip.add(p);
+        else if (p != p) nan = true;
+        else inf |= p > 0.0 ? 1 : 2;
+    }
+    if (inf || nan || !(denom < __builtin_inf())) {
+        const double indefinite = __longlong_as_double((long long)0xFFF8000000000000ull);
+        if (nan || inf == 3 || denom != denom) return indefinite;
+        if (inf) return denom == __builtin_inf() ? indefinite : inf == 1 ? __builtin_inf() : -__builtin_inf();
+        return ip.value().s ? -0.0 : 0.0;                  // finite / inf
+    }
+    return x87_quot(ip.value(), denom);
 }
 
 __device__ inline double rc_sumsq(const double* __restrict__ x, int d) {
@@ -1457,13 +1474,14 @@ int launch_rc_norms(hipStream_t s, const double* X, int64_t N, int d, double* xa
 int launch_rc_p_closest(hipStream_t s, const double* X, const double* xa, int d, const double* U, int64_t nq,
                         const int64_t* cand_ptr, const int32_t* cand_idx, int P, double* sim, double* key,
                         int32_t* pos, int32_t* out_idx, double* out_sim, int32_t* out_cnt, int32_t* replay,
-                        unsigned int* replay_count) {
+                        unsigned int* replay_count, bool replay_pass) {
     if (nq <= 0) return 0;
     if (hipMemsetAsync(replay_count, 0, sizeof(unsigned int), s) != hipSuccess) return kstatus("recom.hip");
     hipLaunchKernelGGL(rc_p_closest_kernel, dim3(gsz(nq, RC_WAVES, 8192)), dim3(64 * RC_WAVES), 0, s, X, xa, d, U, nq,
                        cand_ptr, cand_idx, P, sim, key, out_idx, out_sim, out_cnt, replay, replay_count);
-    hipLaunchKernelGGL(rc_replay_kernel, dim3(gsz(nq, 64, 1024)), dim3(64), 0, s, cand_ptr, cand_idx, P, sim, key, pos,
-                       replay, replay_count, out_idx, out_sim);
+    if (replay_pass)
+        hipLaunchKernelGGL(rc_replay_kernel, dim3(gsz(nq, 64, 1024)), dim3(64), 0, s, cand_ptr, cand_idx, P, sim, key, pos,
+                           replay, replay_count, out_idx, out_sim);
     return kstatus("recom.hip");
 }
 

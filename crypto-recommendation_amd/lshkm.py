@@ -24,6 +24,7 @@ STAT_HASH_EXACT, STAT_ASSIGN_AMBIG, STAT_COS_FIX, STAT_REFINED, STAT_HASH_FIX, S
 STAT_POW_FIX = 8
 STAT_KM_SEQ = 9
 STAT_PAM_SCREENED, STAT_PAM_EXACT = 10, 11
+STAT_LSHPC_SETTLED, STAT_LSHPC_LISTS, STAT_LSHPC_KEPT, STAT_LSHPC_SEEN = 12, 13, 14, 15
 _METRIC = {"euclidean": EUCLIDEAN, "cosine": COSINE, EUCLIDEAN: EUCLIDEAN, COSINE: COSINE}
 DIST_CERTIFIED, DIST_EXACT = 0, 1
 _DIST = {"certified": DIST_CERTIFIED, "default": DIST_CERTIFIED, "exact": DIST_EXACT,
@@ -133,6 +134,7 @@ def lib():
             "lshkm_kpp_shard_pick": (i32, [vp, i64, f64, i32, vp, i64, C.POINTER(i64)]),
             "lshkm_rand_selection": (i32, [u64, i64, i32, vp]),
             "lshkm_p_closest": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, i32, vp, vp, vp]),
+            "lshkm_lsh_p_closest": (i32, [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp]),
             "lshkm_top_n_recom": (i32, [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i32, i32, vp]),
             "lshkm_cluster_top_n": (i32, [vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, i32, vp]),
             "lshkm_cluster_sims": (i32, [vp, vp, i64, i32, vp, vp, i32, vp, i64, vp, vp, vp, vp, i64,
@@ -791,6 +793,33 @@ def top_n_recom(ctx, X, x_mean, u_mean, unk_ptr, unk_idx, nb_idx, nb_sim, nb_cnt
                                 _t_ptr(unk_idx) if unk_idx.numel() else None, _t_ptr(nb_idx), _t_ptr(nb_sim),
                                 _t_ptr(nb_cnt), P, n_top, _t_ptr(out)))
     return out
+
+
+def lsh_p_closest(ctx, lsh, X, U, P, exclude=None, counts=False):
+    """main.cpp:160-162 for all users of U at once (lshkm_lsh_p_closest): the
+    P closest of each user's LSH neighbours, straight from the built index lsh
+    over X. X [N][d], U [nq][d] fp64 device tensors; exclude = (lo, hi): rows
+    [lo, hi) are no one's neighbours. Returns (idx [nq][P] -1-padded, sim
+    [nq][P], cnt [nq]) as p_closest does, and with counts each user's
+    neighbour count (int64 [nq]) as a fourth."""
+    torch = ctx.torch
+    nq = U.shape[0]
+    lo, hi = (0, 0) if exclude is None else (int(exclude[0]), int(exclude[1]))
+    idx = ctx.empty((nq, P), torch.int32)
+    sim = ctx.empty((nq, P), torch.float64)
+    cnt = ctx.empty((nq,), torch.int32)
+    nc = ctx.empty((nq,), torch.int64) if counts else None
+    _ck(lib().lshkm_lsh_p_closest(lsh.h, _t_ptr(X), _t_ptr(U), nq, lo, hi, P, _t_ptr(idx), _t_ptr(sim), _t_ptr(cnt),
+                                  _t_ptr(nc)))
+    return (idx, sim, cnt, nc) if counts else (idx, sim, cnt)
+
+
+def lsh_recommend(ctx, lsh, X, x_mean, U, u_mean, unk_ptr, unk_idx, P, n_top):
+    """main.cpp:159-170 as one call: lsh_p_closest, then top_n_recom over its
+    lists. Returns (top [nq][n_top] int32, cnt [nq]); cnt == 0 marks the users
+    main.cpp:161 skips (no neighbours)."""
+    idx, sim, cnt = lsh_p_closest(ctx, lsh, X, U, P)
+    return top_n_recom(ctx, X, x_mean, u_mean, unk_ptr, unk_idx, idx, sim, cnt, n_top), cnt
 
 
 def cluster_top_n(ctx, X, x_mean, crow, crows, U, u_mean, ucl, unk_ptr, unk_idx, n_top):

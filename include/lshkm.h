@@ -131,7 +131,13 @@ int lshkm_memcpy_d2h(lshkm_ctx ctx, void* dst_host, const void* src_dev, int64_t
  * 9 = k-means (cluster, dim) sums of fp32 rows whose never-rounds test failed,
  *     i.e. that took a rounding-aware chain instead of plain fp64 adds,
  * 10 = PAM update: clusters whose argmin went through the MFMA screen,
- * 11 = PAM update: members of those clusters the screen left to the exact chain. */
+ * 11 = PAM update: members of those clusters the screen left to the exact chain,
+ * 12 = lshkm_lsh_p_closest: users the MFMA screen settled,
+ * 13 = lshkm_lsh_p_closest: users sent to the lists path (a poison row or user, a
+ *      kept-list overflow, a tie or a NaN among the first P + 1; every user of a
+ *      call the screen does not take),
+ * 14 = lshkm_lsh_p_closest: candidates the screen kept for the exact pass,
+ * 15 = lshkm_lsh_p_closest: candidates the screen saw. */
 int lshkm_get_stat(lshkm_ctx ctx, int which, int64_t* value_host);
 int lshkm_reset_stats(lshkm_ctx ctx);
 /* HIP-event timing of the dominant kernel launch (the fused hash+assign kernel)
@@ -524,6 +530,24 @@ int lshkm_rand_selection(uint64_t seed, int64_t N, int K, int32_t* rows_host);
 int lshkm_p_closest(lshkm_ctx ctx, const double* X_dev, int64_t N, int d, const double* U_dev, int64_t nq,
                     const int64_t* cand_ptr_dev, const int32_t* cand_idx_dev, int P, int32_t* out_idx_dev,
                     double* out_sim_dev, int32_t* out_cnt_dev);
+/* main.cpp:160-162 for nq users at once: get_LSH_filtered_combined_buckets
+ * (lsh_cube.hpp:93-106) followed by get_P_closest (crypto_rec.hpp:213-231),
+ * without the neighbour vectors. out_idx_dev / out_sim_dev / out_cnt_dev are bit
+ * for bit what lshkm_lsh_query_f64(filtered = 1, alias NULL) ->
+ * lshkm_cv_exclude(excl_lo, excl_hi) -> lshkm_p_closest produce, on any doubles
+ * (ties, NaNs, zero rows, empty neighbourhoods). X_dev [N][d]: the fp64 rows lsh
+ * was built over; U_dev [nq][d]; rows in [excl_lo, excl_hi) are no one's
+ * neighbours (merge_except_for; excl_lo == excl_hi: none). ncand_dev [nq] or
+ * NULL: each user's neighbour count. A cosine handle with d <= 128, L * k <= 32
+ * and P <= 447 goes through an f32 MFMA screen with a rigorous bound (DESIGN.md
+ * 5c) that leaves only the candidates near a user's P best to the exact chain and
+ * never writes a candidate list; everything else, and every user the screen
+ * cannot decide, runs the sequence above in chunks of bounded size. The handle
+ * must be built (LSHKM_ERR_STATE); P < 1 or excl_lo > excl_hi is LSHKM_ERR_ARG.
+ * nq < 2^31. Returns after its workspace is free for the next call. */
+int lshkm_lsh_p_closest(lshkm_lsh lsh, const double* X_dev, const double* U_dev, int64_t nq, int32_t excl_lo,
+                        int32_t excl_hi, int P, int32_t* out_idx_dev, double* out_sim_dev, int32_t* out_cnt_dev,
+                        int64_t* ncand_dev);
 /* get_top_N_recom (crypto_rec.hpp:305-325) over lshkm_p_closest's lists:
  * predicted scores of each user's unknown indexes (get_predicted_user_sim,
  * :280-302; unk_* = CSR of the ascending unknown indexes, std::set order),

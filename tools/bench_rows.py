@@ -6,7 +6,7 @@ syncs (host launch and sync latency included) -- next to the CPU restatement (or
 thread, OMP_NUM_THREADS=1, kind "port") on a bounded sample of the same
 workload, scaled to the row's unit. Prints one JSON line per row.
 
-    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64,cv] [--no-cpu]
+    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64,cv,lshpc] [--no-cpu]
 """
 import argparse
 import json
@@ -119,6 +119,7 @@ def main():
     ap.add_argument("--rows", default="cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cv-sizes", default="20000,1000000", help="user counts of the cv row")
+    ap.add_argument("--lshpc-sizes", default="20000,200000", help="user counts of the lshpc row")
     ap.add_argument("--pam-shapes", default="100000x16,1000000x256", help="NxK list of the pam row (d = 128)")
     a = ap.parse_args()
     rows = set(a.rows.split(","))
@@ -434,6 +435,65 @@ def main():
                  + ", ".join(f"{n} {v * 1e3:.2f}" for n, v in parts.items())
                  + f"; {cand} candidates after exclusion ({cand / F:.0f} per user); fold 0 sum equals the driver's: {same}")
             del X, W, H, lsh, ptr, idx, eptr, eidx
+
+    if "lshpc" in rows:      # main.cpp:160-162 from the index: the lists sequence against lshkm_lsh_p_closest
+        d, k, L, P = 100, 4, 5, 20
+        tsec, seeds = 1546300800, np.arange(1, 11, dtype=np.uint64)
+
+        def event_ms(fn, warm=3, reps=10):
+            """HIP events around single calls: (median, min, max) ms of reps after warm warm-ups."""
+            ms = []
+            for i in range(warm + reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                fn()
+                e1.record()
+                ctx.sync()
+                torch.cuda.synchronize()
+                if i >= warm:
+                    ms.append(e0.elapsed_time(e1))
+            return float(np.median(ms)), float(min(ms)), float(max(ms))
+        for N in (int(v) for v in a.lshpc_sizes.split(",")):
+            # the cv row's fold-0 inputs: the pool W in split order, fold 0's users hidden, excluded as rows [0, F)
+            xh, xmh, uph, uih = cv_users(N, d)
+            X, xm, up, ui = (torch.from_numpy(v).to(ctx.dev) for v in (xh, xmh, uph, uih))
+            F = N // 10
+            split = torch.from_numpy(lshkm.cv_split10(tsec, N).ravel().astype(np.int64)).to(ctx.dev)
+            draw = torch.full((N,), int(lshkm.cv_draws([tsec])[0, 0]), dtype=torch.int32, device=ctx.dev)
+            H, hm, hi, old = lshkm.cv_hide(ctx, X, xm, up, ui, draw)
+            W = X[split].contiguous()
+            W[:F] = H[split[:F]]
+            R, _ = lshkm.params_lsh_cosine(int(seeds[0]), L, k, d)
+            lsh = lshkm.LSH(ctx, "cosine", d, k, L, R=R)
+            lsh.build(W)
+            Q = W[:F].contiguous()
+            del X, H
+            out = {}
+
+            def sequence():
+                eptr, eidx = lshkm.cv_exclude(ctx, *lsh.query(Q, True, device=True), 0, F)
+                out["seq"] = lshkm.p_closest(ctx, W, Q, eptr, eidx, P)
+                out["cand"] = int(eptr[-1])
+
+            def direct():
+                out["new"] = lshkm.lsh_p_closest(ctx, lsh, W, Q, P, exclude=(0, F))
+            t_seq = event_ms(sequence)
+            ctx.reset_stats()
+            t_new = event_ms(direct)
+            st = [ctx.stat(i) // 13 for i in (12, 13, 14, 15)]
+            same = all(torch.equal(g, w) for g, w in zip((out["new"][0], out["new"][1].view(torch.int64), out["new"][2]),
+                                                         (out["seq"][0], out["seq"][1].view(torch.int64), out["seq"][2])))
+            print(json.dumps({
+                "row": "lshpc", "users": F, "pool": 10 * F, "d": d, "k": k, "L": L, "P": P,
+                "candidates": out["cand"], "sequence_ms": {"median": t_seq[0], "min": t_seq[1], "max": t_seq[2]},
+                "lsh_p_closest_ms": {"median": t_new[0], "min": t_new[1], "max": t_new[2]},
+                "speedup_median": t_seq[0] / t_new[0], "bar_new_max_below_sequence_min": t_new[2] < t_seq[1],
+                "stat_settled": st[0], "stat_lists": st[1], "stat_kept": st[2], "stat_seen": st[3],
+                "outputs_identical": same,
+                "note": "query + exclusion + p_closest against lshkm_lsh_p_closest on the same handle; HIP events, "
+                        "median of 10 after 3 warm-ups; stats per call"}), flush=True)
+            del W, Q, lsh, out
 
     if "csv" in rows:        # VectorReader (vector_reader.hpp:54-85)
         n, d = 200_000, 64
