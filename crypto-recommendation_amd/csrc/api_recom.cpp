@@ -186,7 +186,8 @@ extern "C" int lshkm_lsh_p_closest(lshkm_lsh lsh, const double* X, const double*
     } else {
         int ncu = 0;
         if ((rc = device_cu_count(&ncu))) return rc;
-        const LshpcPlan plan = lshpc_plan(N, nq, P, ncu, small_cap);
+        const size_t budget = test_switch("LSHKM_LSHPC_BUDGET", "small") ? (size_t)1 << 20 : LSHPC_BUDGET;
+        const LshpcPlan plan = lshpc_plan(N, nq, P, ncu, small_cap, budget);
         const int dp = lshpc_dp(d);
         const LshpcImage ix = lshpc_image(N, dp, 0), iu = lshpc_image(nq, dp, L);
         const LshpcChunk cmax = lshpc_chunk(plan.chunk, plan.cap, plan.segs);

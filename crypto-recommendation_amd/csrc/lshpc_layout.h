@@ -77,7 +77,9 @@ struct LshpcPlan {
 // segment, the segments' states (count, seen, T, flag), the settle's CSR
 // (cidx int32, sim and key double, per kept entry).
 inline size_t lshpc_user_bytes(int cap, int segs) { return (size_t)segs * ((size_t)cap * (12 + 4 + 16) + 16) + 64; }
-inline LshpcPlan lshpc_plan(int64_t N, int64_t nq, int P, int ncu, bool small_cap) {
+// budget: LSHPC_BUDGET, or the test build's LSHKM_LSHPC_BUDGET=small (1 MiB:
+// chunks of one user tile).
+inline LshpcPlan lshpc_plan(int64_t N, int64_t nq, int P, int ncu, bool small_cap, size_t budget = LSHPC_BUDGET) {
     LshpcPlan p;
     p.cap = lshpc_cap(P, small_cap);
     const int64_t tiles = (nq + LSHPC_COLS - 1) / LSHPC_COLS;
@@ -87,7 +89,7 @@ inline LshpcPlan lshpc_plan(int64_t N, int64_t nq, int P, int ncu, bool small_ca
     const int64_t per = (N + p.segs - 1) / p.segs;
     p.seg_rows = std::max<int64_t>(LSHPC_STAGE, (per + LSHPC_STAGE - 1) / LSHPC_STAGE * LSHPC_STAGE);
     p.segs = (int)std::max<int64_t>(1, (N + p.seg_rows - 1) / p.seg_rows);
-    const int64_t fit = (int64_t)(LSHPC_BUDGET / lshpc_user_bytes(p.cap, p.segs));
+    const int64_t fit = (int64_t)(budget / lshpc_user_bytes(p.cap, p.segs));
     p.chunk = std::max<int64_t>(LSHPC_COLS, fit / LSHPC_COLS * LSHPC_COLS);
     if (p.chunk > nq) p.chunk = nq;
     return p;

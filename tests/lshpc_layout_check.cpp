@@ -36,28 +36,49 @@ int main() {
         for (int64_t nq : nqs)
             for (int P : {1, 20, 100, 447})
                 for (int ncu : {0, 1, 256})
-                    for (int small = 0; small < 2; small++) {
-                        const LshpcPlan p = lshpc_plan(N, nq, P, ncu, small != 0);
-                        CHECK(p.segs >= 1 && p.segs <= LSHPC_SEG_MAX);
-                        CHECK(p.seg_rows % LSHPC_STAGE == 0 && p.seg_rows >= LSHPC_STAGE);
-                        CHECK((int64_t)p.segs * p.seg_rows >= N);                  // the segments cover the rows
-                        CHECK((int64_t)(p.segs - 1) * p.seg_rows < N);             // and none is empty
-                        CHECK(p.chunk >= 1 && p.chunk <= nq);
-                        CHECK(p.chunk == nq || p.chunk % LSHPC_COLS == 0);
-                        const LshpcChunk c = lshpc_chunk(p.chunk, p.cap, p.segs);
-                        CHECK(c.np >= p.chunk && c.np % LSHPC_COLS == 0 && c.np - p.chunk < LSHPC_COLS);
-                        const size_t e = (size_t)c.np * p.segs * p.cap;
-                        CHECK(c.khi >= c.klo + 4 * e && c.krow >= c.khi + 4 * e && c.state >= c.krow + 4 * e);
-                        CHECK(c.nkept >= c.state + 16 * (size_t)p.segs * c.np);
-                        CHECK(c.cptr >= c.nkept + 8 * (size_t)p.chunk && c.cidx >= c.cptr + 8 * (size_t)(p.chunk + 1));
-                        CHECK(c.sim >= c.cidx + 4 * e && c.key >= c.sim + 8 * e && c.replay >= c.key + 8 * e);
-                        CHECK(c.counts >= c.replay + 4 * (size_t)p.chunk && c.bytes >= c.counts + 16);
-                        CHECK(c.sim % 8 == 0 && c.key % 8 == 0 && c.nkept % 8 == 0 && c.cptr % 8 == 0);
-                        // the budget holds unless one tile of users alone exceeds it
-                        CHECK(c.bytes <= LSHPC_BUDGET + ((size_t)1 << 20) || p.chunk <= LSHPC_COLS);
-                        // a smaller last chunk fits the reservation made for the largest
-                        CHECK(lshpc_chunk(1, p.cap, p.segs).bytes <= c.bytes);
-                    }
+                    for (int small = 0; small < 2; small++)
+                        for (size_t budget : {(size_t)1 << 20, LSHPC_BUDGET}) {
+                            const LshpcPlan p = lshpc_plan(N, nq, P, ncu, small != 0, budget);
+                            if (budget == LSHPC_BUDGET) {        // the default parameter is the product's budget
+                                const LshpcPlan p0 = lshpc_plan(N, nq, P, ncu, small != 0);
+                                CHECK(p0.cap == p.cap && p0.segs == p.segs && p0.seg_rows == p.seg_rows);
+                                CHECK(p0.chunk == p.chunk);
+                            }
+                            CHECK(p.segs >= 1 && p.segs <= LSHPC_SEG_MAX);
+                            CHECK(p.seg_rows % LSHPC_STAGE == 0 && p.seg_rows >= LSHPC_STAGE);
+                            CHECK((int64_t)p.segs * p.seg_rows >= N);                  // the segments cover the rows
+                            CHECK((int64_t)(p.segs - 1) * p.seg_rows < N);             // and none is empty
+                            CHECK(p.chunk >= 1 && p.chunk <= nq);
+                            CHECK(p.chunk == nq || p.chunk % LSHPC_COLS == 0);
+                            const LshpcChunk c = lshpc_chunk(p.chunk, p.cap, p.segs);
+                            CHECK(c.np >= p.chunk && c.np % LSHPC_COLS == 0 && c.np - p.chunk < LSHPC_COLS);
+                            const size_t e = (size_t)c.np * p.segs * p.cap;
+                            CHECK(c.khi >= c.klo + 4 * e && c.krow >= c.khi + 4 * e && c.state >= c.krow + 4 * e);
+                            CHECK(c.nkept >= c.state + 16 * (size_t)p.segs * c.np);
+                            CHECK(c.cptr >= c.nkept + 8 * (size_t)p.chunk);
+                            CHECK(c.cidx >= c.cptr + 8 * (size_t)(p.chunk + 1));
+                            CHECK(c.sim >= c.cidx + 4 * e && c.key >= c.sim + 8 * e && c.replay >= c.key + 8 * e);
+                            CHECK(c.counts >= c.replay + 4 * (size_t)p.chunk && c.bytes >= c.counts + 16);
+                            CHECK(c.sim % 8 == 0 && c.key % 8 == 0 && c.nkept % 8 == 0 && c.cptr % 8 == 0);
+                            // the budget holds unless one tile of users alone exceeds it
+                            CHECK(c.bytes <= budget + ((size_t)1 << 20) || p.chunk <= LSHPC_COLS);
+                            // the chunks cover the users: whole chunks, then one smaller and not empty
+                            const int64_t nchunks = (nq + p.chunk - 1) / p.chunk, last = nq - (nchunks - 1) * p.chunk;
+                            CHECK(nchunks >= 1 && last >= 1 && last <= p.chunk && (nchunks - 1) * p.chunk + last == nq);
+                            // a smaller last chunk fits the reservation made for the largest
+                            CHECK(lshpc_chunk(last, p.cap, p.segs).bytes <= c.bytes);
+                            CHECK(lshpc_chunk(1, p.cap, p.segs).bytes <= c.bytes);
+                        }
+    // the test build's 1 MiB budget (LSHKM_LSHPC_BUDGET=small): the shapes of
+    // tests/test_gpu_lsh_closest_edges.py fall to one user tile per chunk
+    for (int ncu : {1, 64, 256, 304}) {
+        const size_t mib = (size_t)1 << 20;
+        CHECK(lshpc_plan(6000, 600, 20, ncu, false, mib).chunk == LSHPC_COLS);
+        CHECK(lshpc_plan(2000, 200, 15, ncu, false, mib).chunk == LSHPC_COLS);
+        CHECK(lshpc_plan(1061, 130, 20, ncu, false, mib).chunk == LSHPC_COLS);
+        CHECK(lshpc_plan(1061, 300, 20, ncu, false, mib).chunk == LSHPC_COLS);
+        CHECK(lshpc_plan(6000, 600, 20, ncu, false).chunk == 600);
+    }
     const LshpcImage im = lshpc_image(1061, 128, 5);
     CHECK(im.code >= 4 * (size_t)1061 * 128 && im.inv >= im.code + 4 * 1061 && im.rel >= im.inv + 4 * 1061);
     CHECK(im.xa >= im.rel + 4 * 1061 && im.xa % 8 == 0 && im.bucket >= im.xa + 8 * 1061);

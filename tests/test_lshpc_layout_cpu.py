@@ -1,7 +1,8 @@
 """csrc/lshpc_layout.h on the host: lshkm_lsh_p_closest's routing rule with its
 edges (d 128 / 129, L * k 32 / 33, P 447 / 448), the kept-list capacities, every
 plan's row segments (covering, none empty) and user chunks, and the chunk
-workspace's regions (in order, disjoint, aligned, within the budget)."""
+workspace's regions (in order, disjoint, aligned, within the budget), for the
+product's budget and the test build's 1 MiB (LSHKM_LSHPC_BUDGET=small)."""
 import os
 import subprocess
 
