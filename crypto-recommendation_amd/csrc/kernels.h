@@ -461,6 +461,31 @@ int launch_lshpc_scatter(hipStream_t s, const int32_t* list, int64_t m, int P, c
                          const int32_t* gcnt, const int64_t* eptr, int32_t* out_idx, double* out_sim, int32_t* out_cnt,
                          int64_t* ncand);
 
+// User vectors from scored tweets (uservec.hip). The visit list and the tweet
+// table of one lshkm_user_sums call: visit v = tweet tw[v] onto group grp[v]
+// (-1: skipped), tweet t's score and its coins ci_idx[ci_ptr[t] .. ci_ptr[t+1]).
+struct UvVisits {
+    const int32_t *tw, *grp;
+    int64_t V;
+    const double* score;
+    const int64_t* ci_ptr;
+    const int32_t* ci_idx;
+    int64_t T, G;
+    int C;
+};
+// *flag |= 1 (tw), 2 (grp), 8 (ci_ptr) with coins = false; 4 (ci_idx) with
+// coins = true, which reads ci_idx through ci_ptr and so runs after the first passed.
+int launch_uv_check(hipStream_t s, const UvVisits& q, bool coins, uint32_t* flag);
+int launch_uv_count(hipStream_t s, const UvVisits& q, int64_t* cnt);
+size_t uv_sort_bytes(int64_t E, int64_t nkeys);
+int launch_uv_sums(hipStream_t s, const UvVisits& q, const int64_t* off, int64_t E, const double* carry_sum,
+                   const uint8_t* carry_known, int32_t* keys, int32_t* vals, int32_t* keys_s, int32_t* vals_s,
+                   void* sort_ws, int64_t* row_ptr, int32_t* long_list, uint32_t* long_count, double* sum,
+                   uint8_t* known);
+int launch_uv_finish(hipStream_t s, const double* sum, const uint8_t* known, int64_t G, int C, int64_t* kept,
+                     int64_t* nunk, int64_t* row_off, int64_t* unk_off, double* mean, int64_t* scan_ws, double* U,
+                     double* mean_out, int64_t* unk_ptr, int32_t* unk_idx, int32_t* src);
+
 // Synthetic data.
 int launch_synth(hipStream_t s, uint64_t seed, int64_t row0, int64_t rows, int d, float* X, int kind = 0);
 

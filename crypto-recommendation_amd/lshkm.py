@@ -110,6 +110,16 @@ def lib():
             "lshkm_vectors_ids": (i32, [vp, vp, vp]),
             "lshkm_vectors_meta": (i32, [vp, i32, C.c_char_p, i64, C.POINTER(i64)]),
             "lshkm_vectors_free": (i32, [vp]),
+            "lshkm_tweets_read": (i32, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char, i32, C.POINTER(vp)]),
+            "lshkm_tweets_info": (i32, [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32),
+                                        C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+            "lshkm_tweets_table": (i32, [vp, vp, vp, vp, vp]),
+            "lshkm_tweets_ids": (i32, [vp, vp, vp]),
+            "lshkm_tweets_user_ids": (i32, [vp, vp, vp]),
+            "lshkm_tweets_match": (i32, [vp, vp, vp, i64, vp]),
+            "lshkm_tweets_free": (i32, [vp]),
+            "lshkm_user_sums": (i32, [vp, vp, vp, i64, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp]),
+            "lshkm_user_finish": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, C.POINTER(i64)]),
             "lshkm_config_value": (i32, [C.c_char_p, C.c_char_p, C.c_char_p, i64, C.POINTER(i32)]),
             "lshkm_config_load": (i32, [C.c_char_p, vp]),
             "lshkm_hash_assign": (i32, [vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
@@ -530,6 +540,163 @@ def read_vectors(path, delimiter=",", strt_line=1, threads=0):
         return ids, X, bool(ex.value), meta
     finally:
         lib().lshkm_vectors_free(h)
+
+
+# ------------------------------------------------- tweets and user vectors
+def _pack_ids(ids):
+    """A list of str / bytes as (bytes, int64 offsets [n+1])."""
+    enc = [s if isinstance(s, bytes) else s.encode() for s in ids]
+    off = np.zeros(len(enc) + 1, np.int64)
+    if enc:
+        np.cumsum([len(b) for b in enc], out=off[1:])
+    return b"".join(enc), off
+
+
+class Tweets:
+    """main.cpp:121-132: the tweet file, the lexicon and the coin file read as the
+    reference reads them (lshkm_tweets_read), the tweets numbered in the
+    iteration order of the reference's `tweets` map and the users in that of
+    tweets_to_user_vectors' user_map. Host only. P, T (distinct tweet IDs),
+    n_users, crypto_num and mentions are attributes."""
+
+    def __init__(self, input_path, lexicon_path, query_path, delimiter=",", threads=0):
+        self.h = None
+        h = C.c_void_p()
+        _ck(lib().lshkm_tweets_read(os.fsencode(input_path), os.fsencode(lexicon_path), os.fsencode(query_path),
+                                    delimiter.encode()[:1], threads, C.byref(h)))
+        self.h = h
+        P, T, nu, cn, mn, ib, ub = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        _ck(lib().lshkm_tweets_info(h, C.byref(P), C.byref(T), C.byref(nu), C.byref(cn), C.byref(mn), C.byref(ib),
+                                    C.byref(ub)))
+        self.P, self.T, self.n_users, self.crypto_num, self.mentions = P.value, T.value, nu.value, cn.value, mn.value
+        self._id_bytes, self._user_id_bytes = ib.value, ub.value
+        self._dev = {}
+
+    def table(self):
+        """(score [T] f64, ci_ptr [T+1] i64, ci_idx [mentions] i32, user_of [T] i32), numpy."""
+        score = np.empty(self.T, np.float64)
+        ci_ptr = np.empty(self.T + 1, np.int64)
+        ci_idx = np.empty(self.mentions, np.int32)
+        user_of = np.empty(self.T, np.int32)
+        _ck(lib().lshkm_tweets_table(self.h, _np_ptr(score), _np_ptr(ci_ptr), _np_ptr(ci_idx), _np_ptr(user_of)))
+        return score, ci_ptr, ci_idx, user_of
+
+    def device_table(self, ctx):
+        """table() as device tensors of ctx (uploaded once per device)."""
+        key = str(ctx.dev)
+        if key not in self._dev:
+            self._dev[key] = tuple(ctx.torch.from_numpy(a).to(ctx.dev) for a in self.table())
+        return self._dev[key]
+
+    def _ids(self, fn, nbytes, n):
+        raw = C.create_string_buffer(max(nbytes, 1))
+        off = np.empty(n + 1, np.int64)
+        _ck(fn(self.h, raw, _np_ptr(off)))
+        b = raw.raw
+        return [b[off[i]:off[i + 1]].decode() for i in range(n)]
+
+    def ids(self):
+        """Tweet IDs in tweet-number order."""
+        return self._ids(lib().lshkm_tweets_ids, self._id_bytes, self.T)
+
+    def user_ids(self):
+        """User IDs in user-slot order."""
+        return self._ids(lib().lshkm_tweets_user_ids, self._user_id_bytes, self.n_users)
+
+    def match(self, ids):
+        """tweets.count(vec.getId()) (crypto_rec.hpp:159) for a list of row IDs (or
+        the (bytes, offsets) pair of lshkm_vectors_ids): the tweet number of
+        each, -1 where it is no tweet's. int32 numpy."""
+        raw, off = ids if isinstance(ids, tuple) else _pack_ids(ids)
+        off = np.ascontiguousarray(off, np.int64)
+        n = off.shape[0] - 1
+        out = np.empty(n, np.int32)
+        _ck(lib().lshkm_tweets_match(self.h, C.c_char_p(bytes(raw)), _np_ptr(off), n, _np_ptr(out)))
+        return out
+
+    def close(self):
+        if self.h:
+            lib().lshkm_tweets_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def user_sums(ctx, tw, grp, table, G, C, carry=None):
+    """The update loop of tweets_to_user_vectors / clusters_to_user_vectors
+    (crypto_rec.hpp:97-102, :166-171) over the visits (tw[v], grp[v]) in order
+    (lshkm_user_sums). tw / grp int32 device tensors (-1: skipped); table =
+    (score, ci_ptr, ci_idx, ...) device tensors; carry = (sum, known) of the
+    visits before these, or None. Returns (sum [G][C] f64, known [G][C] uint8)."""
+    torch = ctx.torch
+    score, ci_ptr, ci_idx = table[0], table[1], table[2]
+    V, T = tw.shape[0], score.shape[0]
+    sums = ctx.empty((G, C), torch.float64)
+    known = ctx.empty((G, C), torch.uint8)
+    cs, ck = (None, None) if carry is None else carry
+    _ck(lib().lshkm_user_sums(ctx.h, _t_ptr(tw) if V else None, _t_ptr(grp) if V else None, V,
+                              _t_ptr(score) if T else None, _t_ptr(ci_ptr), _t_ptr(ci_idx) if ci_idx.numel() else None,
+                              T, G, C, _t_ptr(cs), _t_ptr(ck), _t_ptr(sums) if G * C else None,
+                              _t_ptr(known) if G * C else None))
+    return sums, known
+
+
+def user_finish(ctx, sums, known):
+    """The finishing loop (crypto_rec.hpp:107-137, :177-207) of every group, the
+    kept ones compacted in group order (lshkm_user_finish). Returns (U [n][C]
+    f64, mean [n] f64, unk_ptr [n+1] i64, unk_idx i32, src [n] i32: the group
+    of each kept row), device tensors."""
+    torch = ctx.torch
+    G, C_ = sums.shape
+    U = ctx.empty((G, C_), torch.float64)
+    mean = ctx.empty((G,), torch.float64)
+    unk_ptr = ctx.empty((G + 1,), torch.int64)
+    unk_idx = ctx.empty((max(G * C_, 1),), torch.int32)
+    src = ctx.empty((G,), torch.int32)
+    n = C.c_int64()
+    _ck(lib().lshkm_user_finish(ctx.h, _t_ptr(sums) if G * C_ else None, _t_ptr(known) if G * C_ else None, G, C_,
+                                _t_ptr(U) if G * C_ else None, _t_ptr(mean) if G else None, _t_ptr(unk_ptr),
+                                _t_ptr(unk_idx), _t_ptr(src) if G else None, C.byref(n)))
+    n = n.value
+    unk_ptr = unk_ptr[:n + 1]
+    return U[:n], mean[:n], unk_ptr, unk_idx[:int(unk_ptr[n].item())], src[:n]
+
+
+def tweets_to_user_vectors(ctx, tweets):
+    """tweets_to_user_vectors (crypto_rec.hpp:78-140): the real users, in the
+    reference's order. Returns (U, mean, unk_ptr, unk_idx, src, ids): the rows
+    and their unknown-index CSR as the recommender entry points take them, the
+    user slot of each row, and the user IDs."""
+    torch = ctx.torch
+    table = tweets.device_table(ctx)
+    tw = torch.arange(tweets.T, dtype=torch.int32, device=ctx.dev)
+    sums, known = user_sums(ctx, tw, table[3], table, tweets.n_users, tweets.crypto_num)
+    U, mean, unk_ptr, unk_idx, src = user_finish(ctx, sums, known)
+    names = tweets.user_ids()
+    return U, mean, unk_ptr, unk_idx, src, [names[s] for s in src.cpu().tolist()]
+
+
+def clusters_to_user_vectors(ctx, tweets, tweet_of_row, assign, user_num, carry=None, finish=True):
+    """clusters_to_user_vectors (crypto_rec.hpp:143-210): the user_num clusters
+    of the clustered vectors as "fake users". tweet_of_row: Tweets.match of the
+    rows' IDs (int32, numpy or device); assign: the rows' cluster IDs, the
+    device tensor the assignment wrote. Returns the bundle of
+    tweets_to_user_vectors with src = the cluster of each row and ids =
+    to_string(cluster). carry / finish=False: one contiguous shard of the rows
+    (returns (sum, known) for the next shard's carry)."""
+    torch = ctx.torch
+    table = tweets.device_table(ctx)
+    if isinstance(tweet_of_row, np.ndarray):
+        tweet_of_row = torch.from_numpy(np.ascontiguousarray(tweet_of_row, np.int32)).to(ctx.dev)
+    sums, known = user_sums(ctx, tweet_of_row, assign, table, user_num, tweets.crypto_num, carry)
+    if not finish:
+        return sums, known
+    U, mean, unk_ptr, unk_idx, src = user_finish(ctx, sums, known)
+    return U, mean, unk_ptr, unk_idx, src, [str(s) for s in src.cpu().tolist()]
 
 
 def hash_assign(lsh, X, Cc, src_rows=None, tuples=True, phi=False, bucket=True, metric=None):

@@ -489,6 +489,28 @@ def recommend_sharded(lk, ctx, X, x_mean, assign, K, U, u_mean, ucl, unk_ptr, un
     return out
 
 
+def clusters_to_user_vectors_sharded(lk, ctx, tweets, tweet_of_row, assign, user_num):
+    """clusters_to_user_vectors (crypto_rec.hpp:143-210) over row shards: this
+    rank's rows (tweet_of_row / assign of [row0, row0 + n)) are one contiguous
+    piece of the reference's loop over the clustered vectors, so every
+    (cluster, coin) chain continues from the previous rank's running (sum,
+    known) -- chain_partials' rank-to-rank carry -- and the last rank's totals
+    are finished on every rank. The bundle of lk.clusters_to_user_vectors, equal
+    on every rank and, bit for bit, the single-process result."""
+    torch = ctx.torch
+    C = tweets.crypto_num
+    sums_like = ctx.empty((user_num, C), torch.float64)
+    known_like = ctx.empty((user_num, C), torch.uint8)
+
+    def local(carry_s, carry_k):
+        carry = None if carry_s is None else (carry_s, carry_k)
+        return lk.clusters_to_user_vectors(ctx, tweets, tweet_of_row, assign, user_num, carry=carry, finish=False)
+
+    sums, known = chain_partials(local, sums_like, known_like)
+    U, mean, unk_ptr, unk_idx, src = lk.user_finish(ctx, sums, known)
+    return U, mean, unk_ptr, unk_idx, src, [str(s) for s in src.cpu().tolist()]
+
+
 def synth_recom_users(ctx, n_total, Q, d, seed):
     """The C5 recommend step's query users (bench / tests): Q rows spread over
     the whole job (rows i * floor(N / Q)), their known means (0: synthetic rows

@@ -82,6 +82,7 @@ typedef struct lshkm_ctx_s* lshkm_ctx;
 typedef struct lshkm_lsh_s* lshkm_lsh;
 typedef struct lshkm_cube_s* lshkm_cube;
 typedef struct lshkm_vectors_s* lshkm_vectors;
+typedef struct lshkm_tweets_s* lshkm_tweets;
 
 /* ------------------------------------------------------------------ context */
 const char* lshkm_last_error(void);
@@ -792,6 +793,85 @@ typedef struct lshkm_config {
     char query_file[1024];
 } lshkm_config;
 int lshkm_config_load(const char* path, lshkm_config* out);
+
+/* ------------------------------------------------- tweets and user vectors
+ * main.cpp:121-137: the tweet file, the lexicon and the coin file become
+ * user_vectors (tweets_to_user_vectors, crypto_rec.hpp:78-140) and
+ * fake_user_vectors (clusters_to_user_vectors, crypto_rec.hpp:143-210).
+ *
+ * Host: the formats and the visiting order. file_to_str_vectors (utils.cpp:72-127):
+ * the tweet file's first line sets P from its second token when it has one
+ * (else P = 1, main.cpp:120); every later line, a trailing '\r' dropped, is
+ * split on the delimiter: user ID, tweet ID, words. The coin file (query_path)
+ * is one coin per line, every token a variation. file_to_lexicon
+ * (utils.cpp:130-147): word<delim>score through std::stof, the first occurrence
+ * of a word wins. Tweet::Tweet (tweet.cpp:11-42): a word of the lexicon adds its
+ * float score to a double total in word order; any other word is compared with
+ * every variation of every coin and the matching coin indexes form a std::set;
+ * score = total / sqrt(total * total + 15). The tweet map (main.cpp:128-132)
+ * keeps the first tweet of a duplicated ID. Tweets are numbered in the
+ * iteration order of that std::unordered_map, users in the iteration order of
+ * tweets_to_user_vectors' user_map (crypto_rec.hpp:80-95, :107): both are
+ * libstdc++'s, reproduced with the same container and insertion sequence.
+ * Where the reference has undefined behaviour -- a tweet line or a lexicon
+ * line with fewer than two tokens, a score or a P that std::stof / std::stoi
+ * rejects -- and where a file cannot be opened (the reference goes on with an
+ * empty table), the call returns LSHKM_ERR_ARG, lshkm_last_error names file
+ * and line, and nothing is built. threads <= 0: the hardware's. */
+int lshkm_tweets_read(const char* input_path, const char* lexicon_path, const char* query_path, char delimiter,
+                      int threads, lshkm_tweets* out);
+/* P, the number of distinct tweet IDs, of distinct user IDs, of coin-file
+ * lines (crypto_num, main.cpp:135), of (tweet, coin) mentions, and the total
+ * byte lengths of the tweet and user IDs. Any pointer may be NULL. */
+int lshkm_tweets_info(lshkm_tweets t, int* P, int64_t* n_tweets, int64_t* n_users, int* crypto_num, int64_t* mentions,
+                      int64_t* id_bytes, int64_t* user_id_bytes);
+/* The tweets in map order: score_host [T] (getSentimentScore), ci_ptr_host
+ * [T+1] / ci_idx_host [mentions] (getCryptoIndexes: ascending, distinct),
+ * user_of_host [T] (the user's slot in user_map order). Any may be NULL. */
+int lshkm_tweets_table(lshkm_tweets t, double* score_host, int64_t* ci_ptr_host, int32_t* ci_idx_host,
+                       int32_t* user_of_host);
+/* Tweet IDs in map order / user IDs in user_map order: bytes concatenated, offsets [n+1]. */
+int lshkm_tweets_ids(lshkm_tweets t, char* bytes_host, int64_t* offsets_host);
+int lshkm_tweets_user_ids(lshkm_tweets t, char* bytes_host, int64_t* offsets_host);
+/* tweets.count(vec.getId()) (crypto_rec.hpp:159) for n row IDs (lshkm_vectors_ids'
+ * layout): tweet_of_row_host[i] = the tweet's number, or -1. */
+int lshkm_tweets_match(lshkm_tweets t, const char* id_bytes, const int64_t* id_offsets, int64_t n,
+                       int32_t* tweet_of_row_host);
+int lshkm_tweets_free(lshkm_tweets t);
+
+/* The update loop both functions share (crypto_rec.hpp:97-102, :166-171) over a
+ * list of visits v = 0..V-1 in the reference's loop order: tweet tw_dev[v]
+ * updates group grp_dev[v] (a user slot, or vec.getCluster()); tw or grp == -1:
+ * the visit is skipped (a vector that is no tweet, :159). For every (g, j):
+ * sum_dev[g][j] = the chain s = s + score over the visits of g whose tweet lists
+ * coin j and whose score is > 0, in visit order, from carry_sum_dev[g][j] (NULL:
+ * +0.0): the reference's fp64 value bit for bit (a NaN, zero or negative score
+ * adds nothing, +inf is added); known_dev[g][j] = the carry's flag OR "some
+ * visit of g lists j", whatever the score. With the carry, contiguous shards of
+ * the visit list passed in order give the single pass's result. sum_dev /
+ * known_dev may alias the carry. No floating-point atomics: the incidences are
+ * ordered by (g, j) with the stable scatter and every chain is summed in order.
+ * A tw outside [-1, T), a grp outside [-1, G), a ci_idx outside [0, C) or a
+ * decreasing ci_ptr: LSHKM_ERR_ARG (checked on the device before anything is
+ * written). G * C >= 2^31, V >= 2^31 or 2^31 incidences: LSHKM_ERR_UNSUPPORTED.
+ * Returns after the stream has drained. */
+int lshkm_user_sums(lshkm_ctx ctx, const int32_t* tw_dev, const int32_t* grp_dev, int64_t V, const double* score_dev,
+                    const int64_t* ci_ptr_dev, const int32_t* ci_idx_dev, int64_t T, int64_t G, int C,
+                    const double* carry_sum_dev, const uint8_t* carry_known_dev, double* sum_dev /*[G][C]*/,
+                    uint8_t* known_dev /*[G][C]*/);
+/* Finishing a user (crypto_rec.hpp:107-137, :177-207), for every group g and i
+ * ascending: an unknown i (flag 0) joins the unknown set, a known i does sum =
+ * sum + v[i]; a group whose every v[i] == 0 is dropped; else mean = sum /
+ * known_number and every unknown entry holds the mean. The kept groups are
+ * compacted in group order: U_dev [n_kept][C], mean_dev [n_kept], unk_ptr_dev
+ * [n_kept+1] / unk_idx_dev (ascending), src_dev[i] = the group of kept row i --
+ * the U / u_mean / unk_ptr / unk_idx (X / x_mean) arguments of
+ * lshkm_top_n_recom, lshkm_cluster_top_n, lshkm_lsh_p_closest and
+ * lshkm_lsh_validate10. Rows past n_kept are not written. G * C >= 2^31:
+ * LSHKM_ERR_UNSUPPORTED. Returns after *n_kept_host is on the host. */
+int lshkm_user_finish(lshkm_ctx ctx, const double* sum_dev, const uint8_t* known_dev, int64_t G, int C, double* U_dev,
+                      double* mean_dev, int64_t* unk_ptr_dev, int32_t* unk_idx_dev, int32_t* src_dev,
+                      int64_t* n_kept_host);
 
 /* ------------------------------------------------------------ synthetic data */
 /* include/lshkm_synth.h generator, rows [row0, row0+rows) into X_dev. */
