@@ -226,14 +226,15 @@ __device__ inline void glds16(const void* gsrc, uint32_t lds_dst) {
 // buffer after the image (8 pieces of 1 KiB, four 256-B half rows each); the
 // tile's top reads xf[0..31] from it by ds_read_b128. Bit 0 (register half):
 // dims 64..127 by 16-B register loads into 32 registers the hash phase has left
-// free (the centroid loop needs bh, the accumulator and xf), taken over as
-// xf[32..63] at the top. Both are issued between the hash phase and the
-// centroid tiles (pf_next); either alone still waits for the other half at the
-// top (measurement variants, -DLSHKM_ROWPF=1 / 2). DESIGN.md §4 has the
-// ordering rules. Row p of the buffer holds its 16-B chunk c at position
-// c ^ (p & 15): the 16 rows of a ds_read_b128 group on 16 distinct 4-bank
-// groups; the DMA's destination is lane-linear, so the swizzle sits on the
-// per-lane source address (as the gather ring's).
+// free (the centroid loop needs bh, the accumulator and xf), read in place by
+// the next tile (the tile-pair loop: two such sets trade places). Both are
+// issued between the hash phase and the centroid tiles (pf_next); either alone
+// still waits for the other half at the top (measurement variants,
+// -DLSHKM_ROWPF=1 / 2). DESIGN.md §4 has the ordering rules. Row p of the
+// buffer holds its 16-B chunk c at position c ^ (p & 15): the 16 rows of a
+// ds_read_b128 group on 16 distinct 4-bank groups; the DMA's destination is
+// lane-linear, so the swizzle sits on the per-lane source address (as the
+// gather ring's).
 #ifndef LSHKM_ROWPF
 #define LSHKM_ROWPF 3
 #endif
@@ -265,8 +266,12 @@ __device__ inline void glds16s(const void* sbase, uint32_t voff, uint32_t lds_ba
 // compiled in (no fp64 chain state). Its f32 centroid rows are register loads:
 // through the gather ring (GATH) each 16-dim step waits on its DMA, and the
 // short f32 sum cannot hide that (fused pass 2.21 vs 2.14 ms at C3).
+// HG: the hash tile's live groups of four accumulator registers. Group g holds
+// tables 2g and 2g + 1; with L <= 2 HG tables the registers past 4 HG hold only
+// the zero padding rows of the projection image, and neither their step adds
+// nor their certificates are compiled (the launch picks HG from L).
 template <bool HASH, bool MP = false, int MET = 0, int NIMG = 1, bool GATH = false, int ROWS = 0, bool FAST = false,
-          int PF = 0>
+          int PF = 0, int HG = 4>
 __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fused_hi_kernel(FusedArgs a) {
     constexpr int FH_WAVES = fh_waves<HASH, MP, MET, FAST>();
     constexpr int FH_THREADS = 64 * FH_WAVES;
@@ -277,6 +282,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
     static_assert(!(GATH && ROWS == 2), "fp64 rows re-read x in the chain: register loads of the winner rows");
     static_assert(!FAST || (MET == 0 && ROWS != 2 && NIMG == 1 && !GATH), "fast distance: euclidean, fp32 rows");
     static_assert(PF == 0 || (FAST && !MP && ROWS == 0 && FH_WAVES == FH_FAST_WAVES), "row prefetch: the FAST single-pass form");
+    static_assert(HG == 4 || (HASH && MET == 0 && PF != 0 && HG >= 1 && HG < 4), "fewer live hash groups: the prefetching FAST form");
     constexpr bool PFR = (PF & 1) != 0, PFL = (PF & 2) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int Kpad = a.Kpad;
@@ -410,8 +416,13 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
     // returned (lgkmcnt(0), as ring_advance). Over-waiting: the issue sits behind
     // the last wait on the row registers -- a compiler wait for an older load
     // would not count the DMA and so wait it out too.
-    float xn[32];                             // PFR: the upper halves of the wave's next tile
-    auto pf_next = [&](int64_t tl) {
+    // PFR: the upper halves of a wave's tiles live in two register sets that
+    // trade places from tile to tile (the loop below runs over tile pairs): the
+    // tile at hand computes from one while the next tile's loads land in the
+    // other, so no copy takes them over. The wave's last tile fetches nothing,
+    // and nothing reads the other set after it.
+    float xua[32], xub[32];
+    auto pf_next = [&](int64_t tl, float (&xnx)[32]) {
         if constexpr (PF != 0) {
             if (tl + tstride < ntiles) {
                 if constexpr (PFL) {
@@ -419,10 +430,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
                     asm volatile("" ::: "memory");
                     pf_dma(tl + tstride);
                 }
-                if constexpr (PFR) load_half(tl + tstride, 1, xn);
-            } else if constexpr (PFR) {       // the wave's last tile fetches nothing
-#pragma unroll
-                for (int j = 0; j < 32; j++) xn[j] = 0.f;
+                if constexpr (PFR) load_half(tl + tstride, 1, xnx);
             }
         }
     };
@@ -432,7 +440,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
     if constexpr (PF != 0) {
         if (tfirst + wave < ntiles) {
             if constexpr (PFL) pf_dma(tfirst + wave);
-            if constexpr (PFR) load_half(tfirst + wave, 1, xn);
+            if constexpr (PFR) load_half(tfirst + wave, 1, xua);
             if constexpr (PFL) {
                 __builtin_amdgcn_s_waitcnt(0x0F70);                        // vmcnt(0)
                 asm volatile("" ::: "memory");
@@ -440,10 +448,15 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
         }
     }
     PT_DECL
-    for (int64_t tile = tfirst + wave; NIMG == 2 ? rd < nround : tile < ntiles; tile += tstride, rd++) {
+    // One tile. xup: the tile's upper halves (PFR), xnx: where the next tile's go.
+    auto tile_body = [&](const int64_t tile, float (&xup)[32], float (&xnx)[32]) __attribute__((always_inline)) {
         const int64_t row = tile * 32 + col;
         const bool valid = row < a.N;
+        // dims 0..63 of the lane's share in xf[0..31]; dims 64..127 in xf[32..63],
+        // or with PFR in xup (xf's upper half is then never touched)
         float xf[64];
+        float* const xhi = PFR ? xup : xf + 32;
+        auto x8 = [&](int s) -> const float* { return s < 4 ? xf + 8 * s : xhi + 8 * (s - 4); };
         if constexpr (PF == 0) {
             load_row(tile, xf);
         } else {
@@ -462,6 +475,15 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
                 //    16 B); rn32's load, the stores and the list appends are conditional
                 //    or may be moved, and are not counted;
                 //  - without the register half, the 8 loads just issued above instead.
+                // The pair loop has two copies of this top. Each is reached from exactly
+                // one pf_next: the second tile's from the first tile's (straight down the
+                // pair), the first tile's from the second tile's (round the loop), or from
+                // the prologue on the wave's first tile; a single last tile leaves through
+                // the first copy's "no next tile" arm, having issued nothing. Every such
+                // path runs one whole tile body after the DMA, with that body's 16
+                // centroid-row loads, so the count is 16 in both copies. The register
+                // half (8 loads, issued after the DMA and before those 16) is older than
+                // the 16 as well: the same wait covers the set this tile reads.
                 // vmcnt(16) therefore leaves this tile's own stores in flight and waits
                 // for nothing younger than the centroid rows, which the distance has
                 // consumed: the wait is a guard, not a stall.
@@ -475,10 +497,6 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
                 }
             } else {
                 load_half(tile, 0, xf);
-            }
-            if constexpr (PFR) {
-#pragma unroll
-                for (int j = 0; j < 32; j++) xf[32 + j] = xn[j];
             }
         }
         half8 bh[8];
@@ -503,9 +521,9 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
 #pragma unroll
             for (int s = 0; s < 8; s++) {
                 half8 unused;
-                split_norm_step<false>(xf + 8 * s, bh[s], unused, n2a, n2b, r2);
+                split_norm_step<false>(x8(s), bh[s], unused, n2a, n2b, r2);
             }
-            pf_next(tile);
+            pf_next(tile, xnx);
             finish_norms();
         }
 
@@ -519,13 +537,14 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
 #pragma unroll
                 for (int s = 0; s < 8; s++) {
                     half8 bl;
-                    split_norm_step<true>(xf + 8 * s, bh[s], bl, n2a, n2b, r2);
+                    split_norm_step<true>(x8(s), bh[s], bl, n2a, n2b, r2);
                     const floatx16 acc = hash_tile_step(s, vh_row, vl_row, bh[s], bl);
                     if (s == 0) {
                         tot = acc;
                     } else {
+                        // the live groups only (HG): the others hold padding rows
 #pragma unroll
-                        for (int r = 0; r < 16; r += 2) {
+                        for (int r = 0; r < 4 * HG; r += 2) {
                             const float2v t2 = {tot[r], tot[r + 1]}, a2 = {acc[r], acc[r + 1]};
                             const float2v u2 = t2 + a2;
                             tot[r] = u2.x;
@@ -533,6 +552,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
                         }
                     }
                 }
+                // HG < 4: registers 4 HG.. keep step 0's partial values; no group g >= HG reads them
 #pragma unroll
                 for (int r = 0; r < 16; r++) acc_hi[r] = tot[r];
             }
@@ -543,13 +563,17 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
             const float nxf = (float)nx * (1.f + 0x1p-20f);
             int hc = 0;
             asm volatile("" : "+v"(hc));
-            const float* lt = lt0 + hc;
+            // cosine reads P and Q per function (declared here, outside the loop: inside it
+            // the cosine kernels' register allocation changes, and they are not re-measured)
             const float* lP = lpn0 + hc;
             const float* lQ = lv10 + hc;
-            const int32_t* lr = lr0 + hc;
+            // euclidean: P, Q, t, r are four arrays of 32 in a row (lpn0, lv10, lt0,
+            // lr0), so the constants of table 2g + h's four functions are four 16-B
+            // reads off one base, at the immediate offsets 128 j + 32 g bytes
+            const float* hb = lpn0 + hc + 4 * h;
             if (!x_ok && valid) fmask = (a.LK >= 32 ? 0xFFFFFFFFu : (1u << a.LK) - 1u);
 #pragma unroll
-            for (int g = 0; g < 4; g++) {
+            for (int g = 0; g < HG; g++) {
                 const int l = 2 * g + h;
                 if (l >= a.L || !valid) continue;
                 const int64_t o = row * a.L + l;
@@ -568,17 +592,15 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
                     if (a.bucket) a.bucket[o] = gv;
                     continue;
                 }
+                const float4 P4 = *reinterpret_cast<const float4*>(hb + 8 * g);
+                const float4 Q4 = *reinterpret_cast<const float4*>(hb + 32 + 8 * g);
+                const float4 t4 = *reinterpret_cast<const float4*>(hb + 64 + 8 * g);
+                const int4 r4 = *reinterpret_cast<const int4*>(hb + 96 + 8 * g);
                 int32_t hv[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int f = 4 * l + q;
-                    if (!certify_floor_f32(acc_hi[4 * g + q], lt[f], iw, nxf, lP[f], lQ[f], hv[q])) fmask |= 1u << f;
-                }
+                fmask |= certify_floor4_f32(acc_hi + 4 * g, t4, iw, nxf, P4, Q4, hv) << (4 * l);
                 if (a.tuples) *reinterpret_cast<int4*>(a.tuples + o * 4) = make_int4(hv[0], hv[1], hv[2], hv[3]);
-                uint32_t hn = 0;
-#pragma unroll
-                for (int q = 0; q < 4; q++) hn += phi_term_small(hv[q], lr[4 * l + q]);
-                const uint32_t ph = phi_final(hn);
+                const int32_t rv4[4] = {r4.x, r4.y, r4.z, r4.w};
+                const uint32_t ph = phi_final(phi_sum4_small(hv, rv4));
                 if (a.phi) a.phi[o] = (int32_t)ph;
                 if (a.bucket) a.bucket[o] = bucket_fast(ph, a.bdiv);
             }
@@ -594,7 +616,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
             }
         }
 
-        if (HASH) pf_next(tile);
+        if (HASH) pf_next(tile, xnx);
         PT_MARK(0)
         // the certificate's bound E depends on the row only: formed before the
         // centroid tiles (its fp64 ops overlap the MFMAs). cosine: + 2^-43 |x| for the normalisation and the reference's own q
@@ -653,7 +675,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
         // <HASH, MP> launches only the first of several passes (never the last)
         if (MP && (HASH || !a.pass_last)) {
             a.part[tile * 64 + lane] = make_float4(m1, m2, __int_as_float(t1), 0.f);
-            continue;
+            return;
         }
         const uint32_t l1 = __float_as_uint(m1) & 0xFu;
         const int i1 = t1 * 32 + 8 * (int)(l1 >> 2) + 4 * h + (int)(l1 & 3u);
@@ -779,8 +801,8 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
                 const float* c32 = a.C32 + (size_t)I1 * FU_D + 8 * h;
                 float2v q[4] = {};
                 // PF: the 16 loads issued together, as the form without the prefetch has
-                // them (with xn live the scheduler otherwise takes them two at a time,
-                // eight L2 round trips in a row)
+                // them (with the next tile's register set live the scheduler otherwise
+                // takes them two at a time, eight L2 round trips in a row)
                 float4 cc[16];
                 if constexpr (PF != 0) {
 #pragma unroll
@@ -802,7 +824,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
                     const float2v cv[4] = {{c0.x, c0.y}, {c0.z, c0.w}, {c1.x, c1.y}, {c1.z, c1.w}};
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
-                        const float2v xv = {xf[8 * s + 2 * j], xf[8 * s + 2 * j + 1]};
+                        const float2v xv = {x8(s)[2 * j], x8(s)[2 * j + 1]};
                         const float2v dv = xv - cv[j];
                         q[j] = __builtin_elementwise_fma(dv, dv, q[j]);
                     }
@@ -903,7 +925,7 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
                     if (s + XD < 8) load_x64_step(a, rowc, s + XD, h, xring[s % XD]);
                 } else {
 #pragma unroll
-                    for (int j = 0; j < 4; j++) xcur[j] = make_double2((double)xf[8 * s + 2 * j], (double)xf[8 * s + 2 * j + 1]);
+                    for (int j = 0; j < 4; j++) xcur[j] = make_double2((double)x8(s)[2 * j], (double)x8(s)[2 * j + 1]);
                 }
                 double dv[8];
 #pragma unroll
@@ -960,6 +982,21 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
             __builtin_amdgcn_s_setprio(0);
         }
         PT_MARK(2)
+    };
+    if constexpr (PFR) {
+        // Tile pairs: the first tile reads xua while the second's loads land in
+        // xub, the second reads xub while the next pair's first lands in xua. The
+        // wave's tile count may be odd: its last tile runs the first copy alone.
+        // "Has a next tile" is a scalar test (the wave index is one), here and in
+        // pf_next alike.
+        for (int64_t tile = tfirst + wave; tile < ntiles; tile += 2 * tstride) {
+            tile_body(tile, xua, xub);
+            if (tile + tstride >= ntiles) break;
+            tile_body(tile + tstride, xub, xua);
+        }
+    } else {
+        for (int64_t tile = tfirst + wave; NIMG == 2 ? rd < nround : tile < ntiles; tile += tstride, rd++)
+            tile_body(tile, xua, xub);
     }
     PT_FLUSH
     __syncthreads();
@@ -977,9 +1014,9 @@ __global__ __launch_bounds__((64 * fh_waves<HASH, MP, MET, FAST>()), 1) void fus
     }
 }
 
-template <bool HASH, bool MP, int MET, int NIMG, bool GATH, int ROWS, bool FAST, int PF>
+template <bool HASH, bool MP, int MET, int NIMG, bool GATH, int ROWS, bool FAST, int PF, int HG>
 static void hi_launch(hipStream_t s, unsigned nblk, size_t lds, const FusedArgs& a) {
-    hipLaunchKernelGGL((fused_hi_kernel<HASH, MP, MET, NIMG, GATH, ROWS, FAST, PF>), dim3(nblk),
+    hipLaunchKernelGGL((fused_hi_kernel<HASH, MP, MET, NIMG, GATH, ROWS, FAST, PF, HG>), dim3(nblk),
                        dim3(64 * fh_waves<HASH, MP, MET, FAST>()), lds, s, a);
 }
 
@@ -1010,15 +1047,21 @@ int launch_fused_hi_pass(hipStream_t s, unsigned nblk, const HiForm& f, FusedArg
     // the waves' row buffers after the image
     if (pf & 2) lds = (size_t)fh_rowpf_off(a.Kpad, f.hash) + FH_FAST_WAVES * FH_ROWPF_WAVE;
     const int nimg = f.two_image ? 2 : 1;
+    // live hash groups: 3 for L = 5 or 6 on the prefetching FAST form (the headline shape), else all 4
+    const int hg = f.hash && pf != 0 && (a.L == 5 || a.L == 6) ? 3 : 4;
     // every instantiation the library builds, one line each
-#define HI_CASE_PF(H, MP, MET, NIMG, GATH, ROWS, FAST, PF)                                                  \
+#define HI_CASE_HG(H, MP, MET, NIMG, GATH, ROWS, FAST, PF, HG)                                              \
     if (f.hash == (bool)H && f.mp == (bool)MP && f.metric == MET && nimg == NIMG && f.gath == (bool)GATH && \
-        f.rows == ROWS && f.fast == (bool)FAST && pf == PF) {                                               \
-        hi_launch<H, MP, MET, NIMG, GATH, ROWS, FAST, PF>(s, nblk, lds, a);                                 \
+        f.rows == ROWS && f.fast == (bool)FAST && pf == PF && hg == HG) {                                   \
+        hi_launch<H, MP, MET, NIMG, GATH, ROWS, FAST, PF, HG>(s, nblk, lds, a);                             \
         return 0;                                                                                           \
     }
+#define HI_CASE_PF(H, MP, MET, NIMG, GATH, ROWS, FAST, PF) HI_CASE_HG(H, MP, MET, NIMG, GATH, ROWS, FAST, PF, 4)
 #define HI_CASE(H, MP, MET, NIMG, GATH, ROWS, FAST) HI_CASE_PF(H, MP, MET, NIMG, GATH, ROWS, FAST, 0)
-    //      hash mp met nimg gath rows fast (rows fetched a tile ahead)
+    //      hash mp met nimg gath rows fast (rows fetched a tile ahead) (live hash groups)
+#if LSHKM_ROWPF != 0
+    HI_CASE_HG(1, 0, 0, 1, 0, 0, 1, FH_ROWPF, 3)   // L = 5, 6: tables 6 and 7 are padding
+#endif
     HI_CASE_PF(1, 0, 0, 1, 0, 0, 1, FH_ROWPF)   // euclidean, fp32 d = 128, one pass: the certified f32 distance
     HI_CASE_PF(0, 0, 0, 1, 0, 0, 1, FH_ROWPF)   // with its rows fetched one tile ahead,
     HI_CASE(1, 0, 0, 1, 0, 0, 1)      // or at the tile's top (the test build's LSHKM_ROW_PREFETCH=0),
@@ -1043,6 +1086,7 @@ int launch_fused_hi_pass(hipStream_t s, unsigned nblk, const HiForm& f, FusedArg
     HI_CASE(0, 0, 0, 1, 0, 2, 0)      // general rows: fp64 d <= 128
     HI_CASE(0, 0, 1, 1, 0, 2, 0)
 #undef HI_CASE
+#undef HI_CASE_HG
 #undef HI_CASE_PF
     set_error("launch_fused_hi_pass: no kernel was built for this form");
     return -1;

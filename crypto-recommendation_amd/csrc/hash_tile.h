@@ -98,6 +98,20 @@ __device__ __forceinline__ bool certify_floor_f32(float acc, float t, float iw, 
     v = (int32_t)lo;
     return lo == hi;
 }
+// The same for the four functions of one table (k = 4): certify_floor_f32's
+// arithmetic per function, the operations in its order. Returns the table's
+// mask, bit q set where function q is NOT certified; the caller shifts it to
+// the table's place (one shift per table instead of a 1 << f constant per
+// function held in a register).
+__device__ __forceinline__ uint32_t certify_floor4_f32(const float* acc4, const float4& t4, float iw, float nxf,
+                                                       const float4& P4, const float4& Q4, int32_t (&v)[4]) {
+    const float t[4] = {t4.x, t4.y, t4.z, t4.w}, P[4] = {P4.x, P4.y, P4.z, P4.w}, Q[4] = {Q4.x, Q4.y, Q4.z, Q4.w};
+    uint32_t bad = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+        if (!certify_floor_f32(acc4[q], t[q], iw, nxf, P[q], Q[q], v[q])) bad |= 1u << q;
+    return bad;
+}
 // CosineHGen: ip >= 0, certified when |acc~| exceeds |x| P_f + Q_f (no t, no w).
 __device__ __forceinline__ bool certify_sign_f32(float acc, float nxf, float P, float Q, int& bit) {
     const float B = fmaf(nxf, P, Q);

@@ -85,6 +85,20 @@ __device__ inline uint32_t phi_term_small(int32_t h, int32_t r) {
     const int32_t p = __mul24(h, r);
     return p < 0 ? (uint32_t)p + PHI_M : (uint32_t)p;
 }
+// The uint32 sum of a table's four phi_term_small terms without a select per
+// term. With s = p >> 31 (arithmetic: -1 or 0), p + (p < 0 ? M : 0) = p - M s
+// for every int32 p, so the wrapping sum of the four terms is
+//   (p0 + p1 + p2 + p3) - M (s0 + s1 + s2 + s3)   (mod 2^32),
+// the same ring element, and M x = (x << 31) - x. Same contract as
+// phi_term_small (|h| < 2^22, r in [0, 100], M = 2^31 - 1) for the products;
+// the identity itself holds for any p, so uncertified h give the same
+// (rewritten) value as the term-by-term form too.
+__device__ inline uint32_t phi_sum4_small(const int32_t (&h)[4], const int32_t (&r)[4]) {
+    const int32_t p0 = __mul24(h[0], r[0]), p1 = __mul24(h[1], r[1]), p2 = __mul24(h[2], r[2]), p3 = __mul24(h[3], r[3]);
+    const uint32_t sp = (uint32_t)p0 + (uint32_t)p1 + (uint32_t)p2 + (uint32_t)p3;
+    const uint32_t ss = (uint32_t)((p0 >> 31) + (p1 >> 31) + (p2 >> 31) + (p3 >> 31));
+    return sp + ss - (ss << 31);
+}
 __device__ inline int32_t bucket_fast(uint32_t ph, const BucketDiv& b) {
     if (b.mode == 1) return 0;
     if (b.mode == 2) return (int32_t)ph;
