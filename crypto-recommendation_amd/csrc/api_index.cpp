@@ -662,37 +662,38 @@ static int km_sums(lshkm_ctx ctx, Pts X, int64_t N, int d, const int32_t* assign
     // Parallel exact sums (fixed point where the chain provably never rounds);
     // test switch LSHKM_KM_PATH=chain runs every (c, j) chain sequentially.
     const bool force_chain = test_switch("LSHKM_KM_PATH", "chain");
+    // The segment workspace in buf: ~5 B per row element plus 2.5 KB per
+    // (cluster, dim). NULL past KM_SEG_WS_CAP, when it cannot be reserved, or
+    // when K exceeds the composition grid's y limit.
+    auto seg_ws_in = [&](lshkm::Buf& buf) -> void* {
+        if (K > 65535) return nullptr;
+        const size_t wsb = km_seg_ws_bytes(N, K, d);
+        if (wsb <= KM_SEG_WS_CAP && buf.reserve(wsb) == 0) return buf.p;
+        (void)hipGetLastError();          // a failed reservation leaves no sticky error
+        return nullptr;
+    };
     // fp64 rows: binade segments (update.hip / kmseg.h; the fp64 update of 1M x
     // 100 rows, K = 256: 0.93 ms vs 2.68 ms for fixed point + the wide chains);
-    // test switch LSHKM_KM_PATH=fx: the fixed-point form. The segment workspace
-    // is ~5 B per row element plus 2.5 KB per (cluster, dim): past KM_SEG_WS_CAP
-    // (or when it cannot be reserved, or K exceeds the composition grid's y
-    // limit) the fixed-point form runs instead -- the same exact sums.
-    if (X.f64 && !force_chain && !test_switch("LSHKM_KM_PATH", "fx") && K <= 65535) {
-        const size_t wsb = km_seg_ws_bytes(N, K, d);
-        if (wsb <= KM_SEG_WS_CAP && ctx->ws_range[11].reserve(wsb) == 0) {
+    // test switch LSHKM_KM_PATH=fx: the fixed-point form, which also runs where
+    // there is no segment workspace -- the same exact sums.
+    if (X.f64 && !force_chain && !test_switch("LSHKM_KM_PATH", "fx")) {
+        if (void* seg_ws = seg_ws_in(ctx->ws_km)) {
             if ((rc = launch_km_sums_seg(ctx->stream, X, d, rows_p, crow_p, K, N, sums, counts, carry, carry_counts,
-                                         ctx->ws_range[11].p))) {
+                                         seg_ws))) {
                 LSHKM_LAUNCH_CHECK();
                 return rc;
             }
             return 0;
         }
-        (void)hipGetLastError();          // a failed reservation leaves no sticky error
     }
     if (!force_chain) {
-        if ((rc = ctx->ws_range[11].reserve(km_fx_ws_bytes(K, d)))) return rc;
+        if ((rc = ctx->ws_km.reserve(km_fx_ws_bytes(K, d)))) return rc;
         // the chains the never-rounds test flags: by segments (fp32 rows of
         // general values: ~5 % of the chains of 10K N(0,1) values, most of 40K),
-        // sequential where the segment workspace does not fit
-        void* seg_ws = nullptr;
-        if (!X.f64 && K <= 65535) {
-            const size_t wsb = km_seg_ws_bytes(N, K, d);
-            if (wsb <= KM_SEG_WS_CAP && ctx->ws_km_seg.reserve(wsb) == 0) seg_ws = ctx->ws_km_seg.p;
-            else (void)hipGetLastError();
-        }
+        // sequential where there is no segment workspace
+        void* seg_ws = X.f64 ? nullptr : seg_ws_in(ctx->ws_km_seg);
         if ((rc = launch_km_sums_fx(ctx->stream, X, d, rows_p, crow_p, K, N, sums, counts, carry, carry_counts,
-                                    ctx->ws_range[11].p, (unsigned long long*)ctx->stats.p + STAT_KM_SEQ, seg_ws))) {
+                                    ctx->ws_km.p, (unsigned long long*)ctx->stats.p + STAT_KM_SEQ, seg_ws))) {
             LSHKM_LAUNCH_CHECK();
             return rc;
         }
@@ -805,8 +806,8 @@ static int shard_begin_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const int64_
                 LSHKM_ERR_ARG, "bad arguments");
     LSHKM_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = ctx->ws_range[11].reserve(km_fx_ws_bytes(K, d)))) return rc;
-    if ((rc = launch_km_shard_begin(ctx->stream, X, d, rows, crow, K, N, sums, asum, qt, counts, ctx->ws_range[11].p))) {
+    if ((rc = ctx->ws_km.reserve(km_fx_ws_bytes(K, d)))) return rc;
+    if ((rc = launch_km_shard_begin(ctx->stream, X, d, rows, crow, K, N, sums, asum, qt, counts, ctx->ws_km.p))) {
         LSHKM_LAUNCH_CHECK();
         return rc;
     }
@@ -939,8 +940,8 @@ static int silhouette_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const int32_t
     LSHKM_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     int rc;
-    lshkm::Buf& wn = ctx->ws_range[9];     // near [K] int32, then raw [K] + out [K+1] doubles
-    lshkm::Buf& ws = ctx->ws_range[10];    // s [N] when the caller gives none
+    lshkm::Buf& wn = ctx->ws_sil_near;     // near [K] int32, then raw [K] + out [K+1] doubles
+    lshkm::Buf& ws = ctx->ws_sil_s;        // s [N] when the caller gives none
     if ((rc = reserve(ctx, WS_ROWS, (size_t)std::max<int64_t>(N, 1) * 4)) || (rc = reserve(ctx, WS_CROW, (size_t)(K + 1) * 8)) ||
         (rc = wn.reserve((size_t)K * 4 + 8 + (size_t)(2 * K + 1) * 8)) ||
         (!s_dev && (rc = ws.reserve((size_t)std::max<int64_t>(N, 1) * 8))))

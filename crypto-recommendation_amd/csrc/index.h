@@ -89,8 +89,11 @@ struct lshkm_ctx_s {
     // scatter / query / update workspace (see api_index.cpp for the slot map)
     lshkm::Buf ws[16];
     // range assignment workspace (lshkm_range_assign)
-    lshkm::Buf ws_range[12];
+    lshkm::Buf ws_range[9];
+    lshkm::Buf ws_sil_near;      // silhouette: near [K] int32, then raw [K] + out [K + 1] doubles
+    lshkm::Buf ws_sil_s;         // silhouette: s [N] when the caller gives none
     lshkm::Buf ws_long;          // the recommender's chains of huge clusters (RcLong)
+    lshkm::Buf ws_km;            // k-means: the fixed point's workspace (km_fx_ws_bytes) or every chain's segment records (fp64 rows)
     lshkm::Buf ws_km_seg;        // k-means: the segment records of the chains the never-rounds test flags (fp32 rows)
     lshkm::Buf ws_scan;          // multi-block scans of large query size arrays
     lshkm::Buf ws_pam[5];        // PAM update (lshkm_pam_update): per-member, per-candidate, per-cluster, items, scan

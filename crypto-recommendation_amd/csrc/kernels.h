@@ -30,6 +30,12 @@ struct Pts {
         return q;
     }
 };
+// The row-type dispatch of a launcher: f(X.d()) or f(X.f()), f a generic lambda.
+template <typename F>
+inline void with_rows(Pts X, F&& f) {
+    if (X.f64) f(X.d());
+    else f(X.f());
+}
 
 // One assignment: rows, centroids, metric and the two outputs.
 struct AssignJob {
@@ -194,11 +200,12 @@ int launch_memo_rehome(hipStream_t s, const int32_t* old_memo, int32_t old_min, 
 int launch_memo_scatter(hipStream_t s, const int32_t* off, const int32_t* bit, int64_t n, int32_t* memo);
 
 // k-means update (update.hip).
-// carry / carry_counts (may be NULL): the running sums and counts the chain
-// continues from (exact-order sharded mode).
+// The sequential chains. carry / carry_counts (may be NULL): the running sums
+// and counts the chain continues from (exact-order sharded mode); flag != NULL:
+// only the flagged (cluster, 64-dim block) chains.
 int launch_km_chain(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K,
                     double* sums, int64_t* counts, const double* carry = nullptr,
-                    const int64_t* carry_counts = nullptr);
+                    const int64_t* carry_counts = nullptr, const int* flag = nullptr);
 // The same sums by binade segments (kmseg.h; ws: km_seg_ws_bytes): every chain
 // of fp64 rows; flag != NULL: only the flagged (cluster, 64-dim block) chains.
 size_t km_seg_ws_bytes(int64_t M, int K, int d);
@@ -215,8 +222,9 @@ size_t km_fx_ws_bytes(int K, int d);
 int launch_km_sums_fx(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K, int64_t M,
                       double* sums, int64_t* counts, const double* carry, const int64_t* carry_counts, void* ws,
                       unsigned long long* stat = nullptr, void* seg_ws = nullptr);
-// Sharded form (lshkm_kmeans_shard_*): begin (ws: km_shard_ws_bytes), certify,
-// prepare / chain (the flagged chains' records and their composition).
+// Sharded form (lshkm_kmeans_shard_*): begin (ws: km_fx_ws_bytes), certify,
+// prepare / chain (the flagged chains' records and their composition; ws:
+// km_shard_ws_bytes).
 size_t km_shard_ws_bytes(int64_t M, int K, int d);
 int launch_km_shard_begin(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K, int64_t M,
                           double* sums, double* asum, int32_t* qt, int64_t* counts, void* ws);

@@ -6,11 +6,20 @@
 //   addVectorToThis, cust_vector.hpp:177-184), then / (double)count unless the
 //   cluster is empty (divDimensionsByD skips 0, cust_vector.hpp:187-194);
 //   continue iff some center moved more than min_dist (:63-80).
-// fp64 addition is not associative, so each (c, j) is one sequential chain.
-// The members of every cluster come from the stable radix sort (scatter.hip)
-// in row order; a wave owns 64 dimensions of one cluster, each lane one chain,
-// and streams the member rows with 16 row loads in flight per lane (row
-// indices are wave-uniform scalar loads). Bytes: 4d per row read once.
+// fp64 addition is not associative, so each (c, j) is one sequential chain over
+// the members of c, which come from the stable radix sort (scatter.hip) in row
+// order. Three forms compute the same sums bit for bit:
+//   - the sequential chain (km_chain16_kernel: a wave owns 16 dims of one
+//     cluster and fetches 4 member rows per load; km_chain_lanes_kernel: one
+//     wave per listed chain), which adds in the reference's order;
+//   - binade segments (ks_* kernels, kmseg.h), the default for fp64 rows: the
+//     chain cut into windows whose records one wave per chain composes;
+//   - the fixed point (km_fx_* kernels), the default for fp32 rows: plain adds
+//     in any order wherever the chain provably never rounds (km_cert), the
+//     remaining chains by segments or, without a segment workspace, by the
+//     sequential chain.
+// The sharded form runs the fixed point per rank and the test on the global
+// values; km_finalize_kernel divides and tests the movement.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -22,70 +31,59 @@
 
 namespace lshkm {
 
-constexpr int KM_U = 16;
-
-// One (c, j) chain over the member rows p in [beg, end), row order: groups of
-// KM_U rows, loads issued three groups (48 rows) ahead of the adds so a lane
-// keeps ~48 row loads in flight (the chains of large clusters were latency
-// bound at 16: the k-means update of 1M fp64 rows, d = 100, K = 256 spent 5 ms
-// in the longest chain). Row indices are wave-uniform (scalar loads); positions
-// past the end re-read the last row and are not added.
-template <typename TX>
-__device__ __attribute__((always_inline)) inline double km_chain_rows(const TX* __restrict__ X, int d, int j,
-                                       const __attribute__((address_space(4))) int32_t* r4, int64_t beg, int64_t end,
-                                       double s) {
-    if (end <= beg) return s;
-    const int64_t ng = (end - beg + KM_U - 1) / KM_U;
-    TX v0[KM_U], v1[KM_U], v2[KM_U], v3[KM_U];
-    auto ld = [&](TX (&v)[KM_U], int64_t g) {
-        const int64_t p0 = beg + g * KM_U;
-        if (p0 + KM_U <= end) {          // 16 contiguous indices: one scalar block load
-            const auto* rp = r4 + p0;
-#pragma unroll
-            for (int u = 0; u < KM_U; u++) v[u] = X[(int64_t)rp[u] * d + j];
-        } else {
-#pragma unroll
-            for (int u = 0; u < KM_U; u++) v[u] = X[(int64_t)r4[min(p0 + u, end - 1)] * d + j];
-        }
-    };
-    auto add = [&](const TX (&v)[KM_U], int64_t g) {
-        const int64_t p0 = beg + g * KM_U;
-        if (p0 + KM_U <= end) {
-#pragma unroll
-            for (int u = 0; u < KM_U; u++) s = __dadd_rn(s, (double)v[u]);
-        } else {
-#pragma unroll
-            for (int u = 0; u < KM_U; u++)
-                if (p0 + u < end) s = __dadd_rn(s, (double)v[u]);
-        }
-    };
-    ld(v0, 0);
-    ld(v1, 1);
-    ld(v2, 2);
-    for (int64_t g = 0; g < ng; g += 4) {
-        ld(v3, g + 3);
-        add(v0, g);
-        if (g + 1 >= ng) break;
-        ld(v0, g + 4);
-        add(v1, g + 1);
-        if (g + 2 >= ng) break;
-        ld(v1, g + 5);
-        add(v2, g + 2);
-        if (g + 3 >= ng) break;
-        ld(v2, g + 6);
-        add(v3, g + 3);
+// ------------------------------------------------------------------ shared helpers
+// The cluster of member position p0: the last c with crow[c] <= p0
+// (wave-uniform binary search).
+__device__ inline int ks_first_cluster(const int64_t* __restrict__ crow, int K, int64_t p0) {
+    int lo = 0, hi = K;            // crow[lo] <= p0 < crow[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (crow[mid] <= p0) lo = mid; else hi = mid;
     }
-    return s;
+    return lo;
 }
 
-// Wide form (the sequential chains of large clusters): a wave owns 16 dims of
-// one cluster and each load instruction fetches 4 member rows (lane group k =
-// lane >> 4 the row, lane & 15 the dim), so a wave keeps 4 x 48 rows in flight
-// and the d / 16 waves of a cluster run side by side (the 64-dim form held one
-// row per instruction and two waves per cluster at d = 100; the largest
-// cluster's chain set the time). The chain lanes (k = 0) take the other groups'
-// values by lane-half swaps, in row order. Member indices are read one group of
-// 64 ahead of the row loads that use them.
+// The chains that take a second pass are marked per (cluster, 64-dim block):
+// bit min(31, j / 64) of flag[c]. flag == NULL: every chain.
+__device__ inline int km_flag_bit(int j) { return min(31, j / 64); }
+__device__ inline bool km_flagged(const int* __restrict__ flag, int c, int j) {
+    return !flag || ((flag[c] >> km_flag_bit(j)) & 1);
+}
+
+__device__ inline double ks_rl(double v, int i) {
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, i);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), i);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+__device__ inline int64_t ks_rl(int64_t v, int i) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, i);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), i);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__global__ void km_counts_kernel(const int64_t* __restrict__ crow, int K, const int64_t* __restrict__ carry_counts,
+                                 int64_t* __restrict__ counts) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < K) counts[c] = crow[c + 1] - crow[c] + (carry_counts ? carry_counts[c] : 0);
+}
+
+static void km_counts(hipStream_t s, const int64_t* crow, int K, const int64_t* carry_counts, int64_t* counts) {
+    if (counts)
+        hipLaunchKernelGGL(km_counts_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, crow, K, carry_counts,
+                           counts);
+}
+
+// ------------------------------------------------------------------ sequential chain
+// A wave owns 16 dims of one cluster and each load instruction fetches 4 member
+// rows (lane group k = lane >> 4 the row, lane & 15 the dim), so a wave keeps
+// 4 x 48 rows in flight and the d / 16 waves of a cluster run side by side (a
+// 64-dim wave held one row per instruction and two waves per cluster at d =
+// 100, and the largest cluster's chain set the time: the fp64 update of 1M x
+// 100 rows, K = 256, 3.44 -> 2.68 ms). The chain lanes (k = 0) take the other
+// groups' values by lane-half swaps, in row order. Member indices are read one
+// group of 64 ahead of the row loads that use them. flag: only the flagged
+// (cluster, 64-dim block)s (the fixed point's fallback); NULL: every chain.
 constexpr int KM16_G = 64;                 // member positions per group (16 steps x 4 rows)
 constexpr int KM16_Q = 3;                  // groups of row loads in flight
 
@@ -105,10 +103,9 @@ __device__ inline double km_x32(double v) {      // lanes k = 0, 1: lane + 32's 
 template <typename TX>
 __global__ __launch_bounds__(64) void km_chain16_kernel(const TX* __restrict__ X, int d, const int32_t* __restrict__ rows,
                                                        const int64_t* __restrict__ crow, const double* __restrict__ carry,
-                                                       const int* __restrict__ flag, double* __restrict__ sums,
-                                                       const uint8_t* __restrict__ mask) {
+                                                       const int* __restrict__ flag, double* __restrict__ sums) {
     const int c = blockIdx.x, jb = blockIdx.y;
-    if (flag && !((flag[c] >> min(31, jb / 4)) & 1)) return;
+    if (!km_flagged(flag, c, jb * 16)) return;
     const int lane = threadIdx.x, k = lane >> 4;
     const int j = jb * 16 + (lane & 15);
     const int jl = j < d ? j : d - 1;
@@ -166,245 +163,17 @@ __global__ __launch_bounds__(64) void km_chain16_kernel(const TX* __restrict__ X
             }
         }
     }
-    if (k == 0 && j < d && (!mask || mask[(size_t)c * d + j])) sums[(size_t)c * d + j] = s;
+    if (k == 0 && j < d) sums[(size_t)c * d + j] = s;
 }
 
-template <typename TX>
-__global__ __launch_bounds__(64) void km_chain_kernel(const TX* __restrict__ X, int d, const int32_t* __restrict__ rows,
-                                                     const int64_t* __restrict__ crow, int K,
-                                                     const double* __restrict__ carry, const int64_t* __restrict__ carry_counts,
-                                                     double* __restrict__ sums, int64_t* __restrict__ counts) {
-    const int c = blockIdx.x;
-    const int j = blockIdx.y * 64 + threadIdx.x;
-    const int64_t beg = crow[c], end = crow[c + 1];
-    if (blockIdx.y == 0 && threadIdx.x == 0 && counts) counts[c] = end - beg + (carry_counts ? carry_counts[c] : 0);
-    if (j >= d) return;
-    const __attribute__((address_space(4))) int32_t* r4 = (const __attribute__((address_space(4))) int32_t*)rows;
-    // exact mode across shards: the chain continues from the previous shard's running sum
-    const double s = km_chain_rows(X, d, j, r4, beg, end, carry ? carry[(size_t)c * d + j] : 0.0);
-    sums[(size_t)c * d + j] = s;
-}
-
-__global__ void km_counts_kernel(const int64_t* __restrict__ crow, int K, const int64_t* __restrict__ carry_counts,
-                                 int64_t* __restrict__ counts) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < K) counts[c] = crow[c + 1] - crow[c] + (carry_counts ? carry_counts[c] : 0);
-}
-
-static bool km_wide() {
-    // the wide form (16 dims per wave, 4 member rows per load) by default: the
-    // fp64 update of 1M x 100 rows, K = 256, 3.44 -> 2.68 ms; LSHKM_KM_CHAIN=64:
-    // the 64-dim form
-    return !test_switch("LSHKM_KM_CHAIN", "64");
-}
-
-int launch_km_chain(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K,
-                    double* sums, int64_t* counts, const double* carry, const int64_t* carry_counts) {
-    if (km_wide()) {
-        const dim3 grid((unsigned)K, (unsigned)((d + 15) / 16));
-        if (X.f64)
-            hipLaunchKernelGGL(km_chain16_kernel<double>, grid, dim3(64), 0, s, X.d(), d, rows, crow, carry, nullptr, sums, nullptr);
-        else
-            hipLaunchKernelGGL(km_chain16_kernel<float>, grid, dim3(64), 0, s, X.f(), d, rows, crow, carry, nullptr, sums, nullptr);
-        if (counts)
-            hipLaunchKernelGGL(km_counts_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, crow, K, carry_counts,
-                               counts);
-        return kstatus("update.hip");
-    }
-    const dim3 grid((unsigned)K, (unsigned)((d + 63) / 64));
-    if (X.f64)
-        hipLaunchKernelGGL(km_chain_kernel<double>, grid, dim3(64), 0, s, X.d(), d, rows, crow, K, carry, carry_counts,
-                           sums, counts);
-    else
-        hipLaunchKernelGGL(km_chain_kernel<float>, grid, dim3(64), 0, s, X.f(), d, rows, crow, K, carry, carry_counts,
-                           sums, counts);
+int launch_km_chain(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K, double* sums,
+                    int64_t* counts, const double* carry, const int64_t* carry_counts, const int* flag) {
+    const dim3 grid((unsigned)K, (unsigned)((d + 15) / 16));
+    with_rows(X, [&](auto* x) {
+        hipLaunchKernelGGL(km_chain16_kernel, grid, dim3(64), 0, s, x, d, rows, crow, carry, flag, sums);
+    });
+    km_counts(s, crow, K, carry_counts, counts);
     return kstatus("update.hip");
-}
-
-// ------------------------------------------------------------------ parallel form
-// The reference's chain s = ((0 + x_1) + x_2) + ... rounds only when a partial
-// sum is not a double. Every partial sum -- of the chain, or of any subset of
-// the values in any order -- is an integer multiple of 2^q (q = the lowest set
-// bit over the chain's values) bounded by A = sum |x_i| < count * 2^t (t = the
-// highest bit position + 1), so when ceil(log2 count) + t - q <= 53 every such
-// partial is a double: no step of the chain rounds, and neither does any other
-// order of fp64 additions. The chain's result is then the exact sum, which
-// plain fp64 adds compute in any order -- per lane, then by fp64 atomics into
-// the (c, j) accumulator. q and t are tracked alongside (integer min / max), and
-// a chain whose test fails (or holding inf / nan) is flagged and recomputed by
-// the sequential kernel above (km_chain_kernel).
-// Work: waves stream 512 consecutive member positions of the cluster-sorted
-// list (lane = dimension), flushing their partial (one fp64 atomic add, two
-// integer atomics) whenever the cluster changes.
-constexpr int KMF_CH = 512;
-constexpr int KMF_BAD = 1 << 20;     // qmin marker of a chain that needs the sequential kernel
-
-struct KmFx {                        // per (c, j), zeroed / initialised by km_fx_init_kernel
-    double sum;
-    double asum;                     // sum of |x| (rounded: <= (1 + n 2^-53) times the true one)
-    int qmin;                        // lowest set-bit exponent, -KMF_BAD if flagged
-    int tmax;                        // highest bit position + 1
-};
-
-__global__ void km_fx_init_kernel(KmFx* __restrict__ acc, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { acc[i].sum = 0.0; acc[i].asum = 0.0; acc[i].qmin = 1 << 30; acc[i].tmax = -(1 << 30); }
-}
-
-__device__ inline void km_fx_flush(KmFx* a, double v, double av, int qmin, int tmax, bool bad) {
-    if (v != 0.0) atomicAdd(&a->sum, v);
-    if (av != 0.0) atomicAdd(&a->asum, av);
-    atomicMin(&a->qmin, bad ? -KMF_BAD : qmin);
-    atomicMax(&a->tmax, tmax);
-}
-
-// The never-rounds test of one (c, j): its cnt values are integer multiples of
-// 2^qmin below 2^tmax in magnitude, and their |x| sum to asum (fp64-rounded in
-// any order: within a factor 1 + cnt 2^-53 <= 1 + 2^-22 of the true sum for
-// cnt < 2^31). Every partial sum of any subset, in any order, is a multiple of
-// 2^qmin no larger in magnitude than the true sum of |x|: a double when that is
-// below 2^(53 + qmin). The count form (cnt 2^tmax) is the coarser bound of the
-// same kind; the |x| form passes on far more general fp32 chains (N(0,1) rows:
-// ~95 % vs ~64 % of the chains of 10K values).
-__device__ inline bool km_cert(int qmin, int tmax, int64_t cnt, double asum) {
-    if (qmin <= -KMF_BAD / 2) return false;        // inf / nan among the values
-    if (qmin > tmax) return true;                  // no nonzero value: the sum is +0
-    int lc = 0;
-    while (((int64_t)1 << lc) < cnt) lc++;         // ceil(log2 count)
-    // every partial below cnt 2^tmax <= 2^(lc + tmax): finite only if that is <=
-    // 2^1023 (else an any-order sum may overflow where the reference's chain stays
-    // finite, e.g. [M, -M, M] with M = 1.5 * 2^1023)
-    if (lc + tmax - qmin <= 53 && lc + tmax <= 1023) return true;
-    // the |x| bound (an overflowed asum is inf and fails; 2^(53 + qmin) may be inf)
-    return asum * (1.0 + 0x1p-20) < ldexp(1.0, min(53 + qmin, 1024));
-}
-
-// lowest set-bit exponent q and top t of a nonzero finite value; false for
-// +-0 (adds nothing: -0 + 0 = +0 either way) and inf / nan (sets bad)
-__device__ inline bool km_fx_bits(float v, int& q, int& t, bool& bad) {
-    const uint32_t b = __float_as_uint(v);
-    const int E = (int)((b >> 23) & 255u);
-    const uint32_t f = b & 0x7FFFFFu;
-    if (E == 255) { bad = true; return false; }
-    const uint32_t m = E ? (f | 0x800000u) : f;
-    if (m == 0) return false;
-    const int e = (E ? E : 1) - 150;
-    q = e + __builtin_ctz(m);
-    t = e + 32 - __builtin_clz(m);
-    return true;
-}
-__device__ inline bool km_fx_bits(double v, int& q, int& t, bool& bad) {
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    const int E = (int)((b >> 52) & 2047u);
-    const uint64_t f = b & 0xFFFFFFFFFFFFFull;
-    if (E == 2047) { bad = true; return false; }
-    const uint64_t m = E ? (f | (1ull << 52)) : f;
-    if (m == 0) return false;
-    const int e = (E ? E : 1) - 1075;
-    q = e + __builtin_ctzll(m);
-    t = e + 64 - __builtin_clzll(m);
-    return true;
-}
-
-template <typename TX>
-__global__ __launch_bounds__(64) void km_fx_kernel(const TX* __restrict__ X, int d, const int32_t* __restrict__ rows,
-                                                  const int64_t* __restrict__ crow, int K, int64_t M,
-                                                  KmFx* __restrict__ acc) {
-    const int64_t p0 = (int64_t)blockIdx.x * KMF_CH;
-    if (p0 >= M) return;
-    const int64_t p1 = min(M, p0 + KMF_CH);
-    const int j = blockIdx.y * 64 + threadIdx.x;
-    const bool on = j < d;
-    const __attribute__((address_space(4))) int32_t* r4 = (const __attribute__((address_space(4))) int32_t*)rows;
-    // cluster of position p0: the last c with crow[c] <= p0 (wave-uniform binary search)
-    int lo = 0, hi = K;              // crow[lo] <= p0 < crow[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (crow[mid] <= p0) lo = mid; else hi = mid;
-    }
-    int c = lo;
-    int64_t cend = crow[c + 1];
-    double s = 0.0, as = 0.0;
-    int qmin = 1 << 30, tmax = -(1 << 30);
-    bool bad = false;
-    for (int64_t p = p0; p < p1; p += 16) {
-        TX v[16];
-#pragma unroll
-        for (int u = 0; u < 16; u++) v[u] = (on && p + u < p1) ? X[(int64_t)r4[p + u] * d + j] : (TX)0;
-#pragma unroll
-        for (int u = 0; u < 16; u++) {
-            if (p + u >= p1) break;
-            while (p + u >= cend) {              // cluster boundary: flush, move on (skipping empty clusters)
-                if (on) km_fx_flush(acc + (size_t)c * d + j, s, as, qmin, tmax, bad);
-                s = 0.0; as = 0.0; qmin = 1 << 30; tmax = -(1 << 30); bad = false;
-                c++;
-                cend = crow[c + 1];
-            }
-            int q, t;
-            if (!km_fx_bits(v[u], q, t, bad)) continue;
-            qmin = min(qmin, q);
-            tmax = max(tmax, t);
-            s = __dadd_rn(s, (double)v[u]);     // exact whenever the chain's test passes
-            as = __dadd_rn(as, fabs((double)v[u]));
-        }
-    }
-    if (on) km_fx_flush(acc + (size_t)c * d + j, s, as, qmin, tmax, bad);
-}
-
-// fp32 rows with d % 128 == 0: a wave reads whole 512-B row slices (two
-// dims per lane, float2), half the load instructions of km_fx_kernel's 256-B
-// half-rows for the same gather.
-#ifndef KMF2_U
-#define KMF2_U 16       // rows in flight per wave
-#endif
-__global__ __launch_bounds__(64) void km_fx2_kernel(const float* __restrict__ X, int d, const int32_t* __restrict__ rows,
-                                                    const int64_t* __restrict__ crow, int K, int64_t M,
-                                                    KmFx* __restrict__ acc) {
-    const int64_t p0 = (int64_t)blockIdx.x * KMF_CH;
-    if (p0 >= M) return;
-    const int64_t p1 = min(M, p0 + KMF_CH);
-    const int j = blockIdx.y * 128 + 2 * threadIdx.x;
-    const __attribute__((address_space(4))) int32_t* r4 = (const __attribute__((address_space(4))) int32_t*)rows;
-    int lo = 0, hi = K;              // crow[lo] <= p0 < crow[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (crow[mid] <= p0) lo = mid; else hi = mid;
-    }
-    int c = lo;
-    int64_t cend = crow[c + 1];
-    double s0 = 0.0, s1 = 0.0, a0 = 0.0, a1 = 0.0;
-    int q0 = 1 << 30, t0 = -(1 << 30), q1 = 1 << 30, t1 = -(1 << 30);
-    bool bad0 = false, bad1 = false;
-    for (int64_t p = p0; p < p1; p += KMF2_U) {
-        float2 v[KMF2_U];
-#pragma unroll
-        for (int u = 0; u < KMF2_U; u++)
-            v[u] = p + u < p1 ? *reinterpret_cast<const float2*>(X + (int64_t)r4[p + u] * d + j) : make_float2(0.f, 0.f);
-#pragma unroll
-        for (int u = 0; u < KMF2_U; u++) {
-            if (p + u >= p1) break;
-            while (p + u >= cend) {              // cluster boundary: flush, move on (skipping empty clusters)
-                km_fx_flush(acc + (size_t)c * d + j, s0, a0, q0, t0, bad0);
-                km_fx_flush(acc + (size_t)c * d + j + 1, s1, a1, q1, t1, bad1);
-                s0 = s1 = a0 = a1 = 0.0; q0 = q1 = 1 << 30; t0 = t1 = -(1 << 30); bad0 = bad1 = false;
-                c++;
-                cend = crow[c + 1];
-            }
-            int q, t;
-            if (km_fx_bits(v[u].x, q, t, bad0)) {
-                q0 = min(q0, q); t0 = max(t0, t);
-                s0 = __dadd_rn(s0, (double)v[u].x);
-                a0 = __dadd_rn(a0, (double)fabsf(v[u].x));
-            }
-            if (km_fx_bits(v[u].y, q, t, bad1)) {
-                q1 = min(q1, q); t1 = max(t1, t);
-                s1 = __dadd_rn(s1, (double)v[u].y);
-                a1 = __dadd_rn(a1, (double)fabsf(v[u].y));
-            }
-        }
-    }
-    km_fx_flush(acc + (size_t)c * d + j, s0, a0, q0, t0, bad0);
-    km_fx_flush(acc + (size_t)c * d + j + 1, s1, a1, q1, t1, bad1);
 }
 
 // The flagged chains of at most KM_LANE_MAX members (global count): one wave
@@ -418,7 +187,6 @@ __global__ __launch_bounds__(64) void km_fx2_kernel(const float* __restrict__ X,
 // the C5 chains on full-mantissa rows: their 64-dim blocks touch ~40 % of the
 // windows).
 constexpr int64_t KM_LANE_MAX = 32768;
-__device__ inline double ks_rl(double v, int i);
 template <typename TX>
 __global__ __launch_bounds__(64) void km_chain_lanes_kernel(const TX* __restrict__ X, int d,
                                                            const int32_t* __restrict__ rows,
@@ -454,128 +222,17 @@ __global__ __launch_bounds__(64) void km_chain_lanes_kernel(const TX* __restrict
     }
 }
 
-// Per (c, j): the exact sum if the chain provably never rounds, else a flag for
-// the sequential kernel. carry (sharded exact mode): the chain starts from it.
-__global__ void km_fx_finalize_kernel(const KmFx* __restrict__ acc, const int64_t* __restrict__ crow, int K, int d,
-                                      const double* __restrict__ carry, const int64_t* __restrict__ carry_counts,
-                                      double* __restrict__ sums, int* __restrict__ flag,
-                                      unsigned long long* __restrict__ stat, int32_t* __restrict__ lanes,
-                                      unsigned int* __restrict__ lane_cnt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)K * d) return;
-    const int c = (int)(i / d);
-    const KmFx a = acc[i];
-    int64_t cnt = crow[c + 1] - crow[c];
-    double s = a.sum, as = a.asum;
-    int qmin = a.qmin, tmax = a.tmax;
-    bool ok = qmin > -KMF_BAD / 2;
-    if (carry && ok) {                  // the carried running sum is one more value of the chain
-        const double s0 = carry[i];
-        cnt += 1;
-        int q, t;
-        bool bad = false;
-        if (km_fx_bits(s0, q, t, bad)) {
-            qmin = min(qmin, q);
-            tmax = max(tmax, t);
-            s = __dadd_rn(s0, s);
-            as = __dadd_rn(as, fabs(s0));
-        }
-        if (bad) ok = false;
-    }
-    ok = ok && km_cert(qmin, tmax, cnt, as);
-    // a flagged chain: one lane of km_chain_lanes_kernel when it is short (and
-    // a lane list is given), else its (c, 64-dim block) to the block kernels
-    const bool lane_chain = !ok && lanes && cnt <= KM_LANE_MAX;
-    if (ok) sums[i] = s;
-    else if (!lane_chain) atomicOr(flag + c, 1 << min(31, (int)(i % d) / 64));
-    if (lanes) seg_append(lane_chain, (int32_t)i, lane_cnt, lanes, (int)(threadIdx.x & 63));
-    if (stat) {
-        const unsigned long long nb = __ballot(!ok);
-        if (nb && (threadIdx.x & 63) == __builtin_ctzll(nb)) atomicAdd(stat, (unsigned long long)__popcll(nb));
-    }
-}
-
-// The sequential chains of the flagged (c, 64-dim block)s only.
-template <typename TX>
-__global__ __launch_bounds__(64) void km_chain_flagged_kernel(const TX* __restrict__ X, int d,
-                                                             const int32_t* __restrict__ rows,
-                                                             const int64_t* __restrict__ crow, int K,
-                                                             const double* __restrict__ carry,
-                                                             const int* __restrict__ flag, double* __restrict__ sums) {
-    const int c = blockIdx.x;
-    if (!((flag[c] >> min(31, (int)blockIdx.y)) & 1)) return;
-    const int j = blockIdx.y * 64 + threadIdx.x;
-    if (j >= d) return;
-    const __attribute__((address_space(4))) int32_t* r4 = (const __attribute__((address_space(4))) int32_t*)rows;
-    const int64_t beg = crow[c], end = crow[c + 1];
-    sums[(size_t)c * d + j] = km_chain_rows(X, d, j, r4, beg, end, carry ? carry[(size_t)c * d + j] : 0.0);
-}
-
-
-size_t km_fx_ws_bytes(int K, int d) { return (size_t)K * d * sizeof(KmFx) + (size_t)K * 4 + 64 + (size_t)K * d * 4 + 64; }
-
-int launch_km_sums_seg(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K, int64_t M,
-                       double* sums, int64_t* counts, const double* carry, const int64_t* carry_counts, void* ws,
-                       const int* flag);
-
-int launch_km_sums_fx(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K, int64_t M,
-                      double* sums, int64_t* counts, const double* carry, const int64_t* carry_counts, void* ws,
-                      unsigned long long* stat, void* seg_ws) {
-    KmFx* acc = reinterpret_cast<KmFx*>(ws);
-    int* flag = reinterpret_cast<int*>(acc + (size_t)K * d);
-    unsigned int* lane_cnt = reinterpret_cast<unsigned int*>(flag + K);
-    int32_t* lanes = reinterpret_cast<int32_t*>(lane_cnt + 16);
-    const int64_t n = (int64_t)K * d;
-    (void)hipMemsetAsync(flag, 0, (size_t)K * 4 + 64, s);      // the flags and the lane count
-    hipLaunchKernelGGL(km_fx_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, n);
-    const int jb = (d + 63) / 64;
-    const dim3 fgrid((unsigned)((M + KMF_CH - 1) / KMF_CH), (unsigned)jb);
-    if (M > 0) {
-        if (X.f64) hipLaunchKernelGGL(km_fx_kernel<double>, fgrid, dim3(64), 0, s, X.d(), d, rows, crow, K, M, acc);
-        else if (d % 128 == 0)
-            hipLaunchKernelGGL(km_fx2_kernel, dim3(fgrid.x, (unsigned)(d / 128)), dim3(64), 0, s, X.f(), d, rows, crow, K, M,
-                               acc);
-        else hipLaunchKernelGGL(km_fx_kernel<float>, fgrid, dim3(64), 0, s, X.f(), d, rows, crow, K, M, acc);
-    }
-    // the lane form for short flagged chains where the segment form would run
-    // (test switch LSHKM_KM_LANES=0: every flagged chain to the block kernels)
-    const bool use_lanes = seg_ws && !test_switch("LSHKM_KM_FLAGGED", "chain") && !test_switch("LSHKM_KM_LANES", "0");
-    hipLaunchKernelGGL(km_fx_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, crow, K, d, carry,
-                       carry_counts, sums, flag, stat, use_lanes ? lanes : nullptr, lane_cnt);
-    if (use_lanes) {
-        if (X.f64)
-            hipLaunchKernelGGL(km_chain_lanes_kernel<double>, dim3(gsz(n, 1, 8192)), dim3(64), 0, s, X.d(), d, rows, crow,
-                               lanes, lane_cnt, carry, sums);
-        else
-            hipLaunchKernelGGL(km_chain_lanes_kernel<float>, dim3(gsz(n, 1, 8192)), dim3(64), 0, s, X.f(), d, rows, crow,
-                               lanes, lane_cnt, carry, sums);
-    }
-    if (seg_ws && !test_switch("LSHKM_KM_FLAGGED", "chain")) {
-        // the flagged chains by binade segments (every window of theirs in
-        // parallel; the sequential form's time was set by the longest chain:
-        // 20 ms for a 206K-member cluster of full-mantissa rows)
-        if (const int rc = launch_km_sums_seg(s, X, d, rows, crow, K, M, sums, nullptr, carry, nullptr, seg_ws, flag))
-            return rc;
-    } else if (km_wide()) {
-        const dim3 g16((unsigned)K, (unsigned)((d + 15) / 16));
-        if (X.f64)
-            hipLaunchKernelGGL(km_chain16_kernel<double>, g16, dim3(64), 0, s, X.d(), d, rows, crow, carry, flag, sums, nullptr);
-        else
-            hipLaunchKernelGGL(km_chain16_kernel<float>, g16, dim3(64), 0, s, X.f(), d, rows, crow, carry, flag, sums, nullptr);
-    } else if (X.f64)
-        hipLaunchKernelGGL(km_chain_flagged_kernel<double>, dim3((unsigned)K, (unsigned)jb), dim3(64), 0, s, X.d(), d,
-                           rows, crow, K, carry, flag, sums);
-    else
-        hipLaunchKernelGGL(km_chain_flagged_kernel<float>, dim3((unsigned)K, (unsigned)jb), dim3(64), 0, s, X.f(), d,
-                           rows, crow, K, carry, flag, sums);
-    if (counts)
-        hipLaunchKernelGGL(km_counts_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, crow, K, carry_counts,
-                           counts);
-    return kstatus("update.hip (fixed point)");
+// lanes [*lane_cnt]: the listed chains (c * d + j) of a [K][d] problem
+static void km_chain_lanes(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K,
+                           const int32_t* lanes, const unsigned int* lane_cnt, const double* carry, double* sums) {
+    with_rows(X, [&](auto* x) {
+        hipLaunchKernelGGL(km_chain_lanes_kernel, dim3(gsz((int64_t)K * d, 1, 8192)), dim3(64), 0, s, x, d, rows, crow,
+                           lanes, lane_cnt, carry, sums);
+    });
 }
 
 // ------------------------------------------------------------------ segmented form
-// fp64 rows (general doubles: the fixed-point test above fails for almost every
+// fp64 rows (general doubles: the fixed-point test below fails for almost every
 // chain, and the sequential chain of the largest cluster set the time). Every
 // (c, j) chain is cut into pairs (512-position window x cluster) and each pair
 // into binade segments (kmseg.h), four launches:
@@ -588,18 +245,7 @@ int launch_km_sums_fx(hipStream_t s, Pts X, int d, const int32_t* rows, const in
 // A and C stream the member rows (lane = dimension, 512-B row slices); pair
 // (w, c) has index w + c (windows and clusters advance monotonically together).
 constexpr int KS_USUM = 16;        // member rows in flight per wave: pass A
-#ifndef KS_USEG
-#define KS_USEG 16                 // pass C (its per-step state holds more registers)
-#endif
-
-__device__ inline int ks_first_cluster(const int64_t* __restrict__ crow, int K, int64_t p0) {
-    int lo = 0, hi = K;            // crow[lo] <= p0 < crow[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (crow[mid] <= p0) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+constexpr int KS_USEG = 16;        // pass C (its per-step state holds more registers)
 
 // Walk window w's positions (lane j); f(p, x) per position, close(c) when
 // cluster c's part of the window ends (only for clusters with positions in it),
@@ -666,7 +312,7 @@ __device__ inline bool ks_window_flagged(const int* __restrict__ flag, const int
     if (!flag) return true;
     const int c0 = ks_first_cluster(crow, K, p0);
     const int c1 = ks_first_cluster(crow, K, min(M, p0 + KS_W) - 1);
-    const int bit = min(31, (int)blockIdx.y);
+    const int bit = km_flag_bit((int)blockIdx.y * 64);
     int any = 0;
     for (int c = c0; c <= c1; c++) any |= (flag[c] >> bit) & 1;
     return any != 0;
@@ -691,7 +337,7 @@ __global__ __launch_bounds__(64) void ks_scan_kernel(const double* __restrict__ 
                                                      int K, int d, const double* __restrict__ carry,
                                                      double* __restrict__ sin, const int* __restrict__ flag) {
     const int c = blockIdx.x;
-    if (flag && !((flag[c] >> min(31, (int)blockIdx.y)) & 1)) return;
+    if (!km_flagged(flag, c, (int)blockIdx.y * 64)) return;
     const int j = blockIdx.y * 64 + threadIdx.x;
     const int64_t beg = crow[c], end = crow[c + 1];
     if (j >= d || beg == end) return;
@@ -759,17 +405,6 @@ __global__ __launch_bounds__(64) void ks_seg_kernel(const TX* __restrict__ X, in
 // flight meanwhile. Each lane keeps the sum it received; one check over the
 // lanes after the pass finds the first record whose summary does not apply,
 // whose positions are then walked with real adds before the pass resumes.
-__device__ inline double ks_rl(double v, int i) {
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, i);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), i);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-__device__ inline int64_t ks_rl(int64_t v, int i) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, i);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), i);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 
 // Lane form of ks_apply for the pass: every lane applies its record to its own
 // sum (the result where the summary does not apply is unused).
@@ -812,7 +447,7 @@ __global__ __launch_bounds__(64) void ks_compose_kernel(const TX* __restrict__ X
                                                         const uint8_t* __restrict__ mask) {
     const int j = blockIdx.x, c = blockIdx.y;
     const int lane = threadIdx.x;
-    if (flag && !((flag[c] >> min(31, j / 64)) & 1)) return;          // the flagged chains only
+    if (!km_flagged(flag, c, j)) return;                              // the flagged chains only
     const int64_t beg = crow[c], end = crow[c + 1];
     double s = carry ? carry[(size_t)c * d + j] : 0.0;
     if (beg < end) {
@@ -958,17 +593,318 @@ int launch_km_sums_seg(hipStream_t s, Pts X, int d, const int32_t* rows, const i
                        double* sums, int64_t* counts, const double* carry, const int64_t* carry_counts, void* ws,
                        const int* flag) {
     const KsWs w(ws, M, K, d);
-    if (X.f64) {
-        km_seg_records(s, X.d(), d, rows, crow, K, M, carry, flag, w);
-        km_seg_compose(s, X.d(), d, rows, crow, K, carry, flag, nullptr, w, sums);
-    } else {
-        km_seg_records(s, X.f(), d, rows, crow, K, M, carry, flag, w);
-        km_seg_compose(s, X.f(), d, rows, crow, K, carry, flag, nullptr, w, sums);
-    }
-    if (counts)
-        hipLaunchKernelGGL(km_counts_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, crow, K, carry_counts,
-                           counts);
+    with_rows(X, [&](auto* x) {
+        km_seg_records(s, x, d, rows, crow, K, M, carry, flag, w);
+        km_seg_compose(s, x, d, rows, crow, K, carry, flag, nullptr, w, sums);
+    });
+    km_counts(s, crow, K, carry_counts, counts);
     return kstatus("update.hip (segmented)");
+}
+
+// Column sums of a row-major [n][m] fp64 block V, each column one sequential
+// chain in row order from carry (NULL: 0) -- the same segmented evaluation
+// with the rows as one "cluster" (iota: 0..n-1, crow: {0, n}). The clustering
+// recommender's prediction chains of a huge cluster (recom.hip) take it.
+__global__ void seg_iota_kernel(int32_t* __restrict__ iota, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        iota[i] = (int32_t)i;
+}
+
+size_t seg_columns_ws_bytes(int64_t n, int K, int m) { return km_seg_ws_bytes(n, K, m); }
+
+int launch_seg_iota(hipStream_t s, int32_t* iota, int64_t n) {
+    hipLaunchKernelGGL(seg_iota_kernel, dim3(gsz(n, 256, 4096)), dim3(256), 0, s, iota, n);
+    return kstatus("update.hip (iota)");
+}
+
+// K blocks of rows [crow[k], crow[k+1]) of V [n][m], each column of each block
+// one chain from carry[k][e] (NULL: 0) into out [K][m].
+int launch_seg_columns(hipStream_t s, const double* V, int64_t n, int K, int m, const int32_t* iota,
+                       const int64_t* crow, const double* carry, double* out, void* ws) {
+    if (n <= 0 || m <= 0 || K <= 0) return 0;
+    const KsWs w(ws, n, K, m);
+    km_seg_records(s, V, m, iota, crow, K, n, carry, nullptr, w);
+    km_seg_compose(s, V, m, iota, crow, K, carry, nullptr, nullptr, w, out);
+    return kstatus("update.hip (column chains)");
+}
+
+// ------------------------------------------------------------------ fixed point
+// The reference's chain s = ((0 + x_1) + x_2) + ... rounds only when a partial
+// sum is not a double. Every partial sum -- of the chain, or of any subset of
+// the values in any order -- is an integer multiple of 2^q (q = the lowest set
+// bit over the chain's values) bounded by A = sum |x_i| < count * 2^t (t = the
+// highest bit position + 1), so when ceil(log2 count) + t - q <= 53 every such
+// partial is a double: no step of the chain rounds, and neither does any other
+// order of fp64 additions. The chain's result is then the exact sum, which
+// plain fp64 adds compute in any order -- per lane, then by fp64 atomics into
+// the (c, j) accumulator. q and t are tracked alongside (integer min / max), and
+// a chain whose test fails (or holding inf / nan) is flagged and recomputed in
+// the reference's order: by km_chain_lanes_kernel when it is short, else by
+// segments or, without a segment workspace, by km_chain16_kernel.
+// Work: waves stream 512 consecutive member positions of the cluster-sorted
+// list (lane = dimension), flushing their partial (one fp64 atomic add, two
+// integer atomics) whenever the cluster changes.
+constexpr int KMF_CH = 512;
+constexpr int KMF_BAD = 1 << 20;     // qmin marker of a chain that needs the sequential kernel
+
+struct KmFx {                        // per (c, j), zeroed / initialised by km_fx_init_kernel
+    double sum;
+    double asum;                     // sum of |x| (rounded: <= (1 + n 2^-53) times the true one)
+    int qmin;                        // lowest set-bit exponent, -KMF_BAD if flagged
+    int tmax;                        // highest bit position + 1
+};
+
+__global__ void km_fx_init_kernel(KmFx* __restrict__ acc, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { acc[i].sum = 0.0; acc[i].asum = 0.0; acc[i].qmin = 1 << 30; acc[i].tmax = -(1 << 30); }
+}
+
+// The never-rounds test of one (c, j): its cnt values are integer multiples of
+// 2^qmin below 2^tmax in magnitude, and their |x| sum to asum (fp64-rounded in
+// any order: within a factor 1 + cnt 2^-53 <= 1 + 2^-22 of the true sum for
+// cnt < 2^31). Every partial sum of any subset, in any order, is a multiple of
+// 2^qmin no larger in magnitude than the true sum of |x|: a double when that is
+// below 2^(53 + qmin). The count form (cnt 2^tmax) is the coarser bound of the
+// same kind; the |x| form passes on far more general fp32 chains (N(0,1) rows:
+// ~95 % vs ~64 % of the chains of 10K values).
+__device__ inline bool km_cert(int qmin, int tmax, int64_t cnt, double asum) {
+    if (qmin <= -KMF_BAD / 2) return false;        // inf / nan among the values
+    if (qmin > tmax) return true;                  // no nonzero value: the sum is +0
+    int lc = 0;
+    while (((int64_t)1 << lc) < cnt) lc++;         // ceil(log2 count)
+    // every partial below cnt 2^tmax <= 2^(lc + tmax): finite only if that is <=
+    // 2^1023 (else an any-order sum may overflow where the reference's chain stays
+    // finite, e.g. [M, -M, M] with M = 1.5 * 2^1023)
+    if (lc + tmax - qmin <= 53 && lc + tmax <= 1023) return true;
+    // the |x| bound (an overflowed asum is inf and fails; 2^(53 + qmin) may be inf)
+    return asum * (1.0 + 0x1p-20) < ldexp(1.0, min(53 + qmin, 1024));
+}
+
+// lowest set-bit exponent q and top t of a nonzero finite value; false for
+// +-0 (adds nothing: -0 + 0 = +0 either way) and inf / nan (sets bad)
+__device__ inline bool km_fx_bits(float v, int& q, int& t, bool& bad) {
+    const uint32_t b = __float_as_uint(v);
+    const int E = (int)((b >> 23) & 255u);
+    const uint32_t f = b & 0x7FFFFFu;
+    if (E == 255) { bad = true; return false; }
+    const uint32_t m = E ? (f | 0x800000u) : f;
+    if (m == 0) return false;
+    const int e = (E ? E : 1) - 150;
+    q = e + __builtin_ctz(m);
+    t = e + 32 - __builtin_clz(m);
+    return true;
+}
+__device__ inline bool km_fx_bits(double v, int& q, int& t, bool& bad) {
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    const int E = (int)((b >> 52) & 2047u);
+    const uint64_t f = b & 0xFFFFFFFFFFFFFull;
+    if (E == 2047) { bad = true; return false; }
+    const uint64_t m = E ? (f | (1ull << 52)) : f;
+    if (m == 0) return false;
+    const int e = (E ? E : 1) - 1075;
+    q = e + __builtin_ctzll(m);
+    t = e + 64 - __builtin_clzll(m);
+    return true;
+}
+
+// One chain's part of a walker's window: the partial sum (exact whenever the
+// chain's test passes), the |x| sum, q / t and the inf / nan mark, flushed into
+// the (c, j) accumulator when the cluster changes.
+struct KmPart {
+    double s = 0.0, as = 0.0;
+    int qmin = 1 << 30, tmax = -(1 << 30);
+    bool bad = false;
+    __device__ void reset() { *this = KmPart(); }
+    template <typename TX>
+    __device__ void add(TX v) {
+        int q, t;
+        if (!km_fx_bits(v, q, t, bad)) return;
+        qmin = min(qmin, q);
+        tmax = max(tmax, t);
+        s = __dadd_rn(s, (double)v);
+        as = __dadd_rn(as, fabs((double)v));
+    }
+    __device__ void flush(KmFx* a) const {
+        if (s != 0.0) atomicAdd(&a->sum, s);
+        if (as != 0.0) atomicAdd(&a->asum, as);
+        atomicMin(&a->qmin, bad ? -KMF_BAD : qmin);
+        atomicMax(&a->tmax, tmax);
+    }
+};
+
+template <typename TX>
+__global__ __launch_bounds__(64) void km_fx_kernel(const TX* __restrict__ X, int d, const int32_t* __restrict__ rows,
+                                                  const int64_t* __restrict__ crow, int K, int64_t M,
+                                                  KmFx* __restrict__ acc) {
+    const int64_t p0 = (int64_t)blockIdx.x * KMF_CH;
+    if (p0 >= M) return;
+    const int64_t p1 = min(M, p0 + KMF_CH);
+    const int j = blockIdx.y * 64 + threadIdx.x;
+    const bool on = j < d;
+    const __attribute__((address_space(4))) int32_t* r4 = (const __attribute__((address_space(4))) int32_t*)rows;
+    int c = ks_first_cluster(crow, K, p0);
+    int64_t cend = crow[c + 1];
+    KmPart part;
+    for (int64_t p = p0; p < p1; p += 16) {
+        TX v[16];
+#pragma unroll
+        for (int u = 0; u < 16; u++) v[u] = (on && p + u < p1) ? X[(int64_t)r4[p + u] * d + j] : (TX)0;
+#pragma unroll
+        for (int u = 0; u < 16; u++) {
+            if (p + u >= p1) break;
+            while (p + u >= cend) {              // cluster boundary: flush, move on (skipping empty clusters)
+                if (on) part.flush(acc + (size_t)c * d + j);
+                part.reset();
+                c++;
+                cend = crow[c + 1];
+            }
+            part.add(v[u]);
+        }
+    }
+    if (on) part.flush(acc + (size_t)c * d + j);
+}
+
+// fp32 rows with d % 128 == 0: a wave reads whole 512-B row slices (two
+// dims per lane, float2), half the load instructions of km_fx_kernel's 256-B
+// half-rows for the same gather.
+constexpr int KMF2_U = 16;       // rows in flight per wave
+__global__ __launch_bounds__(64) void km_fx2_kernel(const float* __restrict__ X, int d, const int32_t* __restrict__ rows,
+                                                    const int64_t* __restrict__ crow, int K, int64_t M,
+                                                    KmFx* __restrict__ acc) {
+    const int64_t p0 = (int64_t)blockIdx.x * KMF_CH;
+    if (p0 >= M) return;
+    const int64_t p1 = min(M, p0 + KMF_CH);
+    const int j = blockIdx.y * 128 + 2 * threadIdx.x;
+    const __attribute__((address_space(4))) int32_t* r4 = (const __attribute__((address_space(4))) int32_t*)rows;
+    int c = ks_first_cluster(crow, K, p0);
+    int64_t cend = crow[c + 1];
+    KmPart part0, part1;
+    for (int64_t p = p0; p < p1; p += KMF2_U) {
+        float2 v[KMF2_U];
+#pragma unroll
+        for (int u = 0; u < KMF2_U; u++)
+            v[u] = p + u < p1 ? *reinterpret_cast<const float2*>(X + (int64_t)r4[p + u] * d + j) : make_float2(0.f, 0.f);
+#pragma unroll
+        for (int u = 0; u < KMF2_U; u++) {
+            if (p + u >= p1) break;
+            while (p + u >= cend) {              // cluster boundary: flush, move on (skipping empty clusters)
+                part0.flush(acc + (size_t)c * d + j);
+                part1.flush(acc + (size_t)c * d + j + 1);
+                part0.reset();
+                part1.reset();
+                c++;
+                cend = crow[c + 1];
+            }
+            part0.add(v[u].x);
+            part1.add(v[u].y);
+        }
+    }
+    part0.flush(acc + (size_t)c * d + j);
+    part1.flush(acc + (size_t)c * d + j + 1);
+}
+
+// Every (c, j) accumulator of acc [K][d] from the M member positions.
+static void km_fx_accumulate(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K, int64_t M,
+                             KmFx* acc) {
+    const int64_t n = (int64_t)K * d;
+    hipLaunchKernelGGL(km_fx_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, n);
+    if (M <= 0) return;
+    const unsigned nch = (unsigned)((M + KMF_CH - 1) / KMF_CH);
+    if (!X.f64 && d % 128 == 0)
+        hipLaunchKernelGGL(km_fx2_kernel, dim3(nch, (unsigned)(d / 128)), dim3(64), 0, s, X.f(), d, rows, crow, K, M, acc);
+    else
+        with_rows(X, [&](auto* x) {
+            hipLaunchKernelGGL(km_fx_kernel, dim3(nch, (unsigned)((d + 63) / 64)), dim3(64), 0, s, x, d, rows, crow, K, M,
+                               acc);
+        });
+}
+
+// Per (c, j): the exact sum if the chain provably never rounds, else a flag for
+// the sequential kernel. carry (sharded exact mode): the chain starts from it.
+__global__ void km_fx_finalize_kernel(const KmFx* __restrict__ acc, const int64_t* __restrict__ crow, int K, int d,
+                                      const double* __restrict__ carry, const int64_t* __restrict__ carry_counts,
+                                      double* __restrict__ sums, int* __restrict__ flag,
+                                      unsigned long long* __restrict__ stat, int32_t* __restrict__ lanes,
+                                      unsigned int* __restrict__ lane_cnt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)K * d) return;
+    const int c = (int)(i / d);
+    const KmFx a = acc[i];
+    int64_t cnt = crow[c + 1] - crow[c];
+    double s = a.sum, as = a.asum;
+    int qmin = a.qmin, tmax = a.tmax;
+    bool ok = qmin > -KMF_BAD / 2;
+    if (carry && ok) {                  // the carried running sum is one more value of the chain
+        const double s0 = carry[i];
+        cnt += 1;
+        int q, t;
+        bool bad = false;
+        if (km_fx_bits(s0, q, t, bad)) {
+            qmin = min(qmin, q);
+            tmax = max(tmax, t);
+            s = __dadd_rn(s0, s);
+            as = __dadd_rn(as, fabs(s0));
+        }
+        if (bad) ok = false;
+    }
+    ok = ok && km_cert(qmin, tmax, cnt, as);
+    // a flagged chain: one lane of km_chain_lanes_kernel when it is short (and
+    // a lane list is given), else its (c, 64-dim block) to the block kernels
+    const bool lane_chain = !ok && lanes && cnt <= KM_LANE_MAX;
+    if (ok) sums[i] = s;
+    else if (!lane_chain) atomicOr(flag + c, 1 << km_flag_bit((int)(i % d)));
+    if (lanes) seg_append(lane_chain, (int32_t)i, lane_cnt, lanes, (int)(threadIdx.x & 63));
+    if (stat) {
+        const unsigned long long nb = __ballot(!ok);
+        if (nb && (threadIdx.x & 63) == __builtin_ctzll(nb)) atomicAdd(stat, (unsigned long long)__popcll(nb));
+    }
+}
+
+// The fixed point's workspace: accumulators [K][d] | flag [K] | lane count
+// (64 B) | lane list [K * d].
+struct KmFxWs {
+    KmFx* acc;
+    int* flag;
+    unsigned int* lane_cnt;
+    int32_t* lanes;
+    static size_t bytes(int K, int d) {
+        const size_t n = (size_t)K * d;
+        return n * sizeof(KmFx) + (size_t)K * 4 + 64 + n * 4 + 64;
+    }
+    static size_t flag_bytes(int K) { return (size_t)K * 4 + 64; }      // the flags and the lane count, contiguous
+    KmFxWs(void* ws, int K, int d) {
+        acc = reinterpret_cast<KmFx*>(ws);
+        flag = reinterpret_cast<int*>(acc + (size_t)K * d);
+        lane_cnt = reinterpret_cast<unsigned int*>(flag + K);
+        lanes = reinterpret_cast<int32_t*>(lane_cnt + 16);
+    }
+};
+
+size_t km_fx_ws_bytes(int K, int d) { return KmFxWs::bytes(K, d); }
+
+int launch_km_sums_fx(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K, int64_t M,
+                      double* sums, int64_t* counts, const double* carry, const int64_t* carry_counts, void* ws,
+                      unsigned long long* stat, void* seg_ws) {
+    const KmFxWs w(ws, K, d);
+    const int64_t n = (int64_t)K * d;
+    (void)hipMemsetAsync(w.flag, 0, KmFxWs::flag_bytes(K), s);
+    km_fx_accumulate(s, X, d, rows, crow, K, M, w.acc);
+    // the lane form for short flagged chains where the segment form runs
+    hipLaunchKernelGGL(km_fx_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.acc, crow, K, d, carry,
+                       carry_counts, sums, w.flag, stat, seg_ws ? w.lanes : nullptr, w.lane_cnt);
+    int rc;
+    if (seg_ws) {
+        km_chain_lanes(s, X, d, rows, crow, K, w.lanes, w.lane_cnt, carry, sums);
+        // the flagged chains by binade segments (every window of theirs in
+        // parallel; the sequential form's time was set by the longest chain:
+        // 20 ms for a 206K-member cluster of full-mantissa rows)
+        rc = launch_km_sums_seg(s, X, d, rows, crow, K, M, sums, nullptr, carry, nullptr, seg_ws, w.flag);
+    } else {
+        rc = launch_km_chain(s, X, d, rows, crow, K, sums, nullptr, carry, nullptr, w.flag);
+    }
+    if (rc) return rc;
+    km_counts(s, crow, K, carry_counts, counts);
+    return kstatus("update.hip (fixed point)");
 }
 
 // ------------------------------------------------------------------ grid test
@@ -1006,47 +942,19 @@ __global__ __launch_bounds__(256) void grid_bits_kernel(const TX* __restrict__ X
 }
 int launch_grid_bits(hipStream_t s, Pts X, int64_t n, int* qt) {
     hipLaunchKernelGGL(grid_bits_init_kernel, dim3(1), dim3(1), 0, s, qt);
-    if (n > 0) {
-        if (X.f64) hipLaunchKernelGGL(grid_bits_kernel<double>, dim3(gsz(n, 256, 4096)), dim3(256), 0, s, X.d(), n, qt);
-        else hipLaunchKernelGGL(grid_bits_kernel<float>, dim3(gsz(n, 256, 4096)), dim3(256), 0, s, X.f(), n, qt);
-    }
+    if (n > 0)
+        with_rows(X, [&](auto* x) {
+            hipLaunchKernelGGL(grid_bits_kernel, dim3(gsz(n, 256, 4096)), dim3(256), 0, s, x, n, qt);
+        });
     return kstatus("update.hip (grid bits)");
 }
 bool grid_exact_squares(const int* qt_host) {
     return qt_host[2] == 0 && (qt_host[0] > qt_host[1] || (qt_host[1] - qt_host[0] <= 25 && qt_host[0] >= -460));
 }
 
-// ------------------------------------------------------------------ long chains
-// Column sums of a row-major [n][m] fp64 block V, each column one sequential
-// chain in row order from carry (NULL: 0) -- the same segmented evaluation
-// with the rows as one "cluster" (iota: 0..n-1, crow: {0, n}). The clustering
-// recommender's prediction chains of a huge cluster (recom.hip) take it.
-__global__ void seg_iota_kernel(int32_t* __restrict__ iota, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        iota[i] = (int32_t)i;
-}
-
-size_t seg_columns_ws_bytes(int64_t n, int K, int m) { return km_seg_ws_bytes(n, K, m); }
-
-int launch_seg_iota(hipStream_t s, int32_t* iota, int64_t n) {
-    hipLaunchKernelGGL(seg_iota_kernel, dim3(gsz(n, 256, 4096)), dim3(256), 0, s, iota, n);
-    return kstatus("update.hip (iota)");
-}
-
-// K blocks of rows [crow[k], crow[k+1]) of V [n][m], each column of each block
-// one chain from carry[k][e] (NULL: 0) into out [K][m].
-int launch_seg_columns(hipStream_t s, const double* V, int64_t n, int K, int m, const int32_t* iota,
-                       const int64_t* crow, const double* carry, double* out, void* ws) {
-    if (n <= 0 || m <= 0 || K <= 0) return 0;
-    const KsWs w(ws, n, K, m);
-    km_seg_records(s, V, m, iota, crow, K, n, carry, nullptr, w);
-    km_seg_compose(s, V, m, iota, crow, K, carry, nullptr, nullptr, w, out);
-    return kstatus("update.hip (column chains)");
-}
-
 // ------------------------------------------------------------------ sharded form
 // The reference's chain over row shards (lshkm_kmeans_shard_*, include/lshkm.h):
-// every rank forms its partial sums by the parallel form above and reports its
+// every rank forms its partial sums by the fixed point above and reports its
 // values' q / t / sum |x|; after the exchange (partial sums gathered, q MIN, t
 // MAX, |x| sums and counts SUM) the never-rounds test runs on the GLOBAL values.
 // Where it passes, every partial sum of any subset of the chain's values, in
@@ -1087,27 +995,19 @@ __global__ void km_shard_certify_kernel(const double* __restrict__ gathered, int
     if (start) start[i] = pre;
     sums_out[i] = tot;                           // the chain's value where ok; the carry replaces the rest
     mask[i] = ok ? 0 : (lane_chain ? 2 : 1);     // 1: segment records, 2: one lane (km_chain_lanes_kernel)
-    if (!ok && !lane_chain) atomicOr(flag + c, 1 << min(31, (int)(i % d) / 64));
+    if (!ok && !lane_chain) atomicOr(flag + c, 1 << km_flag_bit((int)(i % d)));
     const unsigned long long nb = __ballot(!ok);
     if (nb && (threadIdx.x & 63) == __builtin_ctzll(nb)) atomicAdd(nflag, (unsigned long long)__popcll(nb));
 }
 
+// ws: the fixed point's workspace (km_fx_ws_bytes)
 int launch_km_shard_begin(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K, int64_t M,
                           double* sums, double* asum, int32_t* qt, int64_t* counts, void* ws) {
-    KmFx* acc = reinterpret_cast<KmFx*>(ws);      // the context's k-means workspace (km_fx_ws_bytes)
+    const KmFxWs w(ws, K, d);
     const int64_t n = (int64_t)K * d;
-    hipLaunchKernelGGL(km_fx_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, n);
-    const int jb = (d + 63) / 64;
-    const dim3 fgrid((unsigned)((M + KMF_CH - 1) / KMF_CH), (unsigned)jb);
-    if (M > 0) {
-        if (X.f64) hipLaunchKernelGGL(km_fx_kernel<double>, fgrid, dim3(64), 0, s, X.d(), d, rows, crow, K, M, acc);
-        else if (d % 128 == 0)
-            hipLaunchKernelGGL(km_fx2_kernel, dim3(fgrid.x, (unsigned)(d / 128)), dim3(64), 0, s, X.f(), d, rows, crow, K, M,
-                               acc);
-        else hipLaunchKernelGGL(km_fx_kernel<float>, fgrid, dim3(64), 0, s, X.f(), d, rows, crow, K, M, acc);
-    }
-    hipLaunchKernelGGL(km_shard_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, n, sums, asum, qt);
-    hipLaunchKernelGGL(km_counts_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, crow, K, nullptr, counts);
+    km_fx_accumulate(s, X, d, rows, crow, K, M, w.acc);
+    hipLaunchKernelGGL(km_shard_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.acc, n, sums, asum, qt);
+    km_counts(s, crow, K, nullptr, counts);
     return kstatus("update.hip (shard begin)");
 }
 
@@ -1122,12 +1022,24 @@ int launch_km_shard_certify(hipStream_t s, const double* gathered, int world, in
     return kstatus("update.hip (shard certify)");
 }
 
-// [lane count (64 B) | lane list (K * d int32), 256-B aligned] then the
-// begin pass's accumulators or the segment records
-static size_t km_shard_lane_bytes(int K, int d) { return ((size_t)K * d * 4 + 64 + 255) / 256 * 256; }
-size_t km_shard_ws_bytes(int64_t M, int K, int d) {
-    return km_shard_lane_bytes(K, d) + std::max((size_t)K * d * sizeof(KmFx) + 64, km_seg_ws_bytes(M, K, d));
-}
+// The caller's workspace of prepare / chain: lane count (64 B) | lane list
+// [K * d], padded to 256 B | the segment workspace (sized to hold a set of
+// accumulators as well).
+struct KmShardWs {
+    unsigned int* lane_cnt;
+    int32_t* lanes;
+    KsWs seg;
+    static size_t lane_bytes(int K, int d) { return ((size_t)K * d * 4 + 64 + 255) / 256 * 256; }
+    static size_t bytes(int64_t M, int K, int d) {
+        return lane_bytes(K, d) + std::max((size_t)K * d * sizeof(KmFx) + 64, km_seg_ws_bytes(M, K, d));
+    }
+    KmShardWs(void* ws, int64_t M, int K, int d)
+        : lane_cnt(reinterpret_cast<unsigned int*>(ws)),
+          lanes(reinterpret_cast<int32_t*>(lane_cnt + 16)),
+          seg(reinterpret_cast<char*>(ws) + lane_bytes(K, d), M, K, d) {}
+};
+
+size_t km_shard_ws_bytes(int64_t M, int K, int d) { return KmShardWs::bytes(M, K, d); }
 
 __global__ void km_lane_list_kernel(const uint8_t* __restrict__ mask, int64_t n, int32_t* __restrict__ list,
                                     unsigned int* __restrict__ cnt) {
@@ -1141,14 +1053,11 @@ __global__ void km_lane_list_kernel(const uint8_t* __restrict__ mask, int64_t n,
 // rank (passes A-C, carry-free: all ranks at once).
 int launch_km_shard_prepare(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K, int64_t M,
                             const double* start, const int* flag, const uint8_t* mask, void* ws) {
-    unsigned int* lane_cnt = reinterpret_cast<unsigned int*>(ws);
-    int32_t* lanes = reinterpret_cast<int32_t*>(lane_cnt + 16);
+    const KmShardWs w(ws, M, K, d);
     const int64_t n = (int64_t)K * d;
-    if (hipMemsetAsync(lane_cnt, 0, 64, s) != hipSuccess) return kstatus("update.hip (shard prepare memset)");
-    hipLaunchKernelGGL(km_lane_list_kernel, dim3(gsz(n, 256, 4096)), dim3(256), 0, s, mask, n, lanes, lane_cnt);
-    const KsWs w(reinterpret_cast<char*>(ws) + km_shard_lane_bytes(K, d), M, K, d);
-    if (X.f64) km_seg_records(s, X.d(), d, rows, crow, K, M, start, flag, w);
-    else km_seg_records(s, X.f(), d, rows, crow, K, M, start, flag, w);
+    if (hipMemsetAsync(w.lane_cnt, 0, 64, s) != hipSuccess) return kstatus("update.hip (shard prepare memset)");
+    hipLaunchKernelGGL(km_lane_list_kernel, dim3(gsz(n, 256, 4096)), dim3(256), 0, s, mask, n, w.lanes, w.lane_cnt);
+    with_rows(X, [&](auto* x) { km_seg_records(s, x, d, rows, crow, K, M, start, flag, w.seg); });
     return kstatus("update.hip (shard prepare)");
 }
 
@@ -1156,23 +1065,14 @@ int launch_km_shard_prepare(hipStream_t s, Pts X, int d, const int32_t* rows, co
 // rank's running sums; NULL on the first rank: from 0), written where mask is set.
 int launch_km_shard_chain(hipStream_t s, Pts X, int d, const int32_t* rows, const int64_t* crow, int K, int64_t M,
                           const int* flag, const uint8_t* mask, const double* carry, void* ws, double* sums) {
-    const unsigned int* lane_cnt = reinterpret_cast<const unsigned int*>(ws);
-    const int32_t* lanes = reinterpret_cast<const int32_t*>(lane_cnt + 16);
-    const int64_t n = (int64_t)K * d;
-    const KsWs w(reinterpret_cast<char*>(ws) + km_shard_lane_bytes(K, d), M, K, d);
+    const KmShardWs w(ws, M, K, d);
     // mask 1: the segment composition (flag bits), mask 2: one lane per chain
-    if (X.f64) {
-        km_seg_compose(s, X.d(), d, rows, crow, K, carry, flag, mask, w, sums);
-        hipLaunchKernelGGL(km_chain_lanes_kernel<double>, dim3(gsz(n, 1, 8192)), dim3(64), 0, s, X.d(), d, rows, crow,
-                           lanes, lane_cnt, carry, sums);
-    } else {
-        km_seg_compose(s, X.f(), d, rows, crow, K, carry, flag, mask, w, sums);
-        hipLaunchKernelGGL(km_chain_lanes_kernel<float>, dim3(gsz(n, 1, 8192)), dim3(64), 0, s, X.f(), d, rows, crow,
-                           lanes, lane_cnt, carry, sums);
-    }
+    with_rows(X, [&](auto* x) { km_seg_compose(s, x, d, rows, crow, K, carry, flag, mask, w.seg, sums); });
+    km_chain_lanes(s, X, d, rows, crow, K, w.lanes, w.lane_cnt, carry, sums);
     return kstatus("update.hip (shard chain)");
 }
 
+// ------------------------------------------------------------------ finalize
 // One wave per cluster: divide (unless empty), then the reference's movement
 // test with euclideanDistance(new, old) or cosineDistance(new, old).
 __global__ __launch_bounds__(64) void km_finalize_kernel(const double* __restrict__ sums, const int64_t* __restrict__ counts,

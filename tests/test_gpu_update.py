@@ -83,6 +83,27 @@ def test_parallel_sums_match_chains(ctx, sctx, sw, kind, monkeypatch):
         assert np.array_equal(bits(Cn), Co.view(np.uint64))
 
 
+def test_f32_flagged_chains_without_segment_workspace(ctx, sctx, sw, monkeypatch):
+    # K > 65535 gives no segment workspace (km_sums), so the fp32 chains the
+    # never-rounds test flags go to the sequential kernel by their flag bits.
+    # Eight clusters of ~6,600 values spanning > 100 binades: each of their 8 x 20
+    # chains fails both bounds of km_cert (restated in numpy on these very
+    # values: 160 of 160 fail).
+    rng = np.random.default_rng(47)
+    N, d, K = 70_000, 20, 65_600
+    Xh = (rng.standard_normal((N, d)) * 10.0 ** rng.integers(-30, 8, (N, d))).astype(np.float32)
+    a = rng.integers(0, K, N).astype(np.int32)
+    big = np.array([0, 7, 4097, 32768, 65535, 65536, 65590, K - 1], np.int32)
+    a[: N * 3 // 4] = big[rng.integers(0, 8, N * 3 // 4)]
+    X, A = to_dev(ctx, Xh), to_dev(ctx, a)
+    C = to_dev(ctx, rng.standard_normal((K, d)))
+    seq0 = ctx.stat(lshkm.STAT_KM_SEQ)
+    Cn, cnt = both(ctx, X, A, C, monkeypatch, (sw, sctx))
+    assert ctx.stat(lshkm.STAT_KM_SEQ) - seq0 >= 8 * d
+    Co, co, _ = oracle.kmeans_update(Xh, a, C.cpu().numpy(), "euclidean", 0.0)
+    assert np.array_equal(bits(Cn), Co.view(np.uint64)) and np.array_equal(cnt.cpu().numpy(), co)
+
+
 def test_parallel_sums_carry_mode(ctx):
     # sharded exact mode: the chains continue shard to shard; parallel == chain
     rng = np.random.default_rng(2)
@@ -137,12 +158,10 @@ def test_f64_segmented_sums_match_chains(ctx, sctx, sw, kind, path, monkeypatch)
     else:
         monkeypatch.setenv("LSHKM_KM_PATH", path)
         Cn, cnt, _ = sw.kmeans_update(sctx, X, A, C, "euclidean", 0.0)
-    # reference runs: the sequential chains in their older 64-dim form, and the oracle
+    # reference runs: the sequential chains, and the oracle
     monkeypatch.setenv("LSHKM_KM_PATH", "chain")
-    monkeypatch.setenv("LSHKM_KM_CHAIN", "64")
     Cs, cs, _ = sw.kmeans_update(sctx, X, A, C, "euclidean", 0.0)
     monkeypatch.delenv("LSHKM_KM_PATH")
-    monkeypatch.delenv("LSHKM_KM_CHAIN")
     assert np.array_equal(cnt.cpu().numpy(), cs.cpu().numpy())
     assert np.array_equal(bits(Cn), bits(Cs))
     Co, _, _ = oracle.kmeans_update(Xh, a, C.cpu().numpy(), "euclidean", 0.0)
