@@ -6,6 +6,7 @@
 //   Tweet::Tweet               lib/data_structures/tweet.cpp:11-42
 //   the tweet map              main.cpp:128-132
 //   tweets_to_user_vectors     lib/crypto_rec.hpp:84-103 (the user map's order)
+//   print_recommendations      main.cpp:557-569 and the blocks' lines, :151-173
 //
 // Everything after main.cpp:132 iterates std::unordered_map<std::string, ...>,
 // so the order of the tweets and of the users is libstdc++'s hash order. It is
@@ -16,6 +17,7 @@
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -118,6 +120,7 @@ struct lshkm_tweets_s {
     // users in the iteration order of the reference's `user_map`
     std::vector<std::string> uid;
     std::unordered_map<std::string, int32_t> number;      // tweet ID -> its number
+    std::vector<std::vector<std::string>> coin_fields;    // query_crypto: the coin file's lines, split
 };
 
 extern "C" {
@@ -150,10 +153,13 @@ int lshkm_tweets_read(const char* input_path, const char* lexicon_path, const ch
     // same matches, by variation.
     std::unordered_map<std::string, std::vector<int32_t>> coin_of;
     int crypto_num = 0;
+    std::vector<std::vector<std::string>> coin_fields;
     {
         const std::vector<std::string> ls = lines_of(q_data);
+        coin_fields.reserve(ls.size());
         for (const std::string& l : ls) {
-            for (const std::string& var : str_vector(l, delimiter)) {
+            coin_fields.push_back(str_vector(l, delimiter));
+            for (const std::string& var : coin_fields.back()) {
                 std::vector<int32_t>& v = coin_of[var];
                 if (v.empty() || v.back() != crypto_num) v.push_back(crypto_num);
             }
@@ -216,6 +222,7 @@ int lshkm_tweets_read(const char* input_path, const char* lexicon_path, const ch
     lshkm_tweets t = new lshkm_tweets_s();
     t->P = P;
     t->crypto_num = crypto_num;
+    t->coin_fields.swap(coin_fields);
     const size_t T = tweets.size();
     t->tid.reserve(T);
     t->score.reserve(T);
@@ -306,6 +313,64 @@ int lshkm_tweets_match(lshkm_tweets t, const char* id_bytes, const int64_t* id_o
         auto it = t->number.find(id);
         tweet_of_row_host[i] = it == t->number.end() ? -1 : it->second;
     }
+    return 0;
+}
+
+// print_recommendations' choice (main.cpp:563-566); a line without a field has no name
+static const std::string& coin_name(const lshkm_tweets_s* t, int32_t coin, int name_index) {
+    static const std::string none;
+    const std::vector<std::string>& f = t->coin_fields[(size_t)coin];
+    if (f.size() > (size_t)name_index) return f[(size_t)name_index];
+    return f.empty() ? none : f[0];
+}
+
+int lshkm_tweets_coin_names(lshkm_tweets t, int name_index, char* bytes_host, int64_t* offsets_host) {
+    LSHKM_CHECK(t && name_index >= 0 && offsets_host, LSHKM_ERR_ARG, "bad arguments");
+    int64_t o = 0;
+    offsets_host[0] = 0;
+    for (int32_t c = 0; c < t->crypto_num; c++) {
+        const std::string& s = coin_name(t, c, name_index);
+        if (bytes_host) std::memcpy(bytes_host + o, s.data(), s.size());
+        o += (int64_t)s.size();
+        offsets_host[c + 1] = o;
+    }
+    return 0;
+}
+
+int lshkm_recom_write(lshkm_tweets t, int name_index, const char* path, int append, const char* title,
+                      const char* user_id_bytes, const int64_t* user_id_offsets, int64_t nq, const int32_t* top_host,
+                      int n_top, const uint8_t* skip_host, int64_t elapsed_ms) {
+    LSHKM_CHECK(t && name_index >= 0 && path && title && nq >= 0 && n_top >= 0, LSHKM_ERR_ARG, "bad arguments");
+    LSHKM_CHECK(nq == 0 || (user_id_offsets && (top_host || n_top == 0)), LSHKM_ERR_ARG, "bad arguments");
+    // everything is checked before the file is touched
+    for (int64_t q = 0; q < nq; q++) {
+        LSHKM_CHECK(user_id_offsets[q + 1] >= user_id_offsets[q] && (user_id_bytes || user_id_offsets[q + 1] == user_id_offsets[q]),
+                    LSHKM_ERR_ARG, "bad ID offsets");
+        if (skip_host && skip_host[q]) continue;
+        for (int j = 0; j < n_top; j++) {
+            const int32_t c = top_host[q * n_top + j];
+            LSHKM_CHECK(c >= 0 && c < t->crypto_num, LSHKM_ERR_ARG,
+                        "user " + std::to_string(q) + ": coin index " + std::to_string(c) + " outside [0, " +
+                            std::to_string(t->crypto_num) + ")");
+        }
+    }
+    std::string out = std::string(title) + "\n";
+    for (int64_t q = 0; q < nq; q++) {
+        if (skip_host && skip_host[q]) continue;
+        if (user_id_offsets[q + 1] > user_id_offsets[q])
+            out.append(user_id_bytes + user_id_offsets[q], (size_t)(user_id_offsets[q + 1] - user_id_offsets[q]));
+        for (int j = 0; j < n_top; j++) {
+            out.push_back(' ');
+            out += coin_name(t, top_host[q * n_top + j], name_index);
+        }
+        out.push_back('\n');
+    }
+    out += "Execution Time: " + std::to_string((long long)elapsed_ms) + "\n";
+    FILE* f = fopen(path, append ? "ab" : "wb");
+    LSHKM_CHECK(f, LSHKM_ERR_ARG, std::string("cannot open ") + path + " for writing");
+    const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+    const bool closed = fclose(f) == 0;
+    LSHKM_CHECK(ok && closed, LSHKM_ERR_ARG, std::string("cannot write ") + path);
     return 0;
 }
 

@@ -117,6 +117,8 @@ def lib():
             "lshkm_tweets_ids": (i32, [vp, vp, vp]),
             "lshkm_tweets_user_ids": (i32, [vp, vp, vp]),
             "lshkm_tweets_match": (i32, [vp, vp, vp, i64, vp]),
+            "lshkm_tweets_coin_names": (i32, [vp, i32, vp, vp]),
+            "lshkm_recom_write": (i32, [vp, i32, C.c_char_p, i32, C.c_char_p, C.c_char_p, vp, i64, vp, i32, vp, i64]),
             "lshkm_tweets_free": (i32, [vp]),
             "lshkm_user_sums": (i32, [vp, vp, vp, i64, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp]),
             "lshkm_user_finish": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, C.POINTER(i64)]),
@@ -614,6 +616,17 @@ class Tweets:
         _ck(lib().lshkm_tweets_match(self.h, C.c_char_p(bytes(raw)), _np_ptr(off), n, _np_ptr(out)))
         return out
 
+    def coin_names(self, name_index=4):
+        """The name print_recommendations (main.cpp:557-569) prints for every
+        coin: field name_index of its line of the coin file where the line has
+        that many fields, else field 0 (lshkm_tweets_coin_names)."""
+        off = np.empty(self.crypto_num + 1, np.int64)
+        _ck(lib().lshkm_tweets_coin_names(self.h, name_index, None, _np_ptr(off)))
+        raw = C.create_string_buffer(max(int(off[-1]), 1))
+        _ck(lib().lshkm_tweets_coin_names(self.h, name_index, raw, _np_ptr(off)))
+        b = raw.raw
+        return [b[off[i]:off[i + 1]].decode() for i in range(self.crypto_num)]
+
     def close(self):
         if self.h:
             lib().lshkm_tweets_free(self.h)
@@ -624,6 +637,26 @@ class Tweets:
             self.close()
         except Exception:
             pass
+
+
+def recom_write(tweets, path, title, user_ids, top, skip=None, elapsed_ms=0, append=True, name_index=4):
+    """One block of the program's output file (lshkm_recom_write; main.cpp:151-173
+    and print_recommendations, :557-569): the title, `id name name ...` for
+    every user that is not skipped, `Execution Time: <elapsed_ms>`. user_ids: a
+    list of str / bytes or the (bytes, offsets) pair; top [nq][n_top] coin
+    indexes and skip [nq] on the host (numpy). append=False truncates path."""
+    raw, off = user_ids if isinstance(user_ids, tuple) else _pack_ids(user_ids)
+    off = np.ascontiguousarray(off, np.int64)
+    nq = off.shape[0] - 1
+    top = np.ascontiguousarray(top, np.int32)
+    if top.ndim != 2 or top.shape[0] != nq:
+        raise LshkmError(f"recom_write: top must be [{nq}][n_top], got {top.shape}")
+    sk = None if skip is None else np.ascontiguousarray(skip).astype(np.uint8)
+    if sk is not None and sk.shape != (nq,):
+        raise LshkmError(f"recom_write: skip must hold {nq} flags")
+    _ck(lib().lshkm_recom_write(tweets.h, name_index, os.fsencode(path), int(bool(append)), title.encode(),
+                                C.c_char_p(bytes(raw)), _np_ptr(off), nq, _np_ptr(top), top.shape[1], _np_ptr(sk),
+                                int(elapsed_ms)))
 
 
 def user_sums(ctx, tw, grp, table, G, C, carry=None):

@@ -837,6 +837,26 @@ int lshkm_tweets_user_ids(lshkm_tweets t, char* bytes_host, int64_t* offsets_hos
  * layout): tweet_of_row_host[i] = the tweet's number, or -1. */
 int lshkm_tweets_match(lshkm_tweets t, const char* id_bytes, const int64_t* id_offsets, int64_t n,
                        int32_t* tweet_of_row_host);
+/* The printers' host side (main.cpp:557-569, :151-173). The name
+ * print_recommendations prints for every line of the coin file (query_crypto):
+ * field name_index where the line has more than name_index fields, else field 0
+ * (main.cpp:563-566; the program passes 4); a line without any field, where the
+ * reference reads out of bounds, has the empty name. bytes_host concatenated
+ * (NULL: the offsets alone, for the size), offsets_host [crypto_num + 1]. */
+int lshkm_tweets_coin_names(lshkm_tweets t, int name_index, char* bytes_host, int64_t* offsets_host);
+/* One block of the program's output file: the title line (main.cpp:151, :197,
+ * :242, :336), then for every user q with skip_host[q] == 0 (NULL: none
+ * skipped), in order, print_recommendations' line (main.cpp:557-569) -- the ID,
+ * then " " + the name of coin top_host[q][j] for j < n_top, then "\n" -- and
+ * "Execution Time: <elapsed_ms>" (main.cpp:173), every line ended by '\n'.
+ * append == 0 truncates path (the ofstream of main.cpp:140), else the block is
+ * added at its end. get_top_N_recom's resize(N) padding arrives as index 0 and
+ * prints coin 0's name, as in the reference. An index outside [0, crypto_num)
+ * of a user that is not skipped is LSHKM_ERR_ARG, found before the file is
+ * opened; a path that cannot be opened or written is LSHKM_ERR_ARG too. */
+int lshkm_recom_write(lshkm_tweets t, int name_index, const char* path, int append, const char* title,
+                      const char* user_id_bytes, const int64_t* user_id_offsets, int64_t nq, const int32_t* top_host,
+                      int n_top, const uint8_t* skip_host, int64_t elapsed_ms);
 int lshkm_tweets_free(lshkm_tweets t);
 
 /* The update loop both functions share (crypto_rec.hpp:97-102, :166-171) over a

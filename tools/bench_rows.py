@@ -7,6 +7,7 @@ thread, OMP_NUM_THREADS=1, kind "port") on a bounded sample of the same
 workload, scaled to the row's unit. Prints one JSON line per row.
 
     python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64,cv,lshpc] [--no-cpu]
+    python tools/bench_rows.py --rows main_program --main-dir DIR [--main-ref-seconds S]
 """
 import argparse
 import json
@@ -121,6 +122,8 @@ def main():
     ap.add_argument("--cv-sizes", default="20000,1000000", help="user counts of the cv row")
     ap.add_argument("--lshpc-sizes", default="20000,200000", help="user counts of the lshpc row")
     ap.add_argument("--pam-shapes", default="100000x16,1000000x256", help="NxK list of the pam row (d = 128)")
+    ap.add_argument("--main-dir", default="", help="main_program row: the directory gen_main_golden --time wrote")
+    ap.add_argument("--main-ref-seconds", type=float, default=0.0, help="main_program row: the reference's seconds")
     a = ap.parse_args()
     rows = set(a.rows.split(","))
     ctx = lshkm.Context(0)
@@ -494,6 +497,40 @@ def main():
                 "note": "query + exclusion + p_closest against lshkm_lsh_p_closest on the same handle; HIP events, "
                         "median of 10 after 3 warm-ups; stats per call"}), flush=True)
             del W, Q, lsh, out
+
+    if "main_program" in rows:   # the whole program (main.cpp:36-390) on the files of gen_main_golden --time FACTOR DIR
+        sys.path.insert(0, os.path.join(ROOT, "crypto-recommendation_amd"))
+        import recommend
+        if not a.main_dir:
+            raise SystemExit("main_program: --main-dir DIR (written by tools/gen_main_golden --time FACTOR DIR)")
+        conf, tweets_csv = os.path.join(a.main_dir, "cluster.conf"), os.path.join(a.main_dir, "tweets.csv")
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "out.txt")
+            ts = []
+            for _ in range(3):                                         # the first call warms the context
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = recommend.run_recommendation(ctx, conf, tweets_csv, out, clock0=1, time0=1546300800)
+                ctx.sync()
+                ts.append(time.perf_counter() - t0)
+            with open(out, "rb") as f:
+                got = f.read()
+        mask = lambda data: [b"" if ln.startswith(b"Execution Time: ") else ln for ln in data.split(b"\n")]
+        times = [int(ln.split(b" ")[2]) for ln in got.split(b"\n") if ln.startswith(b"Execution Time: ")]
+        line = {"row": "main_program", "dir": os.path.basename(os.path.normpath(a.main_dir)),
+                "users": int(len(res["user_ids"])), "fake_users": int(res["fake_users"]["x"].shape[0]),
+                "first_call_s": ts[0], "call_s": float(min(ts[1:])), "block_ms": times,
+                "note": "run_recommendation, files in and file out, host reading and writing included; "
+                        "call_s: the faster of two calls after the first"}
+        ref_out = os.path.join(a.main_dir, "expected.out")
+        if os.path.exists(ref_out):                                    # the reference's own file for these inputs
+            with open(ref_out, "rb") as f:
+                line["output_identical"] = mask(f.read()) == mask(got)
+        if a.main_ref_seconds:
+            line["reference_s"] = a.main_ref_seconds
+            line["reference_kind"] = "the reference's main, g++ -O0, 1 core (gen_main_golden --time)"
+            line["reference_over_call"] = a.main_ref_seconds / line["call_s"]
+        print(json.dumps(line), flush=True)
 
     if "csv" in rows:        # VectorReader (vector_reader.hpp:54-85)
         n, d = 200_000, 64
