@@ -10,7 +10,8 @@
 // [acc_lo] on v_mfma_f32_32x32x16_f16: products of f16 values are exact in
 // f32, and the separate hi accumulator keeps the rounding of the large terms
 // at d ulps of f32. Rigorous bound on |dot~ - x.c|:
-//   A1 |x||c| + A2 (|x|_1 + |c|_1),  A1 = 1.25 * 2^-16, A2 = 2^-24,
+//   A1 |x||c| + A2 (|x|_1 + |c|_1),  A1 = FU_A1 = 1.057 * 2^-16 (tile.h: the sum
+// of its parts), A2 = 2^-24,
 // which assumes nothing better than round-toward-zero accumulation. The f16
 // range is guarded: a point with |x_j| > 2^15 (or non-finite) or a centroid set
 // with |c_j| > 2^15 is never certified, so such inputs take the exact path.

@@ -23,8 +23,12 @@ __device__ inline void hash_stage_images(const _Float16* __restrict__ Vh, const 
 
 // Window coefficients of one function (pnorm >= |v|_2, v1 >= |v|_1, rounded
 // up) for B = |y| G + |x| P + Q (certify_floor_f32). EUCLID: in units of y =
-// (acc + t) / w; cosine: of the inner product (t, w unused). 1 + 2^-20 covers
-// the roundings of the products and of f32(1/w), 1 + 2^-18 those of B, y -+ B.
+// (acc + t) / w; cosine: of the inner product (t, w unused). FU_A1H is the
+// tile's derived sum (tile.h): hash_tile_step's roundings, the callers' seven
+// step additions, the split's dropped product and residuals, its margin.
+// 1 + 2^-20 covers the roundings of the products here and of f32(1/w),
+// 1 + 2^-18 those of B, y -+ B. The fix-up (hash_exact.h) decides a listed
+// value from the exact row with its own fp64 bound and reads none of this.
 template <bool EUCLID>
 __device__ inline void hash_window(double pnorm, double v1, float t, float w, float& P, float& Q) {
     const double iwu = EUCLID ? (double)(1.0f / w) * (1.0 + 0x1p-20) : 1.0;
@@ -60,9 +64,13 @@ __device__ __forceinline__ void split_norm_step(const float* x8, half8& hi, half
 }
 
 // Step s of the hash tile after the split (bh, bl: hi and lo f16 of this lane's
-// 8 values): the lo products first, then the hi products into one accumulator
-// (16 roundings relative to the step's sum of |terms|, the lo parts' own ~2^-11
-// smaller); the caller adds the steps in f32 (+7): 24 roundings, inside FU_A1H.
+// 8 values): a fresh accumulator (C = 0), the lo products first, then the hi
+// products into it. Each MFMA makes 16 additions, each rounding by at most
+// 2^-23 relative and in no assumed order: a hi product passes through 16 of
+// them (FU_A1H_MFMA), a lo product through all 48 at 2^-10 of the magnitude
+// (FU_A1H_LO). The caller adds the 8 steps with VALU f32 adds, round to
+// nearest: 7 more at 2^-24 (FU_A1H_STEPS). A caller that chained the steps
+// through the C operand instead would have to charge them at 2^-23.
 // vh_row / vl_row: this lane's projection row in the LDS images + 8 * (lane
 // half). The packed-f32 step add stays written out in the kernels, and
 // hash_mfma_kernel keeps its own row load and split: moved in here they change
@@ -80,9 +88,11 @@ __device__ __forceinline__ floatx16 hash_tile_step(int s, const _Float16* vh_row
 // Certification in f32 (the floor only needs y to ~2^-20): with
 // u = f32(dot~ + t), y = f32(u * f32(1/w)),
 //   |y - (x.v + t)/w| <= (Ed + 2^-23 |u| + 2^-40 |t|) / w + 2^-21 |y|,
-// Ed = A1 |v||x| + A2 (|v|_1 + |x|_1) + 2^-23 |dot~| (the split bound and
-// the final hi + lo add; the reference's x87 / double-product roundings
-// are below 2^-50 (|v||x| + |t|)). With |x|_1 <= sqrt(d) |x|, |dot~| <=
+// Ed = A1 |v||x| + A2 (|v|_1 + |x|_1) + 2^-23 |dot~|: A1 = FU_A1H, the tile's
+// bound term by term (tile.h), which charges nothing for a final hi + lo add;
+// the 2^-23 |dot~| of the older tile's separate lo accumulator stays in G as
+// slack (this tile has no such add), and the reference's x87 / double-product
+// roundings are below 2^-50 (|v||x| + |t|). With |x|_1 <= sqrt(d) |x|, |dot~| <=
 // |u| + |t| and |u| / w <= |y| (1 + 2^-19), that is at most
 //   B = |y| G + |x| P_f + Q_f,   G = (2^-22 + 2^-20)(1 + 2^-18),
 //   P_f = (A1 |v| + A2 sqrt(d)) / w,  Q_f = (A2 |v|_1 + (2^-23 + 2^-40)|t|) / w

@@ -15,12 +15,51 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 constexpr int FU_D = 128;                // dimension handled by this kernel
 constexpr int FU_RS = FU_D + 8;          // f16 LDS row stride (elements) = 272 B
 
-constexpr double FU_A1 = 1.25 * 0x1p-16;
-// Hash tile of the persistent form: hi products of each 16-dim step in a fresh
-// accumulator (<= 15 roundings), steps added in f32 (+7), + lo (+1): 23 * 2^-23
-// = 0.72 * 2^-18 of sum|terms|; the split residuals and lo terms add < 0.25 *
-// 2^-18 as in A1's derivation.
-constexpr double FU_A1H = 1.25 * 0x1p-18;
+// The split-f16 dot product's error (DESIGN.md §4 "Split-f16 scores"):
+//   |dot~ - x.v| <= A1 |x||v| + A2 (|x|_1 + |v|_1),
+// A1 a sum of named parts, each relative to sum_j |x_j v_j| <= |x||v|
+// (Cauchy-Schwarz). The one assumption about the MFMA: every addition inside it
+// rounds somehow, by at most 2^-23 relative (FU_U_ANY; nothing about its order).
+// A term that passes through n such additions carries at most n * 2^-23 of its
+// magnitude (second order: FU_MARGIN). What the users add themselves is not in
+// A1: the 3-product forms' final hi + lo add, the hash's + t and * (1/w)
+// (certify_floor_f32's G), the scores' + cn.
+constexpr double FU_U_ANY = 0x1p-23;     // one addition, any rounding mode or MFMA-internal
+constexpr double FU_U_RN = 0x1p-24;      // one VALU f32 addition, round to nearest (no kernel sets the mode)
+// x = xh + xl + r, xh = f16(x), xl = f16(x - xh), |r| <= 2^-22 |x| in the f16
+// normal range (subnormal lo parts: A2); the same for v. x.v - (xh.vh + xh.vl +
+// xl.vh) = xl.vl + r_x.v + (xh + xl).r_v:
+constexpr double FU_SPLIT_DROPPED = 0x1p-22;        // the product xl.vl, never formed
+constexpr double FU_SPLIT_RESID = 2 * 0x1p-22;      // r_x.v and (xh + xl).r_v
+// sum |lo products| = sum |xh vl| + |xl vh| <= 2 * 2^-11 sum |x v|
+constexpr double FU_LO_SHARE = 0x1p-10;
+// Safety factor on the sum, 1 + 2^-8 (3.9 parts in a thousand) for what the
+// parts leave out: |xh| <= (1 + 2^-11)|x| and the same for v and the lo parts
+// (< 1 + 2^-9 together), (1 + u)^n - 1 against n u (n <= 256: < 1 + 2^-15), a
+// round-up's error measured on its result instead of the exact sum (1 + 2^-23),
+// fp64 projections whose lo part is rounded to f32 first (1 + 2^-13), the
+// reference's own x87 / double-product roundings (2^-50 |x||v|). pnorm and
+// v1 are rounded up where they are formed and need none of it.
+constexpr double FU_MARGIN = 1.0 + 0x1p-8;
+
+// 3-product tile (tile_mfma, fused_impl.h): acc_hi chains the 8 steps' hi
+// products through the MFMA's C operand, acc_lo the 16 lo MFMAs.
+constexpr double FU_A1_HI_CHAIN = 128 * FU_U_ANY;              // 8 MFMAs x 16 additions in one chain
+constexpr double FU_A1_LO_CHAIN = 256 * FU_U_ANY * FU_LO_SHARE;   // 16 MFMAs x 16, on the lo products
+constexpr double FU_A1_C_F32 = FU_U_RN;             // centroids: c rounded to f32 before its split (fused_centroid_prep)
+constexpr double FU_A1 = (FU_A1_HI_CHAIN + FU_A1_LO_CHAIN + FU_A1_C_F32 + FU_SPLIT_DROPPED + FU_SPLIT_RESID) * FU_MARGIN;
+// = 1.0568 * 2^-16
+
+// Hash tile (hash_tile_step, hash_tile.h; every hashing form of fused_hi.hip
+// and hash_mfma.hip): each 16-dim step starts a fresh accumulator (C = 0), the
+// two lo MFMAs first, the hi MFMA last; the caller adds the 8 steps with VALU
+// packed-f32 adds (v_pk_add_f32, round to nearest). A form that chained the
+// steps through the MFMA's C operand would need FU_U_ANY for them, or FU_A1.
+constexpr double FU_A1H_MFMA = 16 * FU_U_ANY;       // a hi product: the 16 additions of the step's last MFMA
+constexpr double FU_A1H_LO = 48 * FU_U_ANY * FU_LO_SHARE;    // a lo product: all 3 x 16 additions of its step
+constexpr double FU_A1H_STEPS = 7 * FU_U_RN;        // the 7 step additions, VALU
+constexpr double FU_A1H = (FU_A1H_MFMA + FU_A1H_LO + FU_A1H_STEPS + FU_SPLIT_DROPPED + FU_SPLIT_RESID) * FU_MARGIN;
+// = 0.8015 * 2^-18
 constexpr double FU_A2 = 0x1p-24;
 constexpr float FU_RANGE = 32768.f;
 
