@@ -718,7 +718,8 @@ static int km_finalize(lshkm_ctx ctx, const double* sums, const int64_t* counts,
 
 static int kmeans_update_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const int32_t* assign, const double* C_old,
                               int K, int metric, double min_dist, double* C_new, int64_t* counts, int* cont) {
-    LSHKM_CHECK(ctx && (X.p || N == 0) && assign && C_old && C_new && N >= 0 && N < (1ll << 31) && d > 0 && K > 0,
+    LSHKM_CHECK(ctx && (X.p || N == 0) && (assign || N == 0) && C_old && C_new && N >= 0 && N < (1ll << 31) && d > 0 &&
+                    K > 0,
                 LSHKM_ERR_ARG, "bad arguments");
     LSHKM_HIP(hipSetDevice(ctx->device));
     int rc;
@@ -730,7 +731,8 @@ static int kmeans_update_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const int3
 
 static int kmeans_partial_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const int32_t* assign, int K, double* sums,
                                int64_t* counts) {
-    LSHKM_CHECK(ctx && (X.p || N == 0) && assign && sums && counts && N >= 0 && N < (1ll << 31) && d > 0 && K > 0,
+    LSHKM_CHECK(ctx && (X.p || N == 0) && (assign || N == 0) && sums && counts && N >= 0 && N < (1ll << 31) && d > 0 &&
+                    K > 0,
                 LSHKM_ERR_ARG, "bad arguments");
     LSHKM_HIP(hipSetDevice(ctx->device));
     return km_sums(ctx, X, N, d, assign, K, sums, counts);

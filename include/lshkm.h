@@ -295,7 +295,9 @@ int lshkm_hash_assign_metric_f64(lshkm_lsh lsh, const double* X_dev, int64_t N, 
                                  int32_t* bucket_dev, int32_t* assign_dev, double* dist_dev);
 /* k_means (update.hpp:37-86): exact-order per-cluster fp64 sums in row order,
  * divided by the count unless empty; *cont_host = 1 iff some center moved
- * more than min_dist. C_new_dev [K][d], counts_dev [K] (may be NULL). */
+ * more than min_dist. C_new_dev [K][d], counts_dev [K] (may be NULL). N = 0
+ * (X_dev and assign_dev may then be NULL; also lshkm_kmeans_partial): every
+ * cluster is empty, every sum +0.0. */
 int lshkm_kmeans_update(lshkm_ctx ctx, const float* X_dev, int64_t N, int d, const int32_t* assign_dev,
                         const double* C_old_dev, int K, int metric, double min_dist,
                         double* C_new_dev, int64_t* counts_dev, int* cont_host);
@@ -320,7 +322,9 @@ int lshkm_kmeans_partial_csr_f64(lshkm_ctx ctx, const double* X_dev, int64_t N, 
 /* Sharded update (exact mode): the per-(c, j) chains continue from
  * carry_sums_dev / carry_counts_dev (the previous shard's result, or NULL for
  * the first shard), so passing the carry shard to shard in row order gives the
- * reference's single sequential sum (update.hpp:45-58) bit for bit. */
+ * reference's single sequential sum (update.hpp:45-58) bit for bit.
+ * carry_sums_dev must be a previous call's sums_dev, or NULL (a chain started
+ * at +0.0 never yields -0.0, and no form is specified for a -0.0 carry). */
 int lshkm_kmeans_partial_carry(lshkm_ctx ctx, const float* X_dev, int64_t N, int d, const int32_t* assign_dev,
                                int K, const double* carry_sums_dev, const int64_t* carry_counts_dev,
                                double* sums_dev, int64_t* counts_dev);

@@ -87,9 +87,10 @@ class NumpyShardSums:
         ok = km_cert(qt[0], -qt[1], counts.numpy(), asum.numpy())
         lane = ~ok & (counts.numpy()[:, None] <= 32768)           # one lane each (km_chain_lanes_kernel)
         mask = np.where(ok, 0, np.where(lane, 2, 1)).astype(np.uint8)
-        flag = np.zeros(self.K, np.int32)
+        flag = np.zeros(self.K, np.uint32)
         for c, j in zip(*np.nonzero(mask == 1)):
-            flag[c] |= np.int32(1 << min(31, j // 64))
+            flag[c] |= np.uint32(1 << min(31, j // 64))
+        flag = flag.view(np.int32)
         return (torch.from_numpy(tot), torch.from_numpy(pre), torch.from_numpy(flag), torch.from_numpy(mask),
                 int((~ok).sum()))
 
