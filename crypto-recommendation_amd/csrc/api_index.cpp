@@ -11,6 +11,7 @@
 #include "common.h"
 #include "index.h"
 #include "kernels.h"
+#include "lshpc_layout.h"
 
 using namespace lshkm;
 
@@ -139,32 +140,6 @@ int build_csr(lshkm_ctx ctx, const int32_t* keys, int64_t kstride, int64_t N, in
                                                   slot<int32_t>(ctx, WS_SKEYS), idx, ctx->ws[WS_SORT].p))) { LSHKM_LAUNCH_CHECK(); return rc; }
     if ((rc = launch_csr_bounds(ctx->stream, slot<int32_t>(ctx, WS_SKEYS), N, nb, row_ptr, T))) { LSHKM_LAUNCH_CHECK(); return rc; }
     return 0;
-}
-
-// Probe masks of get_hypercube_combined_buckets: 0 first (main bucket), then
-// Hamming distance 1 (bit 0..k-1), 2 (lexicographic i<j), ... ; probes == 1
-// starts at distance 2 (lsh_cube.hpp:148-150); stops when the cube is exhausted.
-std::vector<int32_t> probe_masks(int probes, int k) {
-    std::vector<int32_t> m(1, 0);
-    int remaining = probes;
-    int dist = probes > 1 ? 1 : 2;
-    std::vector<int> comb(64);
-    while (remaining > 0 && dist <= k) {
-        for (int i = 0; i < dist; i++) comb[i] = i;
-        for (;;) {
-            int mask = 0;
-            for (int i = 0; i < dist; i++) mask |= 1 << comb[i];
-            m.push_back(mask);
-            if (--remaining == 0) break;
-            int p = dist - 1;
-            while (p >= 0 && comb[p] == k - dist + p) p--;
-            if (p < 0) break;
-            comb[p]++;
-            for (int q = p + 1; q < dist; q++) comb[q] = comb[q - 1] + 1;
-        }
-        dist++;
-    }
-    return m;
 }
 
 }  // namespace
@@ -1123,4 +1098,5 @@ int lshkm_pam_update_f64(lshkm_ctx ctx, const double* X, int64_t N, int d, const
 namespace lshkm {
 int d2h_batch(lshkm_ctx_s* ctx, const D2H* r, int n) { return d2h_batch_impl(ctx, r, n); }
 int h2d_batch(lshkm_ctx_s* ctx, const H2D* r, int n) { return h2d_batch_impl(ctx, r, n); }
+int cube_vertices(lshkm_cube_s* cube, Pts X, int64_t N, int32_t* vertex) { return cube_vertices_impl(cube, X, N, vertex); }
 }  // namespace lshkm

@@ -159,6 +159,96 @@ static int lshpc_lists(lshkm_lsh lsh, const double* X, const double* U, const st
     return 0;
 }
 
+// The screen over every user of a call, for both entry points. row_code
+// [N][L]: the rows' bucket IDs of k bits each (a cube: L = 1, the vertices);
+// probe: the cube's candidacy (NULL: the LSH tables').
+struct ScreenJob {
+    const double *X, *U;
+    int64_t N, nq;
+    int d, L, k, P;
+    const int32_t* row_code;
+    int32_t excl_lo, excl_hi;
+    const CubeProbe* probe;
+};
+
+// One pass over X and one over U (the reference's sums of squares, the users'
+// codes through user_codes(out [nq][L]), the f32 images), then the users in
+// chunks (lshpc_plan): the screen, the join, the exact top-(P+1) over the kept
+// rows, the collect. handed <- the users handed back, ascending; *ucode <- the
+// users' codes on the device (ws_lshpc[1]).
+template <typename UserCodes>
+static int lshpc_screen_all(lshkm_ctx ctx, const ScreenJob& j, UserCodes user_codes, bool small_cap, int32_t* out_idx,
+                            double* out_sim, int32_t* out_cnt, int64_t* ncand, std::vector<int32_t>& handed,
+                            const int32_t** ucode) {
+    hipStream_t s = ctx->stream;
+    unsigned long long* stats = (unsigned long long*)ctx->stats.p;
+    const int64_t N = j.N, nq = j.nq;
+    const int d = j.d, L = j.L, k = j.k, P = j.P;
+    int rc, ncu = 0;
+    if ((rc = device_cu_count(&ncu))) return rc;
+    const size_t budget = test_switch("LSHKM_LSHPC_BUDGET", "small") ? (size_t)1 << 20 : LSHPC_BUDGET;
+    const LshpcPlan plan = lshpc_plan(N, nq, P, ncu, small_cap, budget);
+    const int dp = lshpc_dp(d);
+    const LshpcImage ix = lshpc_image(N, dp, 0), iu = lshpc_image(nq, dp, L);
+    const LshpcChunk cmax = lshpc_chunk(plan.chunk, plan.cap, plan.segs);
+    Buf &bx = ctx->ws_lshpc[0], &bu = ctx->ws_lshpc[1], &bc = ctx->ws_lshpc[2], &bh = ctx->ws_lshpc[3];
+    if ((rc = bx.reserve(ix.bytes)) || (rc = bu.reserve(iu.bytes)) || (rc = bc.reserve(cmax.bytes)) ||
+        (rc = bh.reserve(256 + 4 * (size_t)nq)))
+        return rc;
+    const LshpcSide rows{at<float>(bx, ix.xh), at<uint32_t>(bx, ix.code), at<float>(bx, ix.inv), at<float>(bx, ix.rel),
+                         N};
+    const LshpcSide users{at<float>(bu, iu.xh), at<uint32_t>(bu, iu.code), at<float>(bu, iu.inv),
+                          at<float>(bu, iu.rel), nq};
+    double* xa = at<double>(bx, ix.xa);
+    int32_t* ubucket = at<int32_t>(bu, iu.bucket);
+    *ucode = ubucket;
+    unsigned int* handed_count = bh.as<unsigned int>();
+    int32_t* handed_dev = at<int32_t>(bh, 256);
+    if ((rc = launch_rc_norms(s, j.X, N, d, xa)) || (rc = launch_lshpc_prep(s, j.X, N, d, dp, xa, j.row_code, L, k, rows)) ||
+        (rc = user_codes(ubucket)) || (rc = launch_rc_norms(s, j.U, nq, d, at<double>(bu, iu.xa))) ||
+        (rc = launch_lshpc_prep(s, j.U, nq, d, dp, at<double>(bu, iu.xa), ubucket, L, k, users)))
+        return rc;
+    if (hipMemsetAsync(handed_count, 0, sizeof(unsigned int), s) != hipSuccess) {
+        set_error("lshpc screen: hipMemsetAsync failed");
+        return LSHKM_ERR_HIP;
+    }
+    for (int64_t u0 = 0; u0 < nq; u0 += plan.chunk) {
+        const int64_t n = std::min(plan.chunk, nq - u0);
+        const LshpcChunk c = lshpc_chunk(n, plan.cap, plan.segs);
+        const LshpcKept kept{at<float>(bc, c.klo), at<float>(bc, c.khi), at<int32_t>(bc, c.krow),
+                             at<int32_t>(bc, c.state), c.np, plan.seg_rows, plan.cap, plan.segs};
+        const LshpcSide chunk_users{users.xh + (size_t)u0 * dp, users.code + u0, users.inv + u0, users.rel + u0, n};
+        unsigned int* replay_count = at<unsigned int>(bc, c.counts);
+        if ((rc = j.probe ? launch_cubepc_screen(s, dp, rows, chunk_users, P, *j.probe, kept)
+                          : launch_lshpc_screen(s, dp, rows, chunk_users, j.excl_lo, j.excl_hi, P, L, k, kept)) ||
+            (rc = launch_lshpc_join(s, kept, n, P, at<int64_t>(bc, c.nkept), ncand ? ncand + u0 : nullptr,
+                                    at<int64_t>(bc, c.cptr), at<int32_t>(bc, c.cidx), stats)) ||
+            // the exact top-(P+1) over the kept rows; its replay list (a NaN,
+            // or a tie in the first P+1) is returned, not replayed: Lomuto's
+            // order depends on the whole list, which only the lists path has
+            (rc = launch_rc_p_closest(s, j.X, xa, d, j.U + (size_t)u0 * d, n, at<int64_t>(bc, c.cptr),
+                                      at<int32_t>(bc, c.cidx), P, at<double>(bc, c.sim), at<double>(bc, c.key), nullptr,
+                                      out_idx + (size_t)u0 * P, out_sim + (size_t)u0 * P, out_cnt + u0,
+                                      at<int32_t>(bc, c.replay), replay_count, false)) ||
+            (rc = launch_lshpc_collect(s, kept, n, u0, at<int32_t>(bc, c.replay), replay_count, handed_dev,
+                                       handed_count)))
+            return rc;
+    }
+    unsigned int nh = 0;
+    const D2H rd{&nh, handed_count, sizeof(nh)};
+    if ((rc = d2h_batch(ctx, &rd, 1))) return rc;
+    handed.resize(nh);
+    const D2H rl{handed.data(), handed_dev, 4 * (size_t)nh};
+    if (nh && (rc = d2h_batch(ctx, &rl, 1))) return rc;
+    std::sort(handed.begin(), handed.end());
+    return 0;
+}
+
+static void every_user(int64_t nq, std::vector<int32_t>& handed) {
+    handed.resize((size_t)nq);
+    for (int64_t q = 0; q < nq; q++) handed[q] = (int32_t)q;
+}
+
 extern "C" int lshkm_lsh_p_closest(lshkm_lsh lsh, const double* X, const double* U, int64_t nq, int32_t excl_lo,
                                    int32_t excl_hi, int P, int32_t* out_idx, double* out_sim, int32_t* out_cnt,
                                    int64_t* ncand) {
@@ -181,74 +271,126 @@ extern "C" int lshkm_lsh_p_closest(lshkm_lsh lsh, const double* X, const double*
     std::vector<int32_t> handed;
     if (lshpc_route(lsh->metric == LSHKM_METRIC_COSINE, d, L, k, P,
                     N == 0 || test_switch("LSHKM_LSHPC_PATH", "lists")) == LshpcRoute::lists) {
-        handed.resize((size_t)nq);
-        for (int64_t q = 0; q < nq; q++) handed[q] = (int32_t)q;
+        every_user(nq, handed);
     } else {
-        int ncu = 0;
-        if ((rc = device_cu_count(&ncu))) return rc;
-        const size_t budget = test_switch("LSHKM_LSHPC_BUDGET", "small") ? (size_t)1 << 20 : LSHPC_BUDGET;
-        const LshpcPlan plan = lshpc_plan(N, nq, P, ncu, small_cap, budget);
-        const int dp = lshpc_dp(d);
-        const LshpcImage ix = lshpc_image(N, dp, 0), iu = lshpc_image(nq, dp, L);
-        const LshpcChunk cmax = lshpc_chunk(plan.chunk, plan.cap, plan.segs);
-        Buf &bx = ctx->ws_lshpc[0], &bu = ctx->ws_lshpc[1], &bc = ctx->ws_lshpc[2], &bh = ctx->ws_lshpc[3];
-        if ((rc = bx.reserve(ix.bytes)) || (rc = bu.reserve(iu.bytes)) || (rc = bc.reserve(cmax.bytes)) ||
-            (rc = bh.reserve(256 + 4 * (size_t)nq)))
+        const ScreenJob job{X, U, N, nq, d, L, k, P, lsh->bucket.as<int32_t>(), excl_lo, excl_hi, nullptr};
+        const int32_t* ucode = nullptr;
+        const auto user_codes = [&](int32_t* ubucket) {
+            return hash_rows(ctx, HM_LSH_COSINE, U, nq, lsh->proj, lsh->nb, nullptr, nullptr, ubucket, nullptr);
+        };
+        if ((rc = lshpc_screen_all(ctx, job, user_codes, small_cap, out_idx, out_sim, out_cnt, ncand, handed, &ucode)))
             return rc;
-        const LshpcSide rows{at<float>(bx, ix.xh), at<uint32_t>(bx, ix.code), at<float>(bx, ix.inv),
-                             at<float>(bx, ix.rel), N};
-        const LshpcSide users{at<float>(bu, iu.xh), at<uint32_t>(bu, iu.code), at<float>(bu, iu.inv),
-                              at<float>(bu, iu.rel), nq};
-        double* xa = at<double>(bx, ix.xa);
-        int32_t* ubucket = at<int32_t>(bu, iu.bucket);
-        unsigned int* handed_count = bh.as<unsigned int>();
-        int32_t* handed_dev = at<int32_t>(bh, 256);
-        // one pass over X and one over U: the reference's sums of squares, the
-        // users' bucket IDs, the f32 images
-        if ((rc = launch_rc_norms(s, X, N, d, xa)) ||
-            (rc = launch_lshpc_prep(s, X, N, d, dp, xa, lsh->bucket.as<int32_t>(), L, k, rows)) ||
-            (rc = hash_rows(ctx, HM_LSH_COSINE, U, nq, lsh->proj, lsh->nb, nullptr, nullptr, ubucket, nullptr)) ||
-            (rc = launch_rc_norms(s, U, nq, d, at<double>(bu, iu.xa))) ||
-            (rc = launch_lshpc_prep(s, U, nq, d, dp, at<double>(bu, iu.xa), ubucket, L, k, users)))
-            return rc;
-        if (hipMemsetAsync(handed_count, 0, sizeof(unsigned int), s) != hipSuccess) {
-            set_error("lshkm_lsh_p_closest: hipMemsetAsync failed");
-            return rc = LSHKM_ERR_HIP;
-        }
-        for (int64_t u0 = 0; u0 < nq; u0 += plan.chunk) {
-            const int64_t n = std::min(plan.chunk, nq - u0);
-            const LshpcChunk c = lshpc_chunk(n, plan.cap, plan.segs);
-            const LshpcKept kept{at<float>(bc, c.klo), at<float>(bc, c.khi), at<int32_t>(bc, c.krow),
-                                 at<int32_t>(bc, c.state), c.np, plan.seg_rows, plan.cap, plan.segs};
-            const LshpcSide chunk_users{users.xh + (size_t)u0 * dp, users.code + u0, users.inv + u0, users.rel + u0, n};
-            unsigned int* replay_count = at<unsigned int>(bc, c.counts);
-            if ((rc = launch_lshpc_screen(s, dp, rows, chunk_users, excl_lo, excl_hi, P, L, k, kept)) ||
-                (rc = launch_lshpc_join(s, kept, n, P, at<int64_t>(bc, c.nkept), ncand ? ncand + u0 : nullptr,
-                                        at<int64_t>(bc, c.cptr), at<int32_t>(bc, c.cidx), stats)) ||
-                // the exact top-(P+1) over the kept rows; its replay list (a NaN,
-                // or a tie in the first P+1) is returned, not replayed: Lomuto's
-                // order depends on the whole list, which only the lists path has
-                (rc = launch_rc_p_closest(s, X, xa, d, U + (size_t)u0 * d, n, at<int64_t>(bc, c.cptr),
-                                          at<int32_t>(bc, c.cidx), P, at<double>(bc, c.sim), at<double>(bc, c.key),
-                                          nullptr, out_idx + (size_t)u0 * P, out_sim + (size_t)u0 * P, out_cnt + u0,
-                                          at<int32_t>(bc, c.replay), replay_count, false)) ||
-                (rc = launch_lshpc_collect(s, kept, n, u0, at<int32_t>(bc, c.replay), replay_count, handed_dev,
-                                           handed_count)))
-                return rc;
-        }
-        unsigned int nh = 0;
-        const D2H rd{&nh, handed_count, sizeof(nh)};
-        if ((rc = d2h_batch(ctx, &rd, 1))) return rc;
-        handed.resize(nh);
-        const D2H rl{handed.data(), handed_dev, 4 * (size_t)nh};
-        if (nh && (rc = d2h_batch(ctx, &rl, 1))) return rc;
-        std::sort(handed.begin(), handed.end());
     }
     if ((rc = launch_lshpc_stats(s, stats, nq - (int64_t)handed.size(), (int64_t)handed.size())) ||
         (rc = lshpc_lists(lsh, X, U, handed, excl_lo, excl_hi, P, cand_cap, out_idx, out_sim, out_cnt, ncand)))
         return rc;
     if (hipStreamSynchronize(s) != hipSuccess) {             // the workspace is reused by the next call
         set_error("lshkm_lsh_p_closest: hipStreamSynchronize failed");
+        return LSHKM_ERR_HIP;
+    }
+    return 0;
+}
+
+// --------------------------------- hypercube recommender: P closest from the cube
+// lshkm_cube_p_closest. The lists path: lshkm_cube_query's
+// kernels -> get_P_closest (with its replay) on the users of `list` (ascending),
+// gathered, their vertices (uvert: every user's, from the one vertex pass of
+// the call) gathered too, so that no coin is drawn here. A user's neighbour
+// count is the sum of its probed buckets' lengths: the chunks (at most cand_cap
+// candidate rows and CUBEPC_SLOT_CAP (user, mask) slots) are cut from exact
+// counts, no sizing query.
+constexpr int64_t CUBEPC_SLOT_CAP = (int64_t)1 << 24;
+static int cubepc_lists(lshkm_cube cube, const double* X, const double* U, const int32_t* uvert,
+                        const std::vector<int32_t>& list, int probes, int P, int64_t cand_cap, int32_t* out_idx,
+                        double* out_sim, int32_t* out_cnt, int64_t* ncand) {
+    lshkm_ctx ctx = cube->ctx;
+    hipStream_t s = ctx->stream;
+    const int64_t m_all = (int64_t)list.size(), N = cube->N;
+    const int d = cube->proj.d;
+    if (m_all == 0) return 0;
+    const std::vector<int32_t> masks = probe_masks(probes, cube->k);
+    const int64_t S = (int64_t)masks.size();
+    Buf &bw = ctx->ws_lshpc[4], &bq = ctx->ws_lshpc[5], &bm = ctx->ws_lshpc[6];
+    int rc;
+    // masks | list | vg (int32) | nc (int64)
+    const size_t oma = 0, oli = oma + lshpc_round256(4 * (size_t)S), ovg = oli + lshpc_round256(4 * (size_t)m_all),
+                 onc = ovg + lshpc_round256(4 * (size_t)m_all);
+    if ((rc = bm.reserve(onc + lshpc_round256(8 * (size_t)m_all)))) return rc;
+    const int32_t *dmasks = at<int32_t>(bm, oma), *dlist = at<int32_t>(bm, oli), *vg = at<int32_t>(bm, ovg);
+    const H2D up[2] = {{at<int32_t>(bm, oma), masks.data(), 4 * (size_t)S},
+                       {at<int32_t>(bm, oli), list.data(), 4 * (size_t)m_all}};
+    std::vector<int64_t> nc((size_t)m_all);
+    const D2H rd{nc.data(), at<int64_t>(bm, onc), 8 * (size_t)m_all};
+    if ((rc = h2d_batch(ctx, up, 2)) ||
+        (rc = launch_cubepc_handed(s, uvert, dlist, m_all, dmasks, (int)S, cube->row_ptr.as<int64_t>(),
+                                   at<int32_t>(bm, ovg), at<int64_t>(bm, onc))) ||
+        (rc = d2h_batch(ctx, &rd, 1)))
+        return rc;
+    for (int64_t i0 = 0; i0 < m_all;) {
+        int64_t n = 0, total = 0;
+        while (i0 + n < m_all && (n == 0 || (total + nc[i0 + n] <= cand_cap && (n + 1) * S <= CUBEPC_SLOT_CAP)))
+            total += nc[i0 + n++];
+        // Ug | qptr | sizes | slot_off | scan (int64) | gsim | gcnt | gidx
+        const size_t slots = (size_t)(n * S);
+        const size_t oUg = 0, oq = oUg + lshpc_round256(8 * (size_t)n * d), osz = oq + lshpc_round256(8 * (size_t)(n + 1)),
+                     oso = osz + lshpc_round256(8 * slots), osc = oso + lshpc_round256(8 * (slots + 1)),
+                     ogs = osc + lshpc_round256(scan_ws_bytes((int64_t)slots)), ogc = ogs + lshpc_round256(8 * (size_t)n * P),
+                     ogi = ogc + lshpc_round256(4 * (size_t)n), bytes = ogi + lshpc_round256(4 * (size_t)n * P);
+        if ((rc = bw.reserve(bytes)) || (rc = bq.reserve(4 * (size_t)std::max<int64_t>(total, 1)))) return rc;
+        double* Ug = at<double>(bw, oUg);
+        int64_t* qptr = at<int64_t>(bw, oq);
+        if ((rc = launch_lshpc_gather(s, U, d, dlist + i0, n, Ug)) ||
+            (rc = launch_cube_query(s, vg + i0, n, dmasks, (int)S, cube->row_ptr.as<int64_t>(), cube->idx.as<int32_t>(),
+                                    at<int64_t>(bw, osz), at<int64_t>(bw, oso), qptr, bq.as<int32_t>(),
+                                    at<int64_t>(bw, osc))) ||
+            (rc = p_closest_launch(ctx, X, N, d, Ug, n, qptr, bq.as<int32_t>(), total, P, at<int32_t>(bw, ogi),
+                                   at<double>(bw, ogs), at<int32_t>(bw, ogc))) ||
+            (rc = launch_lshpc_scatter(s, dlist + i0, n, P, at<int32_t>(bw, ogi), at<double>(bw, ogs),
+                                       at<int32_t>(bw, ogc), qptr, out_idx, out_sim, out_cnt, ncand)))
+            return rc;
+        i0 += n;
+    }
+    return 0;
+}
+
+extern "C" int lshkm_cube_p_closest(lshkm_cube cube, const double* X, const double* U, int64_t nq, int probes, int P,
+                                    int32_t* out_idx, double* out_sim, int32_t* out_cnt, int64_t* ncand) {
+    LSHKM_CHECK(cube && cube->built, LSHKM_ERR_STATE, "cube not built (lshkm_cube_build)");
+    LSHKM_CHECK(nq >= 0 && nq < (1ll << 31) && P >= 1, LSHKM_ERR_ARG, "bad arguments (P >= 1)");
+    if (nq == 0) return 0;
+    LSHKM_CHECK(U && out_idx && out_sim && out_cnt && (X || cube->N == 0), LSHKM_ERR_ARG, "bad arguments");
+    lshkm_ctx ctx = cube->ctx;
+    LSHKM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int64_t N = cube->N;
+    const int d = cube->proj.d, k = cube->k;
+    const bool small_cap = test_switch("LSHKM_LSHPC_CAP", "small");
+    const int64_t cand_cap = small_cap ? (int64_t)1 << 16 : LSHPC_CAND_CAP;
+    unsigned long long* stats = (unsigned long long*)ctx->stats.p;
+    int rc = 0;
+    const StreamSyncOnExit sync_guard{s, &rc};           // a failed call leaves nothing running
+
+    // every user's vertex once, by the query's own routine: the euclidean
+    // cube's unseen coins are drawn here, in (user, f) order, and nowhere else
+    const auto user_codes = [&](int32_t* vertex) { return cube_vertices(cube, U, nq, vertex); };
+    std::vector<int32_t> handed;
+    const int32_t* uvert = nullptr;
+    if (cubepc_route(d, k, P, N == 0 || test_switch("LSHKM_LSHPC_PATH", "lists")) == LshpcRoute::lists) {
+        Buf& bu = ctx->ws_lshpc[1];
+        if ((rc = bu.reserve(4 * (size_t)nq)) || (rc = user_codes(bu.as<int32_t>()))) return rc;
+        uvert = bu.as<int32_t>();
+        every_user(nq, handed);
+    } else {
+        const CubeProbe probe = cubepc_probe(probes, k);
+        const ScreenJob job{X, U, N, nq, d, 1, k, P, cube->vertex.as<int32_t>(), 0, 0, &probe};
+        if ((rc = lshpc_screen_all(ctx, job, user_codes, small_cap, out_idx, out_sim, out_cnt, ncand, handed, &uvert)))
+            return rc;
+    }
+    if ((rc = launch_lshpc_stats(s, stats, nq - (int64_t)handed.size(), (int64_t)handed.size())) ||
+        (rc = cubepc_lists(cube, X, U, uvert, handed, probes, P, cand_cap, out_idx, out_sim, out_cnt, ncand)))
+        return rc;
+    if (hipStreamSynchronize(s) != hipSuccess) {             // the workspace is reused by the next call
+        set_error("lshkm_cube_p_closest: hipStreamSynchronize failed");
         return LSHKM_ERR_HIP;
     }
     return 0;

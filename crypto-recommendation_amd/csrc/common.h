@@ -98,7 +98,7 @@ enum Stat {
     STAT_KM_SEQ = 9,         // k-means (cluster, dim) sums whose never-rounds test failed (sequential / segment chain)
     STAT_PAM_SCREENED = 10,  // PAM update: clusters whose argmin went through the MFMA screen
     STAT_PAM_EXACT = 11,     // ... and the members the screen left to the exact chain
-    STAT_LSHPC_SETTLED = 12, // lshkm_lsh_p_closest: users the MFMA screen settled
+    STAT_LSHPC_SETTLED = 12, // lshkm_lsh_p_closest / lshkm_cube_p_closest: users the MFMA screen settled
     STAT_LSHPC_LISTS = 13,   // ... users sent to the lists path (poison, overflow, tie / NaN; or the whole call)
     STAT_LSHPC_KEPT = 14,    // ... candidates the screen kept for the exact pass
     STAT_LSHPC_SEEN = 15,    // ... candidates it saw

@@ -44,7 +44,11 @@ struct ProjTable {
 
 struct lshkm_ctx_s;
 struct lshkm_lsh_s;
+struct lshkm_cube_s;
 namespace lshkm {
+// A batch's vertices as lshkm_cube_query computes them (api_index.cpp): the
+// euclidean cube draws its unseen coins in (row, f) order into the handle's memo.
+int cube_vertices(lshkm_cube_s* cube, Pts X, int64_t N, int32_t* vertex);
 // Hashing of a batch on the split-f16 MFMA kernel where it applies, else the
 // fp64 kernel (api_index.cpp).
 // h16 (cube euclidean): in, int16 h wanted; out, whether int16 was written
@@ -100,8 +104,9 @@ struct lshkm_ctx_s {
     // workspaces of the entry points that synchronise their stream before
     // returning (kmeans_pp, p_closest, top_n_recom): reused across calls
     lshkm::Buf ws_call[10];
-    // lshkm_lsh_p_closest (lshpc_layout.h): the pool's image, the users' image,
-    // the chunk, the handed-back list, the lists path's users and its two lists
+    // lshkm_lsh_p_closest / lshkm_cube_p_closest (lshpc_layout.h): the pool's
+    // image, the users' image, the chunk, the handed-back list, the lists path's
+    // users and its two lists (the cube's: its list, and its masks and sizes)
     lshkm::Buf ws_lshpc[7];
     uint64_t ws_epoch = 0;       // bumped by every user of the ws[] slots (api_index.cpp reserve)
     // optional HIP-event timing of the dominant kernel launch (lshkm_last_kernel_ms)

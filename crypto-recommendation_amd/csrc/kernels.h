@@ -456,6 +456,15 @@ int launch_lshpc_prep(hipStream_t s, const double* X, int64_t n, int d, int dp, 
                       int L, int k, const LshpcSide& out);
 int launch_lshpc_screen(hipStream_t s, int dp, const LshpcSide& rows, const LshpcSide& users, int32_t excl_lo,
                         int32_t excl_hi, int P, int L, int k, const LshpcKept& kept);
+// The same screen over hypercube vertices (codes = vertices, no exclusion):
+// candidates by cubepc_member(code_i ^ code_j, probe).
+struct CubeProbe;
+int launch_cubepc_screen(hipStream_t s, int dp, const LshpcSide& rows, const LshpcSide& users, int P,
+                         const CubeProbe& probe, const LshpcKept& kept);
+// The cube's lists path: vg[i] = vertex[list[i]], ncand[i] = the length of that
+// user's combined bucket over the S probe masks.
+int launch_cubepc_handed(hipStream_t s, const int32_t* vertex, const int32_t* list, int64_t m, const int32_t* masks,
+                         int S, const int64_t* row_ptr, int32_t* vg, int64_t* ncand);
 // The segments joined: nkept [n], ncand [n] (or NULL), cptr [n + 1] = scan of
 // nkept, cidx = the unflagged users' kept rows, ascending; stats 14 / 15.
 int launch_lshpc_join(hipStream_t s, const LshpcKept& kept, int64_t n, int P, int64_t* nkept, int64_t* ncand,

@@ -7,7 +7,10 @@
 // pool rows, LSHPC_STAGE at a time through LDS (the A operand; pam.hip's
 // layout and row stride). Row i is a candidate of user j iff some k-bit field
 // of code_i ^ code_j is zero (they share a bucket in some table) and i is not
-// in the excluded range. For a candidate the screen has s~ = g~ / (|x^||u^|)
+// in the excluded range. lshkm_cube_p_closest (§5e) runs the same kernel over a
+// built hypercube: the codes are vertices and i is a candidate of j iff
+// code_i ^ code_j is one of the probe masks (cubepc_member, lshpc_layout.h).
+// For a candidate the screen has s~ = g~ / (|x^||u^|)
 // and the interval [s~ - E, s~ + E] that holds the reference's similarity
 // (the bound: §5c; E0 below is its part that no row or user changes).
 //
@@ -140,9 +143,13 @@ __device__ inline int lshpc_prune(float* klo, float* khi, int32_t* krow, int n, 
     return w;
 }
 
-template <int DP>
+// CUBE = false: ca / cb = the lowest / highest bit of every table's field in the
+// packed code (a field of code_i ^ code_j is zero iff the subtraction borrows
+// out of it). CUBE = true: the codes are vertices and ca / cb = CubeProbe's
+// shells / rev_last (lshpc_layout.h).
+template <int DP, bool CUBE>
 __global__ __launch_bounds__(256, 2) void lshpc_screen_kernel(LshpcSide rows, LshpcSide users, int32_t excl_lo,
-                                                              int32_t excl_hi, int P, uint32_t lowb, uint32_t highb,
+                                                              int32_t excl_hi, int P, uint32_t ca, uint32_t cb,
                                                               LshpcKept kept) {
     constexpr int H = DP / 2;     // dims per lane half
     constexpr int DS = DP + 4;    // padded LDS row stride (floats): conflict-free ds_read_b128
@@ -233,7 +240,8 @@ __global__ __launch_bounds__(256, 2) void lshpc_screen_kernel(LshpcSide rows, Ls
                     const int ml = t * 32 + 8 * g + 4 * h + q;
                     const float inv = rinv[ml];
                     const uint32_t y = rcode[ml] ^ ucode;
-                    if (!own || inv == 0.f || ((y - lowb) & ~y & highb) == 0u) continue;
+                    const bool cand = CUBE ? cubepc_member(y, ca, cb) : ((y - ca) & ~y & cb) != 0u;
+                    if (!own || inv == 0.f || !cand) continue;
                     seen++;
                     if (inv < 0.f) {
                         pois = true;
@@ -415,6 +423,25 @@ __global__ __launch_bounds__(256) void lshpc_gather_kernel(const double* __restr
         Ug[e] = U[(size_t)list[e / d] * d + e % d];
 }
 
+// lshkm_cube_p_closest's lists path, one thread per user of `list`: its vertex
+// gathered and its combined bucket's length (the probed buckets' lengths).
+__global__ __launch_bounds__(256) void cubepc_handed_kernel(const int32_t* __restrict__ vertex,
+                                                            const int32_t* __restrict__ list, int64_t m,
+                                                            const int32_t* __restrict__ masks, int S,
+                                                            const int64_t* __restrict__ row_ptr,
+                                                            int32_t* __restrict__ vg, int64_t* __restrict__ ncand) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) {
+        const int32_t v = vertex[list[i]];
+        int64_t n = 0;
+        for (int j = 0; j < S; j++) {
+            const int32_t b = v ^ masks[j];
+            n += row_ptr[b + 1] - row_ptr[b];
+        }
+        vg[i] = v;
+        ncand[i] = n;
+    }
+}
+
 // ... and their results back to the users' slots.
 __global__ __launch_bounds__(256) void lshpc_scatter_kernel(const int32_t* __restrict__ list, int64_t m, int P,
                                                             const int32_t* __restrict__ gidx,
@@ -444,23 +471,39 @@ int launch_lshpc_prep(hipStream_t s, const double* X, int64_t n, int d, int dp, 
     return kstatus("lshpc_prep_kernel");
 }
 
+template <bool CUBE>
+static int screen_launch(hipStream_t s, int dp, const LshpcSide& rows, const LshpcSide& users, int32_t excl_lo,
+                         int32_t excl_hi, int P, uint32_t ca, uint32_t cb, const LshpcKept& kept) {
+    if (kept.cap < P + 1 + LSHPC_STAGE || kept.cap > LSHPC_CAP_MAX || kept.np < users.n ||
+        kept.np % LSHPC_COLS != 0 || (dp != 32 && dp != 128)) {
+        set_error("lshpc screen: unsupported shape");
+        return -4;
+    }
+    const dim3 grid((unsigned)(kept.np / LSHPC_COLS), (unsigned)kept.segs), block(256);
+    if (dp == 32)
+        hipLaunchKernelGGL((lshpc_screen_kernel<32, CUBE>), grid, block, 0, s, rows, users, excl_lo, excl_hi, P, ca, cb, kept);
+    else
+        hipLaunchKernelGGL((lshpc_screen_kernel<128, CUBE>), grid, block, 0, s, rows, users, excl_lo, excl_hi, P, ca, cb, kept);
+    return kstatus("lshpc_screen_kernel");
+}
+
 int launch_lshpc_screen(hipStream_t s, int dp, const LshpcSide& rows, const LshpcSide& users, int32_t excl_lo,
                         int32_t excl_hi, int P, int L, int k, const LshpcKept& kept) {
     if (users.n <= 0) return 0;
-    if (kept.cap < P + 1 + LSHPC_STAGE || kept.cap > LSHPC_CAP_MAX || (int64_t)L * k > 32 ||
-        kept.np < users.n || kept.np % LSHPC_COLS != 0 || (dp != 32 && dp != 128)) {
+    if (L < 1 || k < 1 || (int64_t)L * k > 32) {
         set_error("lshpc screen: unsupported shape");
         return -4;
     }
     uint32_t lowb = 0;
     for (int l = 0; l < L; l++) lowb |= 1u << (l * k);
     const uint32_t highb = lowb << (k - 1);
-    const dim3 grid((unsigned)(kept.np / LSHPC_COLS), (unsigned)kept.segs), block(256);
-    if (dp == 32)
-        hipLaunchKernelGGL(lshpc_screen_kernel<32>, grid, block, 0, s, rows, users, excl_lo, excl_hi, P, lowb, highb, kept);
-    else
-        hipLaunchKernelGGL(lshpc_screen_kernel<128>, grid, block, 0, s, rows, users, excl_lo, excl_hi, P, lowb, highb, kept);
-    return kstatus("lshpc_screen_kernel");
+    return screen_launch<false>(s, dp, rows, users, excl_lo, excl_hi, P, lowb, highb, kept);
+}
+
+int launch_cubepc_screen(hipStream_t s, int dp, const LshpcSide& rows, const LshpcSide& users, int P,
+                         const CubeProbe& probe, const LshpcKept& kept) {
+    if (users.n <= 0) return 0;
+    return screen_launch<true>(s, dp, rows, users, 0, 0, P, probe.shells, probe.rev_last, kept);
 }
 
 int launch_lshpc_join(hipStream_t s, const LshpcKept& kept, int64_t n, int P, int64_t* nkept, int64_t* ncand,
@@ -491,6 +534,14 @@ int launch_lshpc_gather(hipStream_t s, const double* U, int d, const int32_t* li
     if (m <= 0) return 0;
     hipLaunchKernelGGL(lshpc_gather_kernel, dim3(gsz(m * d, 256, 8192)), dim3(256), 0, s, U, d, list, m, Ug);
     return kstatus("lshpc_gather_kernel");
+}
+
+int launch_cubepc_handed(hipStream_t s, const int32_t* vertex, const int32_t* list, int64_t m, const int32_t* masks,
+                         int S, const int64_t* row_ptr, int32_t* vg, int64_t* ncand) {
+    if (m <= 0) return 0;
+    hipLaunchKernelGGL(cubepc_handed_kernel, dim3(gsz(m, 256, 8192)), dim3(256), 0, s, vertex, list, m, masks, S, row_ptr,
+                       vg, ncand);
+    return kstatus("cubepc_handed_kernel");
 }
 
 int launch_lshpc_scatter(hipStream_t s, const int32_t* list, int64_t m, int P, const int32_t* gidx, const double* gsim,

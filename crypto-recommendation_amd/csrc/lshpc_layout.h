@@ -1,11 +1,13 @@
-// lshpc_layout.h — the one statement of lshkm_lsh_p_closest's routing rule and
-// of its workspaces: which calls the MFMA screen takes, the kept-list capacity,
-// the row segments, the user chunks and every buffer's regions. Plain host
-// arithmetic: no HIP.
+// lshpc_layout.h — the one statement of lshkm_lsh_p_closest's and
+// lshkm_cube_p_closest's routing rules and of their workspaces: which calls the
+// MFMA screen takes, the cube's candidacy test, the kept-list capacity, the row
+// segments, the user chunks and every buffer's regions. Plain host arithmetic:
+// no HIP (the candidacy test alone is also compiled for the device).
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace lshkm {
 
@@ -37,6 +39,113 @@ inline LshpcRoute lshpc_route(bool cosine, int d, int L, int k, int P, bool forc
 }
 // Padded dims of the f32 image (the screen kernel's two instantiations).
 inline int lshpc_dp(int d) { return d <= 32 ? 32 : 128; }
+
+// ---- lshkm_cube_p_closest: the same screen over a built hypercube. A row's
+// code is its vertex, a user's code the vertex lshkm_cube_query gives it; row i
+// is a candidate of user j iff vertex_i ^ vertex_j is one of the probe masks.
+// Either metric (candidacy is by vertex alone, the similarity is cosine); the
+// lists path: lshkm_cube_query's kernels -> lshkm_p_closest on the users handed
+// back, gathered.
+constexpr int LSHPC_CUBE_KMAX = 30;      // a vertex is a non-negative int32 (lshkm_cube_create's limit)
+inline LshpcRoute cubepc_route(int d, int k, int P, bool force_lists) {
+    if (force_lists || d > LSHPC_DMAX || k > LSHPC_CUBE_KMAX) return LshpcRoute::lists;
+    return (int64_t)P + 1 + LSHPC_STAGE <= LSHPC_CAP_MAX ? LshpcRoute::screen : LshpcRoute::lists;
+}
+
+// Probe masks of get_hypercube_combined_buckets: 0 first (main bucket), then
+// Hamming distance 1 (bit 0..k-1), 2 (lexicographic i<j), ... ; probes == 1
+// starts at distance 2 (lsh_cube.hpp:148-150); stops when the cube is exhausted.
+inline std::vector<int32_t> probe_masks(int probes, int k) {
+    std::vector<int32_t> m(1, 0);
+    int remaining = probes;
+    int dist = probes > 1 ? 1 : 2;
+    std::vector<int> comb(64);
+    while (remaining > 0 && dist <= k) {
+        for (int i = 0; i < dist; i++) comb[i] = i;
+        for (;;) {
+            int mask = 0;
+            for (int i = 0; i < dist; i++) mask |= 1 << comb[i];
+            m.push_back(mask);
+            if (--remaining == 0) break;
+            int p = dist - 1;
+            while (p >= 0 && comb[p] == k - dist + p) p--;
+            if (p < 0) break;
+            comb[p]++;
+            for (int q = p + 1; q < dist; q++) comb[q] = comb[q - 1] + 1;
+        }
+        dist++;
+    }
+    return m;
+}
+
+// Membership in probe_masks(probes, k) without the list. The masks after 0 run
+// through the shells of popcount lo, lo + 1, ... (lo = 1, or 2 for probes == 1),
+// each in lexicographic order of its ascending bit positions; with bit 0 first,
+// that order is the descending order of the bit-reversed masks. So with `last`
+// the popcount of the final mask and rev_last its bit reversal (0: the shell is
+// whole), y is a mask iff y == 0, or popcount(y) in [lo, last), or popcount(y)
+// == last and rev(y) >= rev_last. No mask after 0 (probes <= 0, k < lo): last
+// = 0, which no popcount >= lo equals.
+#if defined(__HIPCC__)
+#define LSHPC_HD __host__ __device__
+#else
+#define LSHPC_HD
+#endif
+LSHPC_HD inline uint32_t cubepc_rev(uint32_t v) {
+#if defined(__clang__)
+    return __builtin_bitreverse32(v);
+#else
+    v = (v >> 16) | (v << 16);
+    v = ((v & 0xff00ff00u) >> 8) | ((v & 0x00ff00ffu) << 8);
+    v = ((v & 0xf0f0f0f0u) >> 4) | ((v & 0x0f0f0f0fu) << 4);
+    v = ((v & 0xccccccccu) >> 2) | ((v & 0x33333333u) << 2);
+    return ((v & 0xaaaaaaaau) >> 1) | ((v & 0x55555555u) << 1);
+#endif
+}
+struct CubeProbe {
+    uint32_t shells;         // lo | last << 8
+    uint32_t rev_last;
+};
+LSHPC_HD inline bool cubepc_member(uint32_t y, uint32_t shells, uint32_t rev_last) {
+    const int p = __builtin_popcount(y), lo = (int)(shells & 0xffu), last = (int)(shells >> 8);
+    // bitwise on purpose: the short-circuit form costs the kernel a branch per test
+    return (y == 0u) | ((p >= lo) & ((p < last) | ((p == last) & (cubepc_rev(y) >= rev_last))));
+}
+inline int64_t cubepc_choose(int n, int r) {
+    if (r < 0 || r > n) return 0;
+    int64_t c = 1;
+    for (int i = 1; i <= r; i++) c = c * (n - r + i) / i;        // exact: C(n - r + i, i) at every step
+    return c;
+}
+inline CubeProbe cubepc_probe(int probes, int k) {
+    const int lo = probes > 1 ? 1 : 2;
+    int64_t remaining = probes;
+    int last = 0;
+    uint32_t rev_last = 0;
+    for (int dist = lo; remaining > 0 && dist <= k; dist++) {
+        const int64_t shell = cubepc_choose(k, dist);
+        last = dist;
+        rev_last = 0;
+        if (remaining >= shell) {
+            remaining -= shell;
+            continue;
+        }
+        // the shell's combination of lexicographic rank remaining - 1
+        int64_t r = remaining - 1;
+        uint32_t mask = 0;
+        for (int i = 0, c = 0; i < dist; i++, c++) {
+            for (;; c++) {
+                const int64_t with_c = cubepc_choose(k - 1 - c, dist - 1 - i);
+                if (r < with_c) break;
+                r -= with_c;
+            }
+            mask |= 1u << c;
+        }
+        rev_last = cubepc_rev(mask);
+        remaining = 0;
+    }
+    return CubeProbe{(uint32_t)lo | (uint32_t)last << 8, rev_last};
+}
 
 inline size_t lshpc_round256(size_t b) { return (b + 255) / 256 * 256; }
 

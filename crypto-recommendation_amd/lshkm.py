@@ -147,6 +147,7 @@ def lib():
             "lshkm_rand_selection": (i32, [u64, i64, i32, vp]),
             "lshkm_p_closest": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, i32, vp, vp, vp]),
             "lshkm_lsh_p_closest": (i32, [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp]),
+            "lshkm_cube_p_closest": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
             "lshkm_top_n_recom": (i32, [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i32, i32, vp]),
             "lshkm_cluster_top_n": (i32, [vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, i32, vp]),
             "lshkm_cluster_sims": (i32, [vp, vp, i64, i32, vp, vp, i32, vp, i64, vp, vp, vp, vp, i64,
@@ -1019,6 +1020,33 @@ def lsh_recommend(ctx, lsh, X, x_mean, U, u_mean, unk_ptr, unk_idx, P, n_top):
     lists. Returns (top [nq][n_top] int32, cnt [nq]); cnt == 0 marks the users
     main.cpp:161 skips (no neighbours)."""
     idx, sim, cnt = lsh_p_closest(ctx, lsh, X, U, P)
+    return top_n_recom(ctx, X, x_mean, u_mean, unk_ptr, unk_idx, idx, sim, cnt, n_top), cnt
+
+
+def cube_p_closest(ctx, cube, X, U, probes, P, counts=False):
+    """get_hypercube_combined_buckets then get_P_closest for all users of U at
+    once (lshkm_cube_p_closest): the P closest of each user's hypercube
+    neighbours (the main bucket and `probes` probed ones), straight from the
+    built cube over X. X [N][d], U [nq][d] fp64 device tensors. Returns what
+    cube.query(U, probes, device=True) -> p_closest returns, bit for bit, and
+    leaves the cube as that query does; with counts each user's neighbour count
+    (int64 [nq]) as a fourth."""
+    torch = ctx.torch
+    nq = U.shape[0]
+    idx = ctx.empty((nq, P), torch.int32)
+    sim = ctx.empty((nq, P), torch.float64)
+    cnt = ctx.empty((nq,), torch.int32)
+    nc = ctx.empty((nq,), torch.int64) if counts else None
+    _ck(lib().lshkm_cube_p_closest(cube.h, _t_ptr(X), _t_ptr(U), nq, int(probes), P, _t_ptr(idx), _t_ptr(sim),
+                                   _t_ptr(cnt), _t_ptr(nc)))
+    return (idx, sim, cnt, nc) if counts else (idx, sim, cnt)
+
+
+def cube_recommend(ctx, cube, X, x_mean, U, u_mean, unk_ptr, unk_idx, probes, P, n_top):
+    """The hypercube recommender as one call: cube_p_closest, then top_n_recom
+    over its lists. Returns (top [nq][n_top] int32, cnt [nq]) as lsh_recommend
+    does; cnt == 0 marks the users to skip (no neighbours)."""
+    idx, sim, cnt = cube_p_closest(ctx, cube, X, U, probes, P)
     return top_n_recom(ctx, X, x_mean, u_mean, unk_ptr, unk_idx, idx, sim, cnt, n_top), cnt
 
 

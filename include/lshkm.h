@@ -133,12 +133,12 @@ int lshkm_memcpy_d2h(lshkm_ctx ctx, void* dst_host, const void* src_dev, int64_t
  *     i.e. that took a rounding-aware chain instead of plain fp64 adds,
  * 10 = PAM update: clusters whose argmin went through the MFMA screen,
  * 11 = PAM update: members of those clusters the screen left to the exact chain,
- * 12 = lshkm_lsh_p_closest: users the MFMA screen settled,
- * 13 = lshkm_lsh_p_closest: users sent to the lists path (a poison row or user, a
- *      kept-list overflow, a tie or a NaN among the first P + 1; every user of a
- *      call the screen does not take),
- * 14 = lshkm_lsh_p_closest: candidates the screen kept for the exact pass,
- * 15 = lshkm_lsh_p_closest: candidates the screen saw. */
+ * 12 = lshkm_lsh_p_closest / lshkm_cube_p_closest: users the MFMA screen settled,
+ * 13 = ... users sent to the lists path (a poison row or user, a kept-list
+ *      overflow, a tie or a NaN among the first P + 1; every user of a call the
+ *      screen does not take),
+ * 14 = ... candidates the screen kept for the exact pass,
+ * 15 = ... candidates the screen saw. */
 int lshkm_get_stat(lshkm_ctx ctx, int which, int64_t* value_host);
 int lshkm_reset_stats(lshkm_ctx ctx);
 /* HIP-event timing of the dominant kernel launch (the fused hash+assign kernel)
@@ -553,6 +553,23 @@ int lshkm_p_closest(lshkm_ctx ctx, const double* X_dev, int64_t N, int d, const 
 int lshkm_lsh_p_closest(lshkm_lsh lsh, const double* X_dev, const double* U_dev, int64_t nq, int32_t excl_lo,
                         int32_t excl_hi, int P, int32_t* out_idx_dev, double* out_sim_dev, int32_t* out_cnt_dev,
                         int64_t* ncand_dev);
+/* The same from a built hypercube: get_hypercube_combined_buckets
+ * (lsh_cube.hpp:138-177) followed by get_P_closest, without the neighbour
+ * vectors. out_idx_dev / out_sim_dev / out_cnt_dev are bit for bit what
+ * lshkm_cube_query_f64(cube, U, nq, probes) -> lshkm_p_closest produce, on any
+ * doubles (ties, NaNs, zero rows, empty neighbourhoods); ncand_dev [nq] or NULL:
+ * each user's combined bucket's length. X_dev [N][d]: the fp64 rows the cube was
+ * built over (lshkm_cube_build_f64); U_dev [nq][d]; probes as lshkm_cube_query
+ * takes it. The handle is left as lshkm_cube_query_f64 on the same users leaves
+ * it (the euclidean cube's coin memo and engine state). Either metric with
+ * d <= 128 and P <= 447 goes through the f32 MFMA screen of lshkm_lsh_p_closest
+ * (a row is a user's candidate iff the XOR of their vertices is a probe mask;
+ * DESIGN.md 5e); everything else, and every user the screen cannot decide, runs
+ * the sequence above in chunks of bounded size. The cube must be built
+ * (LSHKM_ERR_STATE); P < 1 is LSHKM_ERR_ARG. nq < 2^31; nq == 0 writes nothing.
+ * Returns after its workspace is free for the next call. */
+int lshkm_cube_p_closest(lshkm_cube cube, const double* X_dev, const double* U_dev, int64_t nq, int probes, int P,
+                         int32_t* out_idx_dev, double* out_sim_dev, int32_t* out_cnt_dev, int64_t* ncand_dev);
 /* get_top_N_recom (crypto_rec.hpp:305-325) over lshkm_p_closest's lists:
  * predicted scores of each user's unknown indexes (get_predicted_user_sim,
  * :280-302; unk_* = CSR of the ascending unknown indexes, std::set order),

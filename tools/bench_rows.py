@@ -6,7 +6,7 @@ syncs (host launch and sync latency included) -- next to the CPU restatement (or
 thread, OMP_NUM_THREADS=1, kind "port") on a bounded sample of the same
 workload, scaled to the row's unit. Prints one JSON line per row.
 
-    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64,cv,lshpc] [--no-cpu]
+    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64,cv,lshpc,cubepc] [--no-cpu]
     python tools/bench_rows.py --rows main_program --main-dir DIR [--main-ref-seconds S]
 """
 import argparse
@@ -113,6 +113,22 @@ def emit(row, unit, units, t_gpu, cpu=None, note="", bytes_per_unit=None):
     if note:
         line["note"] = note
     print(json.dumps(line), flush=True)
+
+
+def cube_probes_for(cube, Q, k, target):
+    """The probe count (> 1) at which the users of Q see, on average, closest to
+    `target` neighbours in the built cube, and that average: for probes > 1 a
+    user's buckets are a prefix of its full probe sequence."""
+    rp, _ = cube.buckets()
+    sizes = np.diff(rp)
+    uv = cube.vertices(Q).cpu().numpy()
+    vs, n = np.unique(uv, return_counts=True)
+    mean = np.zeros(1 << k)
+    for v, c in zip(vs, n):
+        mean += c * np.cumsum(sizes[oracle.cube_probe_seq(int(v), 1 << k, k)])
+    mean /= len(uv)                                   # mean[p]: the average over p + 1 buckets, i.e. probes = p
+    p = 2 + int(np.argmin(np.abs(mean[2:] - target)))
+    return p, float(mean[p])
 
 
 def main():
@@ -439,24 +455,25 @@ def main():
                  + f"; {cand} candidates after exclusion ({cand / F:.0f} per user); fold 0 sum equals the driver's: {same}")
             del X, W, H, lsh, ptr, idx, eptr, eidx
 
+    def event_ms(fn, warm=3, reps=10):
+        """HIP events around single calls: (median, min, max) ms of reps after warm warm-ups."""
+        ms = []
+        for i in range(warm + reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            ctx.sync()
+            torch.cuda.synchronize()
+            if i >= warm:
+                ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms)), float(min(ms)), float(max(ms))
+
     if "lshpc" in rows:      # main.cpp:160-162 from the index: the lists sequence against lshkm_lsh_p_closest
         d, k, L, P = 100, 4, 5, 20
         tsec, seeds = 1546300800, np.arange(1, 11, dtype=np.uint64)
 
-        def event_ms(fn, warm=3, reps=10):
-            """HIP events around single calls: (median, min, max) ms of reps after warm warm-ups."""
-            ms = []
-            for i in range(warm + reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                e0.record()
-                fn()
-                e1.record()
-                ctx.sync()
-                torch.cuda.synchronize()
-                if i >= warm:
-                    ms.append(e0.elapsed_time(e1))
-            return float(np.median(ms)), float(min(ms)), float(max(ms))
         for N in (int(v) for v in a.lshpc_sizes.split(",")):
             # the cv row's fold-0 inputs: the pool W in split order, fold 0's users hidden, excluded as rows [0, F)
             xh, xmh, uph, uih = cv_users(N, d)
@@ -497,6 +514,54 @@ def main():
                 "note": "query + exclusion + p_closest against lshkm_lsh_p_closest on the same handle; HIP events, "
                         "median of 10 after 3 warm-ups; stats per call"}), flush=True)
             del W, Q, lsh, out
+
+    if "cubepc" in rows:     # the same from a built hypercube: cube.query + p_closest against lshkm_cube_p_closest
+        # k = 6; probes: the count at which a user sees on average closest to 0.41 of the pool, the lshpc row's
+        # share (8,130 / 20,000, 82,579 / 200,000): these rows fill the 64 vertices unevenly, so it is found, not set
+        d, k, P = 100, 6, 20
+        tsec, seeds = 1546300800, np.arange(1, 11, dtype=np.uint64)
+        for N in (int(v) for v in a.lshpc_sizes.split(",")):
+            # the cv row's fold-0 inputs, as the lshpc row's: the pool W in split order, fold 0's users hidden
+            xh, xmh, uph, uih = cv_users(N, d)
+            X, xm, up, ui = (torch.from_numpy(v).to(ctx.dev) for v in (xh, xmh, uph, uih))
+            F = N // 10
+            split = torch.from_numpy(lshkm.cv_split10(tsec, N).ravel().astype(np.int64)).to(ctx.dev)
+            draw = torch.full((N,), int(lshkm.cv_draws([tsec])[0, 0]), dtype=torch.int32, device=ctx.dev)
+            H, hm, hi, old = lshkm.cv_hide(ctx, X, xm, up, ui, draw)
+            W = X[split].contiguous()
+            W[:F] = H[split[:F]]
+            R, st = lshkm.params_cube_cosine(int(seeds[0]), k, d)
+            cube = lshkm.Cube(ctx, "cosine", d, k, R=R, rng_state=st)
+            cube.build(W)
+            Q = W[:F].contiguous()
+            del X, H
+            probes, _ = cube_probes_for(cube, Q, k, 0.41 * 10 * F)
+            out = {}
+
+            def sequence():
+                ptr, idx = cube.query(Q, probes, device=True)
+                out["seq"] = lshkm.p_closest(ctx, W, Q, ptr, idx, P)
+                out["cand"] = int(ptr[-1])
+
+            def direct():
+                out["new"] = lshkm.cube_p_closest(ctx, cube, W, Q, probes, P)
+            t_seq = event_ms(sequence)
+            ctx.reset_stats()
+            t_new = event_ms(direct)
+            st = [ctx.stat(i) // 13 for i in (12, 13, 14, 15)]
+            same = all(torch.equal(g, w) for g, w in zip((out["new"][0], out["new"][1].view(torch.int64), out["new"][2]),
+                                                         (out["seq"][0], out["seq"][1].view(torch.int64), out["seq"][2])))
+            print(json.dumps({
+                "row": "cubepc", "users": F, "pool": 10 * F, "d": d, "k": k, "probes": probes, "P": P,
+                "candidates": out["cand"], "candidates_per_user": out["cand"] / F,
+                "sequence_ms": {"median": t_seq[0], "min": t_seq[1], "max": t_seq[2]},
+                "cube_p_closest_ms": {"median": t_new[0], "min": t_new[1], "max": t_new[2]},
+                "speedup_median": t_seq[0] / t_new[0], "bar_new_max_below_sequence_min": t_new[2] < t_seq[1],
+                "stat_settled": st[0], "stat_lists": st[1], "stat_kept": st[2], "stat_seen": st[3],
+                "outputs_identical": same,
+                "note": "cube.query + p_closest against lshkm_cube_p_closest on the same handle; HIP events, "
+                        "median of 10 after 3 warm-ups; stats per call"}), flush=True)
+            del W, Q, cube, out
 
     if "main_program" in rows:   # the whole program (main.cpp:36-390) on the files of gen_main_golden --time FACTOR DIR
         sys.path.insert(0, os.path.join(ROOT, "crypto-recommendation_amd"))
