@@ -102,7 +102,8 @@ enum Stat {
     STAT_LSHPC_LISTS = 13,   // ... users sent to the lists path (poison, overflow, tie / NaN; or the whole call)
     STAT_LSHPC_KEPT = 14,    // ... candidates the screen kept for the exact pass
     STAT_LSHPC_SEEN = 15,    // ... candidates it saw
-    STAT_COUNT = 16
+    STAT_PAIR_ROWS = 16,     // rows of STAT_ASSIGN_AMBIG the refinement named both candidates of and decided itself
+    STAT_COUNT = 17
 };
 
 constexpr int WAVE = 64;

@@ -67,6 +67,7 @@ int fused_workspace(lshkm_ctx ctx, const FusedShape& sh, FusedWorkspace& w) {
     w.hfix = (unsigned long long*)at(ctx->ws_hfix, l.hfix_off);
     w.cfix = (unsigned long long*)at(ctx->ws_hfix, l.cfix_off);
     w.hfix2 = (unsigned long long*)at(ctx->ws_hfix, l.hfix2_off);
+    w.pairs = (unsigned long long*)at(ctx->ws_hfix, l.pair_off);
     if (l.part) w.part = ctx->ws_part.as<float4>();
     w.cnt = ctx->ws_counter.as<unsigned long long>();
     if (l.xn2) w.xn2 = ctx->ws_xn2.as<double>();
@@ -79,7 +80,7 @@ int fused_workspace(lshkm_ctx ctx, const FusedShape& sh, FusedWorkspace& w) {
 FusedArgs fused_common_args(lshkm_ctx ctx, const AssignRequest& q, const FusedShape& sh, const FusedWorkspace& w) {
     FusedArgs a{};
     a.X = q.X.f64 ? nullptr : q.X.f(); a.X64 = q.X.f64 ? q.X.d() : nullptr;
-    a.N = q.N; a.d = q.d;
+    a.N = q.N; a.d = q.d; a.K = q.K;
     a.xvec = sh.rows == 1 ? (a.d % 4 == 0 && ((uintptr_t)a.X & 15) == 0) : (a.d % 2 == 0 && ((uintptr_t)a.X64 & 15) == 0);
     a.Ch = w.Ch; a.Cl = w.Cl; a.cnh = w.cnh; a.cbound = w.cbound; a.Kpad = sh.Kpad();
     a.C64 = w.C64p ? w.C64p : q.C; a.Cd = q.C;
@@ -280,6 +281,7 @@ int fused_assign(lshkm_ctx ctx, const AssignRequest& q) {
     exact_rows.p = w.list1; exact_rows.count = w.cnt + CNT_AMBIG; exact_rows.bound = q.N;
     RecList dist_fix[2];      // winners listed for their distance alone
     int ndist_fix = 0;
+    RecList pair_rows;        // uncertified rows with both candidates named (bound 0: none)
     SideFork side{ctx};
     if (q.N > 0 && route.form == FusedForm::chunked) {
         FusedArgs a = common;
@@ -326,11 +328,17 @@ int fused_assign(lshkm_ctx ctx, const AssignRequest& q) {
         rf.ambig = l2.p; rf.ambig_count = l2.count; rf.seg_counts = l2.counts;
         // its declined cosine distances go to hfix2 (counts beside list2's)
         rf.hfix = cosine ? w.hfix2 : hi.hfix; rf.hfix_count = cosine ? w.cnt + CNT_CFIX : hi.hfix_count;
+        // euclidean, one refinement pass: the rows it names both candidates of go
+        // to the pair list (counts beside list2's), which each block decides itself
+        // before it ends; LSHKM_PAIR_PASS=0: all to list2
+        if (sh.pairs() && !test_switch("LSHKM_PAIR_PASS", "0")) {
+            pair_rows = segmented(w.pairs, w.cnt + CNT_PAIR, w.seg2, q, p);
+            rf.pairs = pair_rows.p; rf.pair_count = pair_rows.count;
+        }
         if ((rc = fused_refine_passes(s, rf, p))) return rc;
         if (cosine && (rc = side.join())) return rc;
         if ((rc = kstatus("fused_hi_kernel"))) return rc;
-        exact_rows = l2;
-        if (cosine || pwfix) dist_fix[ndist_fix++] = segmented(w.cfix, w.cnt + CNT_CFIX, w.seg3, q, p);
+        exact_rows = l2;        if (cosine || pwfix) dist_fix[ndist_fix++] = segmented(w.cfix, w.cnt + CNT_CFIX, w.seg3, q, p);
         if (cosine) dist_fix[ndist_fix++] = segmented(w.hfix2, w.cnt + CNT_CFIX, w.seg2, q, p);
     }
     if (ctx->timing) LSHKM_HIP(hipEventRecord(ctx->tev[1], s));
@@ -338,11 +346,16 @@ int fused_assign(lshkm_ctx ctx, const AssignRequest& q) {
         return rc;
     if ((rc = side.join())) return rc;
     {
-        int di[3], n = 0;
-        const unsigned long long* sp[3];
+        int di[5], n = 0;
+        const unsigned long long* sp[5];
         di[n] = STAT_REFINED; sp[n++] = w.cnt + CNT_REFINED;
         if (sh.hash) { di[n] = STAT_HASH_FIX; sp[n++] = w.cnt + CNT_HFIX; }
         di[n] = STAT_ASSIGN_AMBIG; sp[n++] = w.cnt + CNT_AMBIG;
+        // pair rows are uncertified rows too (atomic adds: one destination twice is fine)
+        if (pair_rows.bound > 0) {
+            di[n] = STAT_ASSIGN_AMBIG; sp[n++] = w.cnt + CNT_PAIR;
+            di[n] = STAT_PAIR_ROWS; sp[n++] = w.cnt + CNT_PAIR;
+        }
         if ((rc = launch_add_counters(s, ctx->stats.as<unsigned long long>(), n, di, sp))) return rc;
     }
     if (cosine || pwfix) {

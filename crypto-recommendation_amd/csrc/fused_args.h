@@ -79,6 +79,13 @@ struct FusedArgs {
     const double* Cd;                // general rows: the caller's [K][d] centroids (cosine winners)
     int pw_lds;                      // fp64 rows, exact distances: LDS byte offset of the chain's
                                      // gp_sq_wave buffers (4 KiB per wave), 0: PwAcc + fix-up list
+    // euclidean single-pass refinement: the uncertified rows whose two candidates it
+    // can name, one record row | I1 << 32 | I2 << 48 each (pair_record), block b's in
+    // segment b, counted in seg_counts[SEG_SLOTS * b + SEG_FIX]; null: every
+    // uncertified row goes to ambig
+    unsigned long long* pairs;
+    unsigned long long* pair_count;
+    int K;                           // real centroids of the call (a pair names none past them)
 };
 
 }  // namespace lshkm

@@ -20,6 +20,8 @@
 #include "exact.h"
 #include "hash_tile.h"
 #include "fused_args.h"
+#include "pair_merge.h"
+#include "pick.h"
 
 namespace lshkm {
 
@@ -45,6 +47,7 @@ struct FusedWorkspace {
     int32_t *list2 = nullptr, *seg2 = nullptr;   // the refinement's rows (seg2: + its declines' counts)
     int32_t* seg3 = nullptr;                     // counts of cfix
     unsigned long long *hfix = nullptr, *cfix = nullptr, *hfix2 = nullptr;   // FusedLayout::fix regions
+    unsigned long long* pairs = nullptr;         // ... the refinement's pair rows (counts beside list2's)
     float4* part = nullptr;                      // pass state (Kpad > FP_KMAX)
     unsigned long long* cnt = nullptr;           // CNT_* device counters
     double* xn2 = nullptr;                       // cosine on fp64 rows: [N] sum_j pow(x_j, 2)
@@ -216,6 +219,25 @@ __device__ inline void tile_epilogue(const float (&sv)[16], float& m1, float& m2
         m2 = __builtin_amdgcn_fmed3f(m2, __builtin_amdgcn_fmed3f(m1, ta, tb), 0x1.fffffep127f);
         m1 = vmax3(m1, ta, tb);
     }
+}
+
+// The refinement's epilogue where it names the runner-up too (pair_merge.h):
+// the tile's own best three first -- its 16 scores differ in their index bits,
+// so they are distinct and three med3 / max steps per score keep them sorted --
+// then those three, best first, into the running state with the tile's number.
+// m1 and m2 take the values tile_epilogue gives them, and t1 the tile it notes.
+__device__ inline void tile_epilogue3(const float (&sv)[16], int tile, Top3& s) {
+    float a1 = -__builtin_inff(), a2 = a1, a3 = a1;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const float v = __uint_as_float((__float_as_uint(sv[r]) & ~0xFu) | (uint32_t)r);
+        a3 = __builtin_amdgcn_fmed3f(a3, a2, v);
+        a2 = __builtin_amdgcn_fmed3f(a2, a1, v);
+        a1 = vmax3(a1, v, v);
+    }
+    top3_insert(s, a1, tile);
+    top3_insert(s, a2, tile);
+    top3_insert(s, a3, tile);
 }
 
 }  // namespace lshkm

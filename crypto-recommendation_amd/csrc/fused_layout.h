@@ -90,7 +90,8 @@ constexpr int CNT_AMBIG = 0;         // rows left to the listed exact pass
 constexpr int CNT_HFIX = 1;          // hash fix-up records
 constexpr int CNT_REFINED = 2;       // rows the hi-only passes left to the refinement
 constexpr int CNT_CFIX = 3;          // cosine declines / pow fix-ups
-constexpr size_t FUSED_COUNTER_BYTES = 64, FUSED_COUNTER_CLEAR = 32;
+constexpr int CNT_PAIR = 4;          // uncertified rows the refinement named both candidates of and decided itself
+constexpr size_t FUSED_COUNTER_BYTES = 64, FUSED_COUNTER_CLEAR = 40;
 
 // ---- the workspace of one fused assignment
 struct FusedShape {
@@ -107,6 +108,9 @@ struct FusedShape {
     // exact euclidean distances: rows whose chain met an inexact square (glibc's
     // pow(x, 2) may differ from x*x) are listed for the fix-up
     bool pwfix() const { return !cosine && !fast; }
+    // the single-pass euclidean refinement names the two candidates of the rows
+    // it can (the multi-pass form carries no runner-up tile: all to list2)
+    bool pairs() const { return !cosine && Kpad() <= FP_KMAX; }
 };
 struct FusedLayout {
     static constexpr size_t NONE = ~(size_t)0;
@@ -121,13 +125,14 @@ struct FusedLayout {
     size_t fix = 0;                  // u64 records, regions of list_cap entries at hfix_off / cfix_off / hfix2_off:
                                      // [hash fix-ups][cosine declines of the hi-only passes, or pow fix-ups]
                                      // [cosine declines of the refinement]
+                                     // [pair rows of the euclidean refinement]
     size_t part = 0;
     size_t tuples = 0;
     size_t cf32 = 0;                 // [C32: Kpad x 128 f32][rn32: Kpad f32] at 0 / rn32_off
     size_t c64p = 0;                 // general rows of d < 128: [Kpad][128] zero-padded fp64 centroids
     size_t xn2 = 0;                  // cosine on fp64 rows: [N] sums of squares
     size_t cl_off = 0, cnh_off = 0, nbv_off = 0, rn32_off = 0;
-    size_t hfix_off = NONE, cfix_off = NONE, hfix2_off = NONE;
+    size_t hfix_off = NONE, cfix_off = NONE, hfix2_off = NONE, pair_off = NONE;
 };
 inline FusedLayout fused_layout(const FusedShape& q) {
     FusedLayout l;
@@ -148,6 +153,7 @@ inline FusedLayout fused_layout(const FusedShape& q) {
     if (q.hash || q.cosine) l.hfix_off = 0;
     if (q.cosine || pwfix) l.cfix_off = regions++ * cap * 8;
     if (q.cosine) l.hfix2_off = regions++ * cap * 8;
+    if (q.pairs()) l.pair_off = regions++ * cap * 8;
     l.fix = regions * cap * 8;
     if (q.cosine || pwfix) l.seg3 = SEG_COUNTER_BYTES;
     if (Kpad > (size_t)FP_KMAX) l.part = (size_t)(l.part_bytes = fused_part_bytes(q.N));

@@ -37,6 +37,70 @@ __device__ inline void tile_scores(const floatx16& acc_hi, const floatx16& acc_l
 __host__ __device__ constexpr int fp_lds_bytes(int Kpad) { return 16 + 2 * Kpad * FU_RS * 2 + Kpad * 4; }
 static_assert(fp_lds_bytes(FP_KMAX) <= 160 * 1024, "refinement LDS image exceeds 160 KiB");
 
+// ---- the pair rows' finish. A block decides its own pair rows before it ends,
+// in the LDS its centroid image leaves behind: a wave takes FP_PAIR_REC records
+// of the block's segment at a time, stages their rows (8 rows' values in flight
+// at once, as the pruned pass loads its group), and two adjacent lanes per
+// record run the two chains, the even lane on I1 and the odd one on I2. The pick
+// between the two is the pruned pass's own (pruned_pick_euclid, pick.h), so
+// argmin and distance are what that pass gives these rows. (As a kernel of its
+// own after the refinement this waited for the hash fix-up's blocks, which fill
+// every SIMD's registers, to end: DESIGN.md §9.)
+constexpr int FP_PAIR_REC = 16;
+constexpr int FP_PAIR_RS = FU_D | 1;     // odd row stride: element j of the staged rows in different banks
+__host__ __device__ constexpr int fp_pair_lds_bytes(int rows) {
+    return 16 + FP_WAVES * FP_PAIR_REC * FP_PAIR_RS * (rows == 2 ? 8 : 4);
+}
+static_assert(fp_pair_lds_bytes(2) <= 160 * 1024, "pair staging exceeds 160 KiB");
+__host__ __device__ inline unsigned long long pair_record(int64_t row, int i1, int i2) {
+    return (unsigned long long)(uint32_t)row | ((unsigned long long)(uint32_t)i1 << 32) |
+           ((unsigned long long)(uint32_t)i2 << 48);
+}
+template <int ROWS>
+__device__ inline void pair_finish(const FusedArgs& a, const unsigned long long* recs, int total, char* lds,
+                                   int wave, int lane) {
+    using TX = std::conditional_t<ROWS == 2, double, float>;
+    const TX* X;
+    if constexpr (ROWS == 2) X = a.X64; else X = a.X;
+    const int d = ROWS == 0 ? FU_D : a.d;
+    TX* xs = reinterpret_cast<TX*>(lds) + wave * FP_PAIR_REC * FP_PAIR_RS;
+    for (int base = wave * FP_PAIR_REC; base < total; base += FP_WAVES * FP_PAIR_REC) {
+        const int i = base + (lane >> 1);
+        const unsigned long long rec = recs[min(i, total - 1)];
+        int64_t row = (int64_t)(uint32_t)rec;
+        int c = (lane & 1) ? (int)(rec >> 48) : (int)((rec >> 32) & 0xFFFFu);
+        // lanes past the step's records, and a record that names nothing real, sit out
+        if (lane >= 2 * FP_PAIR_REC || i >= total || row >= a.N) row = -1;
+        if (row < 0 || c >= a.K) c = -1;
+#pragma unroll 1
+        for (int r0 = 0; r0 < FP_PAIR_REC && base + r0 < total; r0 += 8) {
+            TX xv[8][FU_D / 64];
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                const int64_t rr = __shfl(row, 2 * (r0 + r));
+#pragma unroll
+                for (int u = 0; u < FU_D / 64; u++) {
+                    const int j = lane + 64 * u;
+                    xv[r][u] = j < d && rr >= 0 ? X[rr * d + j] : TX(0);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 8; r++)
+#pragma unroll
+                for (int u = 0; u < FU_D / 64; u++) xs[(r0 + r) * FP_PAIR_RS + lane + 64 * u] = xv[r][u];
+        }
+        wave_sync();
+        double best = 0.0;
+        int bi = -1;
+        pruned_pick_euclid<2>(xs + ((lane >> 1) & (FP_PAIR_REC - 1)) * FP_PAIR_RS, a.Cd, d, c, !a.fast_dist, best, bi);
+        if (!(lane & 1) && bi >= 0) {
+            a.assign[row] = bi;
+            a.dist[row] = best;
+        }
+        wave_sync();
+    }
+}
+
 // For Kpad <= 256 the whole split centroid set (2 x 256 x 272 B) fits in LDS,
 // so one block per CU loads it ONCE and its 8 waves (2 per SIMD) then loop
 // independently over 32-row tiles: no barrier in the main loop, rows go
@@ -44,7 +108,10 @@ static_assert(fp_lds_bytes(FP_KMAX) <= 160 * 1024, "refinement LDS image exceeds
 // lane&31 -- the B-operand layout) and stay there, exact, for the winner's
 // reference-order distance. Block b's rows are segment b of the list a hi-only
 // pass wrote (a.list_in, counts in a.list_counts); the rows it cannot certify
-// either go to the exact pass (a.ambig, segment b).
+// either go to the exact pass (a.ambig, segment b) -- or, euclidean and one
+// pass, where the runner-up can be named and every third score lies below the
+// certificate's window, to the block's pair segment (a.pairs), which the block
+// decides itself after its last tile (pair_finish).
 // MET = 1: cosine Lloyd: centroids are normalised in the prep (score x.c/|c|,
 // cnh = 0), the winner distance is exact.h's certified form; declines are
 // listed in a.hfix for the distance fix-up.
@@ -56,7 +123,10 @@ template <int MET, bool MP, int ROWS>
 __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int Kpad = a.Kpad;
-    int* lcount = reinterpret_cast<int*>(smem);          // [0] ambiguous rows, [1] cosine declines
+    // euclidean, one pass: the runner-up is named too (tile_epilogue3), and an
+    // uncertified row with every third score below the window is a pair row
+    constexpr bool PAIR = MET == 0 && !MP;
+    int* lcount = reinterpret_cast<int*>(smem);          // [0] ambiguous rows, [1] cosine declines / pair rows
     _Float16* lch = reinterpret_cast<_Float16*>(smem + 16);
     _Float16* lcl = lch + Kpad * FU_RS;
     float* lcn = reinterpret_cast<float*>(lcl + Kpad * FU_RS);
@@ -89,6 +159,7 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
     // global counter serialises at ~12 ns per add, MI355X_MICROARCH.md "fanin").
     int32_t* ambig_seg = a.ambig + (int64_t)blockIdx.x * a.seg_rows;
     unsigned long long* hfix_seg = a.hfix + (int64_t)blockIdx.x * a.seg_rows;
+    unsigned long long* pair_seg = PAIR && a.pairs ? a.pairs + (int64_t)blockIdx.x * a.seg_rows : nullptr;
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -157,6 +228,7 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
                       0x1p-18 * nx * (double)cmaxf + 0x1p-43 * nx) * (1.f + 0x1p-20f) + 1e-30f;
         float m1 = -__builtin_inff(), m2 = -__builtin_inff();
         int t1 = 0;
+        Top3 top = {m1, m1, m1, 0, 0};        // PAIR: the running state instead of (m1, m2, t1)
         if (MP && !a.pass_first) {
             const float4 st = a.part[ptile * 64 + lane];
             m1 = st.x; m2 = st.y; t1 = __float_as_int(st.z);
@@ -165,15 +237,20 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
         __builtin_amdgcn_s_setprio(MFMA_PRIO);
 #pragma unroll 1
         for (int t = 0; t < ntile32; t++) {
-            const float m1_prev = m1;
             float sv[16];
             floatx16 acc_hi, acc_lo;
             tile_mfma(my_h + t * 32 * FU_RS, my_l + t * 32 * FU_RS, bh, bl, acc_hi, acc_lo);
             tile_scores(acc_hi, acc_lo, lcn + t * 32 + 4 * h, sv);
-            tile_epilogue(sv, m1, m2);
-            t1 = m1 != m1_prev ? t + tg0 : t1;
+            if constexpr (PAIR) {
+                tile_epilogue3(sv, t, top);
+            } else {
+                const float m1_prev = m1;
+                tile_epilogue(sv, m1, m2);
+                t1 = m1 != m1_prev ? t + tg0 : t1;
+            }
         }
         __builtin_amdgcn_s_setprio(0);
+        if constexpr (PAIR) { m1 = top.m1; m2 = top.m2; t1 = top.t1; }
         if (MP && !a.pass_last) {             // more slices to come: carry the state
             a.part[ptile * 64 + lane] = make_float4(m1, m2, __int_as_float(t1), 0.f);
             continue;
@@ -186,6 +263,21 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
         const int I1 = (om1 > m1 || (om1 == m1 && oi1 < i1)) ? oi1 : i1;
         const float M1 = fmaxf(m1, om1);
         const bool cert = x_ok && c_ok && ((double)M2 < (double)M1 - 2.0 * (double)E);
+        // A pair row: not certified, but every score other than I1's and I2's is
+        // below the same window (M3 bounds them all), so no third centroid can be
+        // the reference's nearest or tie with it: {I1, I2} decides the row.
+        bool pair = false;
+        int I2 = 0;
+        if constexpr (PAIR) {
+            const uint32_t l2 = __float_as_uint(m2) & 0xFu;
+            const int i2 = top.t2 * 32 + 8 * (int)(l2 >> 2) + 4 * h + (int)(l2 & 3u);
+            const HalfTop me = {m1, m2, top.m3, i1, i2};
+            const HalfTop ot = {om1, om2, __shfl_xor(top.m3, 32), oi1, __shfl_xor(i2, 32)};
+            const PairMerge pm = I1 == i1 ? merge_halves(me, ot) : merge_halves(ot, me);
+            I2 = pm.I2;
+            pair = pair_seg && !cert && x_ok && c_ok && I1 != I2 && I1 < a.K && I2 < a.K &&
+                   (double)pm.M3 < (double)M1 - 2.0 * (double)E;
+        }
 
         // ---- winner distance in reference order: the squares are independent,
         // only the sum is a chain; dims 8seg..8seg+7 belong to lane half seg & 1,
@@ -271,10 +363,12 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
             }
         }
         PT_MARK(3)
-        const bool amb = valid && !cert;
+        if constexpr (PAIR)
+            seg_append(valid && pair && h == 1, pair_record(row, I1, I2), lcount + 1, pair_seg, lane);
+        const bool amb = valid && !cert && !pair;
         const unsigned long long amask = __ballot(amb && h == 1);
         if (h == 1 && valid) {
-            if (!cert) {
+            if (amb) {
                 int base = 0;
                 const int leader = __builtin_ctzll(amask);
                 if (lane == leader) base = atomicAdd(lcount, __popcll(amask));
@@ -287,18 +381,23 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
     }
     PT_FLUSH
     __syncthreads();
-    // slot 0: ambiguous rows; slot 1: the cosine fix-up list (the last pass decides both)
+    // the block's pair rows, once every wave is done with the image (uniform: pair_seg, lcount)
+    if constexpr (PAIR) {
+        if (pair_seg && lcount[1] > 0) pair_finish<ROWS>(a, pair_seg, lcount[1], smem + 16, wave, lane);
+    }
+    // slot 0: ambiguous rows; slot 1: the cosine fix-up list, or the pair rows (the last pass decides both)
     if (threadIdx.x < 2 && (!MP || (threadIdx.x == 0 ? a.pass_last != 0 : (MET == 1 && a.pass_last)))) {
         const int c = lcount[threadIdx.x];
         a.seg_counts[SEG_SLOTS * blockIdx.x + threadIdx.x] = c;
-        if (c) atomicAdd(threadIdx.x == 0 ? a.ambig_count : a.hfix_count, (unsigned long long)c);
+        if (c) atomicAdd(threadIdx.x == 0 ? a.ambig_count : MET == 1 ? a.hfix_count : a.pair_count, (unsigned long long)c);
     }
 }
 
 template <int MET, bool MP, int ROWS>
 static void refine_launch(hipStream_t s, unsigned nblk, const FusedArgs& a) {
-    hipLaunchKernelGGL((fused_persistent_kernel<MET, MP, ROWS>), dim3(nblk), dim3(FP_THREADS),
-                       (size_t)fp_lds_bytes(a.Kpad), s, a);
+    // the image, or the pair rows' staging where that is larger (few centroids)
+    const int lds = MET == 0 && !MP && a.pairs ? std::max(fp_lds_bytes(a.Kpad), fp_pair_lds_bytes(ROWS)) : fp_lds_bytes(a.Kpad);
+    hipLaunchKernelGGL((fused_persistent_kernel<MET, MP, ROWS>), dim3(nblk), dim3(FP_THREADS), (size_t)lds, s, a);
 }
 template <int MET, bool MP>
 static void refine_rows(hipStream_t s, unsigned nblk, int rows, const FusedArgs& a) {

@@ -25,6 +25,7 @@ STAT_POW_FIX = 8
 STAT_KM_SEQ = 9
 STAT_PAM_SCREENED, STAT_PAM_EXACT = 10, 11
 STAT_LSHPC_SETTLED, STAT_LSHPC_LISTS, STAT_LSHPC_KEPT, STAT_LSHPC_SEEN = 12, 13, 14, 15
+STAT_PAIR_ROWS = 16
 _METRIC = {"euclidean": EUCLIDEAN, "cosine": COSINE, EUCLIDEAN: EUCLIDEAN, COSINE: COSINE}
 DIST_CERTIFIED, DIST_EXACT = 0, 1
 _DIST = {"certified": DIST_CERTIFIED, "default": DIST_CERTIFIED, "exact": DIST_EXACT,

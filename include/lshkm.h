@@ -138,7 +138,9 @@ int lshkm_memcpy_d2h(lshkm_ctx ctx, void* dst_host, const void* src_dev, int64_t
  *      overflow, a tie or a NaN among the first P + 1; every user of a call the
  *      screen does not take),
  * 14 = ... candidates the screen kept for the exact pass,
- * 15 = ... candidates the screen saw. */
+ * 15 = ... candidates the screen saw,
+ * 16 = of counter 1's points, those the fused pass's refinement named the only
+ *      two possible nearest centroids of (decided between the two alone). */
 int lshkm_get_stat(lshkm_ctx ctx, int which, int64_t* value_host);
 int lshkm_reset_stats(lshkm_ctx ctx);
 /* HIP-event timing of the dominant kernel launch (the fused hash+assign kernel)
