@@ -638,32 +638,24 @@ static bool fuse_hash(const lshkm_lsh_s* lsh, int metric, int K, bool f64) {
                        test_switch("LSHKM_FUSED_FORM", "chunked")).form != FusedForm::none;
 }
 
-// K <= 1024, d <= 256: the exact pass scores every centroid in f32 first and
-// runs the exact order only on the candidates the bound leaves (euclidean, and
-// cosine on fp32 rows); LSHKM_EXACT_PASS=full: every centroid
-bool lshkm::exact_pruned(Pts X, int d, int K, int metric) {
-    return K <= 1024 && d <= 256 && !test_switch("LSHKM_EXACT_PASS", "full") &&
-           (metric == LSHKM_METRIC_EUCLIDEAN || !X.f64);
+// The exact pass's form (exact_route, exact_layout.h); LSHKM_EXACT_PASS=full:
+// no pruning
+ExactForm lshkm::exact_form(const AssignJob& q) {
+    return exact_route(q.metric != LSHKM_METRIC_EUCLIDEAN, q.X.f64, q.d, q.K, test_switch("LSHKM_EXACT_PASS", "full"));
 }
 
-static size_t exact_ct_bytes(const AssignJob& q) { return (size_t)q.d * ((q.K + 255) / 256 * 256) * 8; }
-
 int lshkm::exact_listed_prep(lshkm_ctx ctx, const AssignJob& q) {
+    const ExactForm form = exact_form(q);
     int rc;
-    if ((rc = ctx->ws_ct.reserve(exact_ct_bytes(q)))) return rc;
-    return launch_assign_pruned_prep(ctx->stream, q.X.f64, q.d, q.C, q.K, (float*)ctx->ws_ct.p,
-                                     q.metric == LSHKM_METRIC_EUCLIDEAN ? 0 : 1);
+    if ((rc = ctx->ws_ct.reserve(exact_ws_bytes(form, q.d, q.K)))) return rc;
+    return launch_exact_prep(ctx->stream, q, form, ctx->ws_ct.p);
 }
 
 int lshkm::exact_listed(lshkm_ctx ctx, const AssignJob& q, const RowList& l, bool exact_dist, bool prepped,
                         const double* xn2, const double* nbv) {
-    const bool prune = exact_pruned(q.X, q.d, q.K, q.metric);
-    if (!prune && (q.metric != LSHKM_METRIC_EUCLIDEAN || (l.nseg == 0 && q.d > 256)))
-        return launch_assign_exact(ctx->stream, q, l, xn2, nbv);
     int rc;
-    if ((rc = ctx->ws_ct.reserve(exact_ct_bytes(q)))) return rc;
-    if (prune) return launch_assign_pruned_list(ctx->stream, q, (float*)ctx->ws_ct.p, l, exact_dist ? 1 : 0, prepped);
-    return launch_assign_exact_list(ctx->stream, q, (double*)ctx->ws_ct.p, l);
+    if (!prepped && l.bound > 0 && (rc = exact_listed_prep(ctx, q))) return rc;
+    return launch_exact_pass(ctx->stream, q, l, exact_form(q), ctx->ws_ct.p, exact_dist, xn2, nbv);
 }
 
 // The f32-MFMA sequence (d <= 256): certified scores, the listed exact pass,
@@ -714,7 +706,7 @@ static int assign_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const double* C, 
         // Exact reference-order pass over every centroid (cosine metric, or d > 256).
         RowList all;
         all.bound = N;
-        rc = launch_assign_exact(s, q, all);
+        rc = launch_exact_pass(s, q, all, ExactForm::every, nullptr, true, nullptr, nullptr);
     }
     if (rc) { LSHKM_LAUNCH_CHECK(); return rc; }
     if (src_rows_host) {

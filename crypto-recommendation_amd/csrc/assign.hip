@@ -18,12 +18,11 @@
 // s~_c - e_c <= min_c (s~_c + e_c); its distance is then recomputed in exact
 // reference order (fp64, no FMA contraction: sum_j (x_j - c_j)^2, j = 0..d-1,
 // then sqrt). Uncertified points (ties, duplicate centroids, near-ties) go
-// to assign_exact_kernel, which evaluates every centroid in reference order
-// and keeps the first minimum (strict '<', assignment.hpp:66).
+// to the listed exact pass (exact_pass.hip), which evaluates centroids in
+// reference order and keeps the first minimum (strict '<', assignment.hpp:66).
 #include "common.h"
 #include "kernels.h"
 #include "exact.h"
-#include "pick.h"
 
 namespace lshkm {
 
@@ -349,795 +348,6 @@ int launch_cos_fix(hipStream_t s, Pts X, int64_t N, int d, const double* C, cons
     if (X.f64) hipLaunchKernelGGL(cos_fix_kernel<double>, grid, dim3(256), 0, s, X.d(), d, C, rows, count, assign, dist);
     else hipLaunchKernelGGL(cos_fix_kernel<float>, grid, dim3(256), 0, s, X.f(), d, C, rows, count, assign, dist);
     return kstatus("assign.hip");
-}
-
-// ---------------------------------------------------------------- exact pass
-constexpr int XC_MAXV = 4;   // cosine candidate form: K <= 256 (values kept per lane)
-constexpr int XE_SPLIT = 2;  // blocks per list segment (segmented form)
-// One wave per listed row; lane c evaluates centroids c, c+64, ... in the
-// reference's exact order (exact.h); the first minimum wins.
-template <typename TX>
-__global__ __launch_bounds__(256) void assign_exact_kernel(
-    const TX* __restrict__ X, int64_t N, int d, const double* __restrict__ C, int K, int metric,
-    const int32_t* __restrict__ rows, const unsigned long long* __restrict__ row_count, int64_t max_rows,
-    int32_t* __restrict__ assign, double* __restrict__ dist, const int32_t* __restrict__ seg_counts,
-    int64_t seg_rows, const double* __restrict__ xn2, const double* __restrict__ nbv) {
-    const int lane = threadIdx.x & 63;
-    int64_t wglobal = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    int64_t nw = (int64_t)gridDim.x * 4;
-    int64_t total = rows ? (int64_t)*row_count : N;
-    if (seg_counts) {            // XE_SPLIT blocks per segment of the persistent fused form's list
-        const int seg = blockIdx.x % (gridDim.x / XE_SPLIT);   // segments across XCDs (cos_fix_seg_kernel)
-        rows += (int64_t)seg * seg_rows;
-        total = seg_counts[SEG_SLOTS * seg + SEG_ROWS];
-        wglobal = (int64_t)(blockIdx.x / (gridDim.x / XE_SPLIT)) * 4 + (threadIdx.x >> 6);
-        nw = XE_SPLIT * 4;
-    }
-    if (total > max_rows) total = max_rows;
-    for (int64_t it = wglobal; it < total; it += nw) {
-        const int64_t row = rows ? rows[it] : it;
-        const TX* x = X + row * d;
-        double best = 0.0; int bi = -1;
-        // cosine: the row's / centroids' sums of squares precomputed (row_sumsq,
-        // the prep's nbv; glibc pow per square, the same for every pair) when given
-        const double xa = metric == 1 && xn2 ? xn2[row] : -1.0;
-        if (metric == 1 && K <= 64 * XC_MAXV) {
-            // cosine: certified values (exact.h cosine_interval) for every
-            // centroid, the soft-x87 chain only for those whose interval can
-            // still reach the minimum; a row with an unknown value (zero
-            // vectors, NaN/inf, extreme ranges) takes the full soft pass below
-            double v[XC_MAXV], rad[XC_MAXV];
-            int st[XC_MAXV];
-            double U = __builtin_inf();
-            bool unknown = false;
-#pragma unroll
-            for (int k = 0; k < XC_MAXV; k++) {
-                const int c = lane + 64 * k;
-                st[k] = 0; v[k] = 0.0; rad[k] = 0.0;
-                if (c < K) {
-                    st[k] = cosine_interval(x, C + (size_t)c * d, d, v[k], rad[k], xa, nbv ? nbv[c] : -1.0);
-                    unknown |= st[k] == 2;
-                    if (st[k] != 2) U = fmin(U, v[k] + rad[k]);
-                }
-            }
-            if (!__ballot(unknown)) {
-                for (int off = 32; off >= 1; off >>= 1) U = fmin(U, __shfl_xor(U, off));
-#pragma unroll
-                for (int k = 0; k < XC_MAXV; k++) {
-                    const int c = lane + 64 * k;
-                    if (c < K && v[k] - rad[k] <= U) {     // non-candidates are strictly above the minimum
-                        const double dd = st[k] == 0 ? v[k] : exact_cosine_x87(x, C + (size_t)c * d, d, xa, nbv ? nbv[c] : -1.0);
-                        if (bi < 0 || dd < best) { best = dd; bi = c; }
-                    }
-                }
-                for (int off = 32; off >= 1; off >>= 1) {
-                    const double ob = __shfl_xor(best, off);
-                    const int oi = __shfl_xor(bi, off);
-                    const bool take = oi >= 0 && (bi < 0 || ob < best || (ob == best && oi < bi));
-                    if (take) { best = ob; bi = oi; }
-                }
-                if (lane == 0) {
-                    assign[row] = bi;
-                    dist[row] = best;
-                }
-                continue;
-            }
-        }
-        for (int c = lane; c < K; c += 64) {
-            const double dd = metric == 0 ? exact_euclid(x, C + (size_t)c * d, d)
-                                          : exact_cosine_x87(x, C + (size_t)c * d, d, xa, nbv ? nbv[c] : -1.0);
-            // assignment.hpp:66: the -1 sentinel takes centroid 0's distance even
-            // if NaN (a zero vector under cosine), which then blocks every later
-            // '<'; any other NaN is never taken
-            if (bi < 0 ? (dd == dd || c == 0) : dd < best) { best = dd; bi = c; }
-        }
-        // wave argmin: smallest value, then smallest index (= first strict minimum in c order)
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double ob = __shfl_xor(best, off);
-            const int oi = __shfl_xor(bi, off);
-            const bool take = oi >= 0 && (bi < 0 || ob < best || (ob == best && oi < bi));
-            if (take) { best = ob; bi = oi; }
-        }
-        if (lane == 0) {
-            assign[row] = bi < 0 ? 0 : bi;
-            dist[row] = bi < 0 ? -1.0 : best;
-        }
-    }
-}
-
-int launch_assign_exact(hipStream_t s, const AssignJob& q, const RowList& l, const double* xn2, const double* nbv) {
-    const Pts X = q.X;
-    const int64_t N = q.N, max_rows = l.bound, seg_rows = l.seg_rows;
-    const int d = q.d, K = q.K, metric = q.metric, nseg = l.nseg;
-    const double* C = q.C;
-    const int32_t *rows = l.p, *seg_counts = l.seg_counts();
-    const unsigned long long* row_count = l.count;
-    int32_t* assign = q.assign;
-    double* dist = q.dist;
-    if (max_rows <= 0) return 0;
-    // rows == NULL: every row (fallback path); else a device-counted list that is
-    // usually ~0.3% of the rows: one block per CU, waves loop over the list.
-    const int64_t blocks = seg_counts ? (int64_t)nseg * XE_SPLIT : std::min<int64_t>((max_rows + 3) / 4, rows ? 256 : 2048);
-    if (blocks <= 0) return 0;
-    if (X.f64)
-        hipLaunchKernelGGL(assign_exact_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, s, X.d(), N, d, C, K,
-                           metric, rows, row_count, max_rows, assign, dist, seg_counts, seg_rows, xn2, nbv);
-    else
-        hipLaunchKernelGGL(assign_exact_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, X.f(), N, d, C, K,
-                           metric, rows, row_count, max_rows, assign, dist, seg_counts, seg_rows, xn2, nbv);
-    return kstatus("assign.hip");
-}
-
-// Listed (uncertified) rows, euclidean: the same reference-order distances as
-// assign_exact_kernel, but a wave takes XB_R rows at once against a transposed
-// fp64 copy CT[j][c], so each centroid value is loaded once (coalesced, lane =
-// centroid) for XB_R rows. Lane holds centroids c0 + lane + 64i, i < 4.
-constexpr int XB_R = 8;
-constexpr int XB_WAVES = 4;
-constexpr int XB_SPLIT = 4;      // blocks per list segment: 16 waves per CU hide the CT-load latency
-constexpr int XB_DMAX = 256;
-
-__global__ void transpose_centroids_kernel(const double* __restrict__ C, int K, int Kpad, int d,
-                                           double* __restrict__ CT) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (int64_t)d * Kpad) return;
-    const int j = (int)(e / Kpad), c = (int)(e % Kpad);
-    CT[e] = c < K ? C[(size_t)c * d + j] : 0.0;
-}
-
-template <typename TX>
-__global__ __launch_bounds__(64 * XB_WAVES) void assign_exact_batch_kernel(
-    const TX* __restrict__ X, int d, const double* __restrict__ CT, int K, int Kpad,
-    const int32_t* __restrict__ rows, const unsigned long long* __restrict__ row_count, int64_t max_rows,
-    int32_t* __restrict__ assign, double* __restrict__ dist, const int32_t* __restrict__ seg_counts,
-    int64_t seg_rows) {
-    __shared__ TX xs[XB_WAVES][XB_R][XB_DMAX];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t total, g0, gstride;
-    if (seg_counts) {            // XB_SPLIT blocks per segment (the one persistent block b wrote)
-        const int nseg = gridDim.x / XB_SPLIT;   // segments across XCDs (cos_fix_seg_kernel)
-        const int seg = blockIdx.x % nseg, part = blockIdx.x / nseg;
-        rows += (int64_t)seg * seg_rows;
-        total = seg_counts[SEG_SLOTS * seg + SEG_ROWS];
-        g0 = (int64_t)part * XB_WAVES + wave;
-        gstride = (int64_t)XB_SPLIT * XB_WAVES;
-    } else {
-        total = (int64_t)*row_count;
-        if (total > max_rows) total = max_rows;
-        g0 = (int64_t)blockIdx.x * XB_WAVES + wave;
-        gstride = (int64_t)gridDim.x * XB_WAVES;
-    }
-    const int64_t ngroups = (total + XB_R - 1) / XB_R;
-    for (int64_t g = g0; g < ngroups; g += gstride) {
-        const int nr = (int)min((int64_t)XB_R, total - g * XB_R);
-        int64_t myrow[XB_R];
-#pragma unroll
-        for (int r = 0; r < XB_R; r++) myrow[r] = rows[g * XB_R + min(r, nr - 1)];   // pad with the last row
-#pragma unroll
-        for (int r = 0; r < XB_R; r++)
-            for (int j = lane; j < d; j += 64) xs[wave][r][j] = X[myrow[r] * d + j];
-        wave_sync();
-        double best[XB_R];
-        int bi[XB_R];
-#pragma unroll
-        for (int r = 0; r < XB_R; r++) { best[r] = 0.0; bi[r] = -1; }
-        for (int c0 = 0; c0 < K; c0 += 256) {
-            double acc[XB_R][4];
-#pragma unroll
-            for (int r = 0; r < XB_R; r++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) acc[r][i] = 0.0;
-            const double* ct = CT + c0 + lane;   // CT rows are padded to a multiple of 256 columns
-#pragma unroll 4
-            for (int j = 0; j < d; j++) {
-                double cv[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) cv[i] = ct[(size_t)j * Kpad + 64 * i];
-#pragma unroll
-                for (int r = 0; r < XB_R; r++) {
-                    const double xj = (double)xs[wave][r][j];
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        const double df = __dsub_rn(xj, cv[i]);
-                        acc[r][i] = __dadd_rn(acc[r][i], gp_sq(df));
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++) {           // increasing c: strict '<' keeps the first minimum
-                const int c = c0 + lane + 64 * i;
-                if (c >= K) continue;
-#pragma unroll
-                for (int r = 0; r < XB_R; r++) {
-                    const double dd = sqrt(acc[r][i]);
-                    if (bi[r] < 0 || dd < best[r]) { best[r] = dd; bi[r] = c; }
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < XB_R; r++) {
-            double b = best[r];
-            int i1 = bi[r];
-            for (int off = 32; off >= 1; off >>= 1) {
-                const double ob = __shfl_xor(b, off);
-                const int oi = __shfl_xor(i1, off);
-                const bool take = oi >= 0 && (i1 < 0 || ob < b || (ob == b && oi < i1));
-                if (take) { b = ob; i1 = oi; }
-            }
-            if (lane == 0 && r < nr) {
-                assign[myrow[r]] = i1;
-                dist[myrow[r]] = b;
-            }
-        }
-        wave_sync();
-    }
-}
-
-// ------------------------------------------------------- pruned exact pass
-// Listed rows, euclidean, K <= 256 (the persistent fused form's lists): a wave
-// takes XB_R rows; phase 1 scores every centroid in f32 (an FMA chain over a
-// transposed f32 copy CT32[j][c], loaded once per XB_R rows) with the bound e_c
-// of the f32 path above; the candidates are the centroids with
-// s~_c - e_c <= min (s~ + e) -- every other centroid's reference distance is
-// provably larger than some candidate's -- and phase 2 evaluates only those in
-// the reference's exact order (one lane each), keeping the first minimum.
-// A row whose f32 scores are not all finite, or with more than 64 candidates,
-// evaluates every centroid exactly instead.
-#ifndef XP_ROWS
-#define XP_ROWS 8
-#endif
-#ifndef XP_SPLITS
-#define XP_SPLITS 4
-#endif
-constexpr int XP_R = XP_ROWS;
-#ifndef XP_WIDE_ROWS
-#define XP_WIDE_ROWS 2      // rows per wave at 256 < K <= 1024 (16 chunks of 64 centroids)
-#endif
-constexpr int XP_WR = XP_WIDE_ROWS;
-constexpr int XP_WAVES = 4;
-constexpr int XP_SPLIT = XP_SPLITS;
-
-// The reference's distance of one (row, centroid) pair on the pruned pass:
-// euclidean in exact order; cosine by the soft-x87 chain (16-B loads when the
-// row length allows).
-template <int MET, typename TX>
-__device__ inline double pruned_dist(const TX* __restrict__ x, const double* __restrict__ c, int d) {
-    if constexpr (MET == 0) {
-        return exact_euclid_rolled(x, c, d);
-    } else {
-        if constexpr (sizeof(TX) == 4) {
-            if ((d & 15) == 0) return exact_cosine_x87_b16(x, c, d);
-        }
-        return exact_cosine_x87(x, c, d);
-    }
-}
-
-__global__ void exact_prep_kernel(const double* __restrict__ C, int K, int Kpad, int d, int xf64,
-                                  float* __restrict__ CT32, float* __restrict__ cconst, int metric) {
-    // one wave per centroid: CT32 [d][Kpad], cconst = cn2[Kpad] ++ {ec, eb}[Kpad/64]
-    // (chunk maxima by atomicMax on the bits of positive floats; zeroed first).
-    // cosine: CT32 holds the normalised row (score -x.c^), cconst 0, or +inf for
-    // a zero / extreme-norm centroid (rows then evaluate every centroid exactly)
-    const int c = blockIdx.x, lane = threadIdx.x;
-    double scale = 1.0;
-    if (metric == 1) {
-        double q = 0.0;
-        for (int j = lane; j < d; j += 64) {
-            const double v = c < K ? C[(size_t)c * d + j] : 0.0;
-            q = fma(v, v, q);
-        }
-        for (int off = 32; off >= 1; off >>= 1) q += __shfl_xor(q, off);
-        scale = (q >= 1e-200 && q <= 1e200) ? 1.0 / sqrt(q) : 0.0;
-        if (c < K && scale == 0.0) {
-            for (int j = lane; j < d; j += 64) CT32[(size_t)j * Kpad + c] = 0.f;
-            if (lane == 0) cconst[c] = __builtin_inff();
-            return;
-        }
-    }
-    double sq = 0.0;
-    for (int j = lane; j < d; j += 64) {
-        const double v = c < K ? C[(size_t)c * d + j] * scale : 0.0;
-        sq = fma(v, v, sq);
-        CT32[(size_t)j * Kpad + c] = (float)v;
-    }
-    for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off);
-    if (lane != 0) return;
-    if (c >= K) { cconst[c] = __builtin_inff(); return; }
-    if (metric == 1) {
-        // |s~ - x.c^| <= (d + 2) 2^-24 |x| (f32 FMA chain, c^'s f32 rounding), and
-        // the reference's q = x.c / (|x||c|) sits within 2^-40 |x| of x.c^ / |x| . |x|
-        cconst[c] = 0.f;
-        const double ec = ((d + 2.0) * 0x1p-24 * (1.0 + 0x1p-10) + 0x1p-40 + (xf64 ? 0x1p-23 : 0.0)) * (1.0 + 0x1p-18);
-        unsigned int* chunk = reinterpret_cast<unsigned int*>(cconst + Kpad + 2 * (c / 64));
-        atomicMax(chunk, __float_as_uint((float)(ec * (1.0 + 0x1p-20))));
-        atomicMax(chunk + 1, __float_as_uint(1e-30f));
-        return;
-    }
-    const double up = 1.0 + 0x1p-18;
-    const double nc = sqrt(sq) * (1.0 + 0x1p-30);
-    cconst[c] = (float)sq;
-    // fp64 rows are scored from their f32 roundings (as centroid_prep_kernel)
-    const double ec = 0x1p-24 * (2.0 * d + 12.0 + (xf64 ? 2.0 : 0.0)) * nc * up;
-    const double eb = (0x1p-24 * 5.0 * sq + 0x1p-40 * sq + (xf64 ? 0x1p-140 * nc : 0.0)) * up + 1e-30;
-    unsigned int* chunk = reinterpret_cast<unsigned int*>(cconst + Kpad + 2 * (c / 64));
-    atomicMax(chunk, __float_as_uint((float)(ec * (1.0 + 0x1p-20))));
-    atomicMax(chunk + 1, __float_as_uint((float)(eb * (1.0 + 0x1p-20))));
-}
-
-// NCH = Kpad / 64 centroid chunks scored per lane (K <= 64 NCH), R rows per wave.
-template <typename TX, int NCH = 4, int R = XP_R, int MET = 0>
-__global__ __launch_bounds__(64 * XP_WAVES) void assign_pruned_kernel(
-    const TX* __restrict__ X, int d, const double* __restrict__ C, const float* __restrict__ CT32,
-    const float* __restrict__ cconst, int K, int Kpad, const int32_t* __restrict__ rows,
-    const unsigned long long* __restrict__ row_count, int64_t max_rows, int32_t* __restrict__ assign,
-    double* __restrict__ dist, const int32_t* __restrict__ seg_counts, int64_t seg_rows, int exact_dist) {
-    constexpr int RL = 64 / R;           // lanes per row in the candidate phase
-    __shared__ TX xs[XP_WAVES][R][XB_DMAX];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t total, g0, gstride;
-    if (seg_counts) {
-        const int nseg = gridDim.x / XP_SPLIT;   // segments across XCDs (cos_fix_seg_kernel)
-        const int seg = blockIdx.x % nseg, part = blockIdx.x / nseg;
-        rows += (int64_t)seg * seg_rows;
-        total = seg_counts[SEG_SLOTS * seg + SEG_ROWS];
-        g0 = (int64_t)part * XP_WAVES + wave;
-        gstride = (int64_t)XP_SPLIT * XP_WAVES;
-    } else {
-        total = (int64_t)*row_count;
-        if (total > max_rows) total = max_rows;
-        g0 = (int64_t)blockIdx.x * XP_WAVES + wave;
-        gstride = (int64_t)gridDim.x * XP_WAVES;
-    }
-    const float* chunkc = cconst + Kpad;
-    const int64_t ngroups = (total + R - 1) / R;
-    for (int64_t g = g0; g < ngroups; g += gstride) {
-        const int nr = (int)min((int64_t)R, total - g * R);
-        int32_t myrow[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) myrow[r] = rows[g * R + min(r, nr - 1)];   // pad with the last row
-        // every row value of the group in flight at once (d <= XB_DMAX: at most
-        // XB_DMAX / 64 per lane and row), then staged in LDS
-        float xn2p[R];
-        TX xv[R][XB_DMAX / 64];
-#pragma unroll
-        for (int r = 0; r < R; r++)
-#pragma unroll
-            for (int u = 0; u < XB_DMAX / 64; u++) {
-                const int j = lane + 64 * u;
-                xv[r][u] = j < d ? X[(int64_t)myrow[r] * d + j] : TX(0);
-            }
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            float q = 0.f;
-#pragma unroll
-            for (int u = 0; u < XB_DMAX / 64; u++) {
-                const int j = lane + 64 * u;
-                if (j < d) {
-                    xs[wave][r][j] = xv[r][u];
-                    q = fmaf((float)xv[r][u], (float)xv[r][u], q);
-                }
-            }
-            xn2p[r] = q;
-        }
-        wave_sync();
-        // phase 1: f32 scores of centroids c = lane + 64 i
-        float acc[R][NCH];
-#pragma unroll
-        for (int r = 0; r < R; r++)
-#pragma unroll
-            for (int i = 0; i < NCH; i++) acc[r][i] = 0.f;
-        // chunks past Kpad read chunk 0 (their scores are never used): the loads
-        // carry no branch, so the unrolled iterations' loads issue together
-        int coff[NCH];
-#pragma unroll
-        for (int i = 0; i < NCH; i++) coff[i] = (64 * i < Kpad ? 64 * i : 0) + lane;
-#pragma unroll 8
-        for (int j = 0; j < d; j++) {
-            float cv[NCH];
-#pragma unroll
-            for (int i = 0; i < NCH; i++) cv[i] = CT32[(size_t)j * Kpad + coff[i]];
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const float xj = (float)xs[wave][r][j];
-#pragma unroll
-                for (int i = 0; i < NCH; i++) acc[r][i] = fmaf(xj, cv[i], acc[r][i]);
-            }
-        }
-        // per row: bound, U = min (s~ + e), candidate masks (wave-uniform)
-        unsigned long long cm[R][NCH];
-        int ncand[R];
-        bool pr[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            // |x|^2 in fp64 over the lanes' f32 partials, rounded up (as the f32 path)
-            double xn2 = (double)xn2p[r];
-            for (int off = 32; off >= 1; off >>= 1) xn2 += __shfl_xor(xn2, off);
-            xn2 = xn2 * (sizeof(TX) == 4 ? 1.0 + 0x1p-20 : 1.0 + 0x1p-19) + (sizeof(TX) == 4 ? 0.0 : 0x1p-280);
-            const float nx = (float)(sqrt(xn2) * (1.0 + 0x1p-30));
-            const float ex = (float)(0x1p-40 * xn2 * (1.0 + 0x1p-18) + 1e-30);
-            float lo[NCH];
-            float U = __builtin_inff();
-            bool finite = nx <= 3.0e38f;
-#pragma unroll
-            for (int i = 0; i < NCH; i++) {
-                const int c = lane + 64 * i;
-                lo[i] = __builtin_inff();
-                if (c < K) {
-                    const float E = fmaf(nx, chunkc[2 * i], chunkc[2 * i + 1] + ex);
-                    const float sc = MET == 1 ? cconst[c] - acc[r][i] : fmaf(-2.f, acc[r][i], cconst[c]);
-                    lo[i] = sc - E;
-                    const float hi = sc + E;
-                    finite = finite && (hi - lo[i]) <= 3.0e38f;   // false for inf / nan
-                    U = fminf(U, hi);
-                }
-            }
-            for (int off = 32; off >= 1; off >>= 1) U = fminf(U, __shfl_xor(U, off));
-            ncand[r] = 0;
-#pragma unroll
-            for (int i = 0; i < NCH; i++) {
-                cm[r][i] = __ballot(lo[i] <= U);
-                ncand[r] += __popcll(cm[r][i]);
-            }
-            pr[r] = r < nr && __all(finite) && ncand[r] >= 1;
-        }
-        // rows with <= RL candidates: lane RL r + k evaluates row r's k-th candidate
-        {
-            const int r = lane / RL, k = lane % RL;
-            int c = -1;
-            int seen = 0;
-#pragma unroll
-            for (int rr = 0; rr < R; rr++) {
-                if (rr != r || !pr[rr] || ncand[rr] > RL) continue;
-#pragma unroll
-                for (int i = 0; i < NCH; i++) {
-                    const int n = __popcll(cm[rr][i]);
-                    if (c < 0 && k >= seen && k < seen + n) {
-                        unsigned long long m = cm[rr][i];
-                        for (int t = k - seen; t > 0; t--) m &= m - 1;
-                        c = 64 * i + __builtin_ctzll(m);
-                    }
-                    seen += n;
-                }
-            }
-            double best = 0.0;
-            int bi = -1;
-            if constexpr (MET == 0) {
-                pruned_pick_euclid<RL>(xs[wave][r], C, d, c, exact_dist != 0, best, bi);   // within the row's lanes
-            } else {
-                if (c >= 0) {
-                    best = pruned_dist<MET>(xs[wave][r], C + (size_t)c * d, d);
-                    bi = c;
-                }
-                group_argmin<RL>(best, bi);
-            }
-            if (k == 0 && bi >= 0) {
-                assign[myrow[r]] = bi;
-                dist[myrow[r]] = best;
-            }
-        }
-        // the other rows, one at a time with the whole wave
-        for (int r = 0; r < nr; r++) {
-            if (pr[r] && ncand[r] <= RL) continue;
-            const bool prune = pr[r] && ncand[r] <= 64;
-            const TX* xr = xs[wave][r];
-            double best = 0.0;
-            int bi = -1;
-            if (prune) {
-                // lane k takes the k-th candidate (increasing c)
-                int c = -1, seen = 0;
-#pragma unroll
-                for (int i = 0; i < NCH; i++) {
-                    const int n = __popcll(cm[r][i]);
-                    if (c < 0 && lane >= seen && lane < seen + n) {
-                        unsigned long long m = cm[r][i];
-                        for (int t = lane - seen; t > 0; t--) m &= m - 1;
-                        c = 64 * i + __builtin_ctzll(m);
-                    }
-                    seen += n;
-                }
-                if constexpr (MET == 0) {
-                    pruned_pick_euclid<64>(xr, C, d, c, exact_dist != 0, best, bi);
-                } else if (c >= 0) {
-                    best = pruned_dist<MET>(xr, C + (size_t)c * d, d);
-                    bi = c;
-                }
-            } else {
-                for (int c = lane; c < K; c += 64) {
-                    const double dd = pruned_dist<MET>(xr, C + (size_t)c * d, d);
-                    // assignment.hpp:66: the -1 sentinel takes centroid 0's distance
-                    // even if NaN, which then blocks every later '<'
-                    if (bi < 0 ? (dd == dd || c == 0) : dd < best) { best = dd; bi = c; }
-                }
-            }
-            for (int off = 32; off >= 1; off >>= 1) {
-                const double ob = __shfl_xor(best, off);
-                const int oi = __shfl_xor(bi, off);
-                const bool take = oi >= 0 && (bi < 0 || ob < best || (ob == best && oi < bi));
-                if (take) { best = ob; bi = oi; }
-            }
-            if (lane == 0) {
-                assign[myrow[r]] = bi < 0 ? 0 : bi;
-                dist[myrow[r]] = bi < 0 ? -1.0 : best;
-            }
-        }
-        wave_sync();
-    }
-}
-
-// 256 < K <= 1024: XPW_R rows per wave -- the centroid columns stream from L2
-// once per XPW_R rows (at 2 rows per wave the C5 pass read ~36 GB of L2 for
-// 140K listed rows) -- and the candidates of each row selected and evaluated in
-// turn by the whole wave (per-row masks only: no [rows][chunks] mask array).
-#ifndef XPW_ROWS
-#define XPW_ROWS 4       // C5 whole call: 2 rows per wave (segmented) 5.46-5.51 ms; flat 2 / 4 / 8: 4.97 / 4.82-4.91 / 4.95-5.08
-#endif
-constexpr int XPW_MAXSEG = 4096;
-template <typename TX, int MET = 0, int NCH = 16, int R = XPW_ROWS>
-__global__ __launch_bounds__(64 * XP_WAVES) void assign_pruned_wide_kernel(
-    const TX* __restrict__ X, int d, const double* __restrict__ C, const float* __restrict__ CT32,
-    const float* __restrict__ cconst, int K, int Kpad, const int32_t* __restrict__ rows,
-    const unsigned long long* __restrict__ row_count, int64_t max_rows, int32_t* __restrict__ assign,
-    double* __restrict__ dist, const int32_t* __restrict__ seg_counts, int64_t seg_rows, int nseg, int exact_dist) {
-    __shared__ TX xs[XP_WAVES][R][XB_DMAX];
-    __shared__ int gpre[XPW_MAXSEG + 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // segmented lists (one per fused block): the groups of every segment in one
-    // flat index space, so the waves share the work whatever the segments' sizes
-    // (per-segment waves left the pass waiting on the fullest segments)
-    int64_t ngroups;
-    if (seg_counts) {
-        for (int sg = threadIdx.x; sg < nseg; sg += 64 * XP_WAVES) gpre[sg + 1] = (seg_counts[SEG_SLOTS * sg + SEG_ROWS] + R - 1) / R;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            gpre[0] = 0;
-            for (int sg = 0; sg < nseg; sg++) gpre[sg + 1] += gpre[sg];
-        }
-        __syncthreads();
-        ngroups = gpre[nseg];
-    } else {
-        int64_t total = (int64_t)*row_count;
-        if (total > max_rows) total = max_rows;
-        ngroups = (total + R - 1) / R;
-    }
-    const float* chunkc = cconst + Kpad;
-    const int64_t g0 = (int64_t)blockIdx.x * XP_WAVES + wave, gstride = (int64_t)gridDim.x * XP_WAVES;
-    for (int64_t g = g0; g < ngroups; g += gstride) {
-        const int32_t* grows;
-        int64_t gbase, cnt;
-        if (seg_counts) {
-            int lo = 0, hi = nseg;                  // gpre[lo] <= g < gpre[hi]
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (gpre[mid] <= g) lo = mid; else hi = mid;
-            }
-            grows = rows + (int64_t)lo * seg_rows;
-            gbase = (g - gpre[lo]) * R;
-            cnt = seg_counts[SEG_SLOTS * lo + SEG_ROWS];
-        } else {
-            grows = rows;
-            gbase = g * R;
-            cnt = min((int64_t)*row_count, max_rows);
-        }
-        const int nr = (int)min((int64_t)R, cnt - gbase);
-        int32_t myrow[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) myrow[r] = grows[gbase + min(r, nr - 1)];   // pad with the last row
-        float xn2p[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            TX xv[XB_DMAX / 64];
-#pragma unroll
-            for (int u = 0; u < XB_DMAX / 64; u++) {
-                const int j = lane + 64 * u;
-                xv[u] = j < d ? X[(int64_t)myrow[r] * d + j] : TX(0);
-            }
-            float q = 0.f;
-#pragma unroll
-            for (int u = 0; u < XB_DMAX / 64; u++) {
-                const int j = lane + 64 * u;
-                if (j < d) {
-                    xs[wave][r][j] = xv[u];
-                    q = fmaf((float)xv[u], (float)xv[u], q);
-                }
-            }
-            xn2p[r] = q;
-        }
-        wave_sync();
-        float acc[R][NCH];
-#pragma unroll
-        for (int r = 0; r < R; r++)
-#pragma unroll
-            for (int i = 0; i < NCH; i++) acc[r][i] = 0.f;
-        int coff[NCH];
-#pragma unroll
-        for (int i = 0; i < NCH; i++) coff[i] = (64 * i < Kpad ? 64 * i : 0) + lane;
-#pragma unroll 2
-        for (int j = 0; j < d; j++) {
-            float cv[NCH];
-#pragma unroll
-            for (int i = 0; i < NCH; i++) cv[i] = CT32[(size_t)j * Kpad + coff[i]];
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const float xj = (float)xs[wave][r][j];
-#pragma unroll
-                for (int i = 0; i < NCH; i++) acc[r][i] = fmaf(xj, cv[i], acc[r][i]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            if (r >= nr) break;                     // wave-uniform
-            double xn2 = (double)xn2p[r];
-            for (int off = 32; off >= 1; off >>= 1) xn2 += __shfl_xor(xn2, off);
-            xn2 = xn2 * (sizeof(TX) == 4 ? 1.0 + 0x1p-20 : 1.0 + 0x1p-19) + (sizeof(TX) == 4 ? 0.0 : 0x1p-280);
-            const float nx = (float)(sqrt(xn2) * (1.0 + 0x1p-30));
-            const float ex = (float)(0x1p-40 * xn2 * (1.0 + 0x1p-18) + 1e-30);
-            float lo[NCH];
-            float U = __builtin_inff();
-            bool finite = nx <= 3.0e38f;
-#pragma unroll
-            for (int i = 0; i < NCH; i++) {
-                const int c = lane + 64 * i;
-                lo[i] = __builtin_inff();
-                if (c < K) {
-                    const float E = fmaf(nx, chunkc[2 * i], chunkc[2 * i + 1] + ex);
-                    const float sc = MET == 1 ? cconst[c] - acc[r][i] : fmaf(-2.f, acc[r][i], cconst[c]);
-                    lo[i] = sc - E;
-                    const float hi = sc + E;
-                    finite = finite && (hi - lo[i]) <= 3.0e38f;   // false for inf / nan
-                    U = fminf(U, hi);
-                }
-            }
-            for (int off = 32; off >= 1; off >>= 1) U = fminf(U, __shfl_xor(U, off));
-            unsigned long long cm[NCH];
-            int ncand = 0;
-#pragma unroll
-            for (int i = 0; i < NCH; i++) {
-                cm[i] = __ballot(lo[i] <= U);
-                ncand += __popcll(cm[i]);
-            }
-            const bool prune = __all(finite) && ncand >= 1 && ncand <= 64;
-            const TX* xr = xs[wave][r];
-            double best = 0.0;
-            int bi = -1;
-            if (prune) {
-                // lane k takes the k-th candidate (increasing c)
-                int c = -1, seen = 0;
-#pragma unroll
-                for (int i = 0; i < NCH; i++) {
-                    const int n = __popcll(cm[i]);
-                    if (c < 0 && lane >= seen && lane < seen + n) {
-                        unsigned long long m = cm[i];
-                        for (int t = lane - seen; t > 0; t--) m &= m - 1;
-                        c = 64 * i + __builtin_ctzll(m);
-                    }
-                    seen += n;
-                }
-                if constexpr (MET == 0) {
-                    pruned_pick_euclid<64>(xr, C, d, c, exact_dist != 0, best, bi);
-                } else if (c >= 0) {
-                    best = pruned_dist<MET>(xr, C + (size_t)c * d, d);
-                    bi = c;
-                }
-            } else {
-                for (int c = lane; c < K; c += 64) {
-                    const double dd = pruned_dist<MET>(xr, C + (size_t)c * d, d);
-                    // assignment.hpp:66: the -1 sentinel takes centroid 0's distance
-                    // even if NaN, which then blocks every later '<'
-                    if (bi < 0 ? (dd == dd || c == 0) : dd < best) { best = dd; bi = c; }
-                }
-            }
-            for (int off = 32; off >= 1; off >>= 1) {
-                const double ob = __shfl_xor(best, off);
-                const int oi = __shfl_xor(bi, off);
-                const bool take = oi >= 0 && (bi < 0 || ob < best || (ob == best && oi < bi));
-                if (take) { best = ob; bi = oi; }
-            }
-            if (lane == 0) {
-                assign[myrow[r]] = bi < 0 ? 0 : bi;
-                dist[myrow[r]] = bi < 0 ? -1.0 : best;
-            }
-        }
-        wave_sync();
-    }
-}
-
-int launch_assign_pruned_prep(hipStream_t s, bool xf64, int d, const double* C, int K, float* ws, int metric) {
-    if (d > XB_DMAX || K > 1024) {
-        set_error("launch_assign_pruned_prep: unsupported shape");
-        return -1;
-    }
-    const int Kpad = (K + 63) / 64 * 64;
-    float* cconst = ws + (size_t)d * Kpad;
-    if (hipMemsetAsync(cconst + Kpad, 0, (size_t)(Kpad / 64) * 2 * 4, s) != hipSuccess) return kstatus("pruned prep");
-    hipLaunchKernelGGL(exact_prep_kernel, dim3((unsigned)Kpad), dim3(64), 0, s, C, K, Kpad, d, xf64 ? 1 : 0, ws, cconst,
-                       metric);
-    return kstatus("exact_prep_kernel");
-}
-
-int launch_assign_pruned_list(hipStream_t s, const AssignJob& q, float* ws, const RowList& l, int exact_dist,
-                              bool prepped) {
-    const Pts X = q.X;
-    const int64_t max_rows = l.bound, seg_rows = l.seg_rows;
-    const int d = q.d, K = q.K, nseg = l.nseg, metric = q.metric == 0 ? 0 : 1;   // 1: cosine
-    const double* C = q.C;
-    const int32_t *rows = l.p, *seg_counts = l.seg_counts();
-    const unsigned long long* row_count = l.count;
-    int32_t* assign = q.assign;
-    double* dist = q.dist;
-    if (max_rows <= 0) return 0;
-    if (d > XB_DMAX || K > 1024 || (seg_counts && nseg <= 0)) {
-        set_error("launch_assign_pruned_list: unsupported shape");
-        return -1;
-    }
-    const int Kpad = (K + 63) / 64 * 64;
-    float* CT32 = ws;
-    float* cconst = ws + (size_t)d * Kpad;
-    if (!prepped) {
-        int rc = launch_assign_pruned_prep(s, X.f64, d, C, K, ws, metric);
-        if (rc) return rc;
-    }
-    // K <= 256: 8 rows per wave over 4 chunks; K <= 1024: 2 rows per wave over 16
-    const bool wide = Kpad > 256;
-    const bool flat = wide && (!seg_counts || nseg <= XPW_MAXSEG);
-    const int R = wide ? (flat ? XPW_ROWS : XP_WR) : XP_R;     // groups of R rows
-    const int64_t groups = (max_rows + R - 1) / R;
-    const int64_t blocks = seg_counts ? (int64_t)nseg * XP_SPLIT : std::min<int64_t>((groups + XP_WAVES - 1) / XP_WAVES, 2048);
-#define XP_LAUNCH(TX, NCH, RR, MT, XP)                                                                              \
-    hipLaunchKernelGGL((assign_pruned_kernel<TX, NCH, RR, MT>), dim3((unsigned)blocks), dim3(64 * XP_WAVES), 0, s, XP, \
-                       d, C, CT32, cconst, K, Kpad, rows, row_count, max_rows, assign, dist, seg_counts, seg_rows, exact_dist)
-#define XPW_LAUNCH(TX, MT, NC, RW, XP)                                                                           \
-    hipLaunchKernelGGL((assign_pruned_wide_kernel<TX, MT, NC, RW>), dim3((unsigned)wblocks), dim3(64 * XP_WAVES), 0, s, \
-                       XP, d, C, CT32, cconst, K, Kpad, rows, row_count, max_rows, assign, dist, seg_counts, seg_rows, nseg, \
-                       exact_dist)
-    const int64_t wblocks = std::min<int64_t>((groups + XP_WAVES - 1) / XP_WAVES, 1024);
-    if (flat) {
-        if (metric == 1) {
-            if (X.f64) XPW_LAUNCH(double, 1, 16, XPW_ROWS, X.d()); else XPW_LAUNCH(float, 1, 16, XPW_ROWS, X.f());
-        } else {
-            if (X.f64) XPW_LAUNCH(double, 0, 16, XPW_ROWS, X.d()); else XPW_LAUNCH(float, 0, 16, XPW_ROWS, X.f());
-        }
-    } else if (metric == 1) {
-        if (X.f64) {
-            if (wide) XP_LAUNCH(double, 16, XP_WR, 1, X.d()); else XP_LAUNCH(double, 4, XP_R, 1, X.d());
-        } else {
-            if (wide) XP_LAUNCH(float, 16, XP_WR, 1, X.f()); else XP_LAUNCH(float, 4, XP_R, 1, X.f());
-        }
-    } else if (X.f64) {
-        if (wide) XP_LAUNCH(double, 16, XP_WR, 0, X.d()); else XP_LAUNCH(double, 4, XP_R, 0, X.d());
-    } else {
-        if (wide) XP_LAUNCH(float, 16, XP_WR, 0, X.f()); else XP_LAUNCH(float, 4, XP_R, 0, X.f());
-    }
-#undef XP_LAUNCH
-#undef XPW_LAUNCH
-    return kstatus("assign_pruned_kernel");
-}
-
-int launch_assign_exact_list(hipStream_t s, const AssignJob& q, double* CT, const RowList& l) {
-    const Pts X = q.X;
-    const int64_t max_rows = l.bound, seg_rows = l.seg_rows;
-    const int d = q.d, K = q.K, nseg = l.nseg;
-    const double* C = q.C;
-    const int32_t *rows = l.p, *seg_counts = l.seg_counts();
-    const unsigned long long* row_count = l.count;
-    int32_t* assign = q.assign;
-    double* dist = q.dist;
-    if (max_rows <= 0) return 0;
-    if (d > XB_DMAX || (seg_counts && nseg <= 0)) {
-        set_error("launch_assign_exact_list: unsupported shape");
-        return -1;
-    }
-    const int Kpad = (K + 255) / 256 * 256;     // CT row stride: whole 256-centroid passes, no bounds checks
-    const int64_t ne = (int64_t)d * Kpad;
-    hipLaunchKernelGGL(transpose_centroids_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, C, K, Kpad, d, CT);
-    const int64_t groups = (max_rows + XB_R - 1) / XB_R;
-    const int64_t blocks = seg_counts ? (int64_t)nseg * XB_SPLIT : std::min<int64_t>((groups + XB_WAVES - 1) / XB_WAVES, 2048);
-    if (X.f64)
-        hipLaunchKernelGGL(assign_exact_batch_kernel<double>, dim3((unsigned)blocks), dim3(64 * XB_WAVES), 0, s, X.d(),
-                           d, CT, K, Kpad, rows, row_count, max_rows, assign, dist, seg_counts, seg_rows);
-    else
-        hipLaunchKernelGGL(assign_exact_batch_kernel<float>, dim3((unsigned)blocks), dim3(64 * XB_WAVES), 0, s, X.f(),
-                           d, CT, K, Kpad, rows, row_count, max_rows, assign, dist, seg_counts, seg_rows);
-    return kstatus("assign_exact_batch_kernel");
 }
 
 // Centroid override (assignment.hpp:77-78): in c order, so the last centroid

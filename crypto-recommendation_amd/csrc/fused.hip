@@ -270,7 +270,7 @@ int fused_assign(lshkm_ctx ctx, const AssignRequest& q) {
     if ((rc = launch_fused_prep(s, q.C, q.K, q.d, cosine ? 1 : 0, w))) return rc;
     // the listed pass's centroid prep ahead of the passes: it then starts as
     // soon as the refinement ends
-    const bool xprep = exact_pruned(q.X, q.d, q.K, q.metric);
+    const bool xprep = exact_is_pruned(exact_form(q));
     if (xprep && (rc = exact_listed_prep(ctx, q))) return rc;
     if (w.xn2 && (rc = launch_row_sumsq(s, q.X.d(), q.N, q.d, w.xn2))) return rc;
 

@@ -56,12 +56,12 @@ int cube_vertices(lshkm_cube_s* cube, Pts X, int64_t N, int32_t* vertex);
 int hash_rows(lshkm_ctx_s* ctx, int mode, Pts X, int64_t N, const ProjTable& pj, int64_t nb, int32_t* out_h,
               int32_t* out_phi, int32_t* out_bucket, int32_t* mm, bool* h16 = nullptr);
 // The listed rows' exact pass (api.cpp): reference-order distances over the
-// rows of l, pruned to the candidates an f32 bound leaves where that applies.
+// rows of l, in the form exact_form gives the job (exact_route, exact_layout.h).
 // exact_listed_prep: its centroid-only part, ahead of the pass that fills l;
 // then prepped. exact_dist: false = a winner distance may come from the x*x
 // chain (LSHKM_DIST_CERTIFIED). xn2 / nbv: cosine, the rows' / centroids' sums
 // of squares where the caller has them (else NULL).
-bool exact_pruned(Pts X, int d, int K, int metric);
+ExactForm exact_form(const AssignJob& q);
 int exact_listed_prep(lshkm_ctx_s* ctx, const AssignJob& q);
 int exact_listed(lshkm_ctx_s* ctx, const AssignJob& q, const RowList& l, bool exact_dist, bool prepped,
                  const double* xn2, const double* nbv);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "exact_layout.h"
 #include "fused_layout.h"
 #include "recom_layout.h"
 
@@ -126,23 +127,17 @@ int launch_assign_mfma(hipStream_t s, Pts X, int64_t N, int d, int DP, const dou
 // rows[0..*count), written by assign_mfma_kernel<., 1>): soft-x87 distances.
 int launch_cos_fix(hipStream_t s, Pts X, int64_t N, int d, const double* C, const int32_t* rows,
                    const unsigned long long* count, const int32_t* assign, double* dist);
-// Every centroid in the reference's order, over the rows of l (cosine: xn2 /
-// nbv, the rows' and centroids' sums of squares, where the caller has them).
-int launch_assign_exact(hipStream_t s, const AssignJob& q, const RowList& l, const double* xn2 = nullptr,
-                        const double* nbv = nullptr);
-// Euclidean, listed rows, batched (CT: d * ceil64(K) doubles of workspace).
-int launch_assign_exact_list(hipStream_t s, const AssignJob& q, double* CT, const RowList& l);
-// Listed rows, K <= 1024: f32 candidate pruning, then exact order on
-// the candidates only (ws: d * ceil64(K) + ceil64(K) + ceil64(K)/32 floats).
-// exact_dist = 0 (LSHKM_DIST_CERTIFIED): a winner distance may come from the
-// x*x chain (<= 2^-44 relative); cluster IDs are the reference's either way.
-// prepped: launch_assign_pruned_prep ran for these centroids on this stream.
-int launch_assign_pruned_list(hipStream_t s, const AssignJob& q, float* ws, const RowList& l, int exact_dist,
-                              bool prepped);
-// The centroid-only part of the pruned pass (f32 transposed centroids, |c|^2,
-// the chunk bounds into ws): launched before the fused pass, off its tail;
-// then launch_assign_pruned_list(..., prepped = true).
-int launch_assign_pruned_prep(hipStream_t s, bool xf64, int d, const double* C, int K, float* ws, int metric);
+// The exact pass (exact_pass.hip) over the rows of l in the given form
+// (exact_route, exact_layout.h); ws: exact_ws_bytes(form, d, K) bytes that
+// launch_exact_prep filled for these centroids on this stream (the form's
+// centroid-only part: it may run ahead of the pass that fills l).
+// exact_dist false (LSHKM_DIST_CERTIFIED; the pruned forms, euclidean): a winner
+// distance may come from the x*x chain (<= 2^-44 relative); cluster IDs are the
+// reference's either way. xn2 / nbv (every, cosine): the rows' and centroids'
+// sums of squares, where the caller has them.
+int launch_exact_prep(hipStream_t s, const AssignJob& q, ExactForm form, void* ws);
+int launch_exact_pass(hipStream_t s, const AssignJob& q, const RowList& l, ExactForm form, const void* ws,
+                      bool exact_dist, const double* xn2, const double* nbv);
 int launch_assign_override(hipStream_t s, const int32_t* src_rows, int K, int64_t N, int32_t* assign,
                            double* dist);
 

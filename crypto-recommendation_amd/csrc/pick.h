@@ -1,6 +1,6 @@
 // pick.h -- the listed passes' euclidean pick among a few candidates in the
 // reference's exact order: the chains, the group reductions and
-// pruned_pick_euclid (the pruned exact pass of assign.hip, and the fused
+// pruned_pick_euclid (the pruned exact pass of exact_pass.hip, and the fused
 // refinement's pair rows, fused_refine.hip).
 #pragma once
 #include "exact.h"
