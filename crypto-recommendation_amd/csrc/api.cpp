@@ -16,6 +16,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "index.h"
+#include "kpp_layout.h"
 
 namespace lshkm {
 static thread_local std::string g_err;
@@ -317,7 +318,7 @@ static int kmeans_pp_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, int K, int met
     chosen[0] = (int32_t)first;
     Buf &ws = ctx->ws_call[0], &dch = ctx->ws_call[1], &dcanon = ctx->ws_call[2];
     int rc;
-    if ((rc = ws.reserve(kmeans_pp_ws_bytes(N))) || (rc = dch.reserve(sizeof(int32_t) * K)) ||
+    if ((rc = ws.reserve(kpp_layout(N).bytes)) || (rc = dch.reserve(sizeof(int32_t) * K)) ||
         (rc = dcanon.reserve(sizeof(double) * K)))
         return rc;
     LSHKM_HIP(hipMemcpyAsync(dch.p, chosen.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, ctx->stream));
@@ -348,23 +349,21 @@ int lshkm_kmeans_pp_f64(lshkm_ctx ctx, const double* X, int64_t N, int d, int K,
 
 // k_means_pp over row shards (lshkm_kpp_shard_*): one step of one iteration on
 // this rank's n rows; an empty shard touches no memory. `out` is what the step
-// leaves for the host behind the workspace's max word (kernels.h).
-struct KppShardHost {
-    uint64_t max_bits;
-    double sum, s_out;
-    int64_t pick;
-};
-
+// leaves for the host behind the workspace's max word (kpp_layout.h).
 static int kpp_shard_ws_check(lshkm_ctx ctx, int64_t n, const void* ws, int64_t ws_bytes) {
     LSHKM_CHECK(ctx && n >= 0 && n <= INT32_MAX, LSHKM_ERR_ARG, "bad arguments (need 0 <= n < 2^31)");
-    LSHKM_CHECK(n == 0 || (ws && ws_bytes >= 0 && (size_t)ws_bytes >= kmeans_pp_ws_bytes(n)), LSHKM_ERR_ARG,
+    LSHKM_CHECK(n == 0 || (ws && ws_bytes >= 0 && (size_t)ws_bytes >= kpp_layout(n).bytes), LSHKM_ERR_ARG,
                 "workspace smaller than lshkm_kpp_shard_ws_bytes");
     LSHKM_HIP(hipSetDevice(ctx->device));
     return 0;
 }
 
-static int kpp_shard_read(lshkm_ctx ctx, int64_t n, const void* ws, KppShardHost* out) {
-    LSHKM_HIP(hipMemcpyAsync(out, (const char*)ws + kpp_shard_out_offset(n), sizeof(*out), hipMemcpyDeviceToHost,
+static int kpp_shard_read(lshkm_ctx ctx, int64_t n, const void* ws, int launch_rc, KppShardOut* out) {
+    if (launch_rc) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return launch_rc;
+    }
+    LSHKM_HIP(hipMemcpyAsync(out, (const char*)ws + kpp_layout(n).out, sizeof(*out), hipMemcpyDeviceToHost,
                              ctx->stream));
     LSHKM_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -380,12 +379,9 @@ static int kpp_shard_dist_impl(lshkm_ctx ctx, Pts X, int64_t n, int d, int metri
     *sum = 0.0;
     if (n == 0) return 0;
     LSHKM_CHECK(X.p && c, LSHKM_ERR_ARG, "rows or centroid row is NULL");
-    KppShardHost o;
-    int rc;
-    if ((rc = launch_kpp_shard_dist(ctx->stream, X, n, d, metric, c, it, ws)) || (rc = kpp_shard_read(ctx, n, ws, &o))) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
+    KppShardOut o;
+    const int lrc = launch_kpp_shard_dist(ctx->stream, X, n, d, metric, c, it, ws);
+    if (const int rc = kpp_shard_read(ctx, n, ws, lrc, &o)) return rc;
     *max_bits = o.max_bits;
     *sum = o.sum;
     return 0;
@@ -395,7 +391,7 @@ extern "C" {
 
 int lshkm_kpp_shard_ws_bytes(int64_t n, int64_t* bytes) {
     LSHKM_CHECK(bytes && n >= 0 && n <= INT32_MAX, LSHKM_ERR_ARG, "bad arguments (need 0 <= n < 2^31)");
-    *bytes = (int64_t)kmeans_pp_ws_bytes(n);
+    *bytes = (int64_t)kpp_layout(n).bytes;
     return 0;
 }
 
@@ -420,13 +416,9 @@ int lshkm_kpp_shard_chain(lshkm_ctx ctx, int64_t n, double s_in, void* ws, int64
     LSHKM_CHECK(s_out, LSHKM_ERR_ARG, "s_out is NULL");
     *s_out = s_in;
     if (n == 0) return 0;
-    KppShardHost o;
-    int rc;
-    if ((rc = launch_kpp_shard_chain(ctx->stream, n, s_in, ws, (unsigned long long*)ctx->stats.p)) ||
-        (rc = kpp_shard_read(ctx, n, ws, &o))) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
+    KppShardOut o;
+    const int lrc = launch_kpp_shard_chain(ctx->stream, n, s_in, ws, (unsigned long long*)ctx->stats.p);
+    if (const int rc = kpp_shard_read(ctx, n, ws, lrc, &o)) return rc;
     *s_out = o.s_out;
     return 0;
 }
@@ -437,12 +429,9 @@ int lshkm_kpp_shard_pick(lshkm_ctx ctx, int64_t n, double rd, int owns_row0, voi
     LSHKM_CHECK(row, LSHKM_ERR_ARG, "row is NULL");
     *row = -1;
     if (n == 0) return 0;
-    KppShardHost o;
-    int rc;
-    if ((rc = launch_kpp_shard_pick(ctx->stream, n, rd, owns_row0, ws)) || (rc = kpp_shard_read(ctx, n, ws, &o))) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
+    KppShardOut o;
+    const int lrc = launch_kpp_shard_pick(ctx->stream, n, rd, owns_row0, ws);
+    if (const int rc = kpp_shard_read(ctx, n, ws, lrc, &o)) return rc;
     LSHKM_CHECK(o.pick >= -1 && o.pick < n, LSHKM_ERR_STATE, "pick outside the shard (rd above the running sum?)");
     *row = o.pick;
     return 0;

@@ -247,16 +247,13 @@ int launch_km_finalize(hipStream_t s, const double* sums, const int64_t* counts,
 
 // k-means++ seeding (kmeanspp.hip): iterations 1..K-1 on the stream.
 // chosen[0] and canon[1..K-1] (the engine's canonical draws) already on the
-// device; ws holds kmeans_pp_ws_bytes(N) bytes.
-size_t kmeans_pp_ws_bytes(int64_t N);
+// device; ws holds kpp_layout(N).bytes bytes (kpp_layout.h).
 int launch_kmeans_pp(hipStream_t s, Pts X, int64_t N, int d, int K, int metric, const double* canon,
                      int32_t* chosen, void* ws, unsigned long long* stats);
 // One iteration over a row shard of n >= 1 rows (lshkm_kpp_shard_*), the host
 // between the steps; ws as above for n rows. Each step leaves what the host
-// reads at ws + kpp_shard_out_offset(n): u64 max bits and f64 sum m^2 (dist),
-// f64 s_out (chain), i64 local row or -1 (pick). crow: the newest centroid's
-// [d] row, of X's type.
-size_t kpp_shard_out_offset(int64_t n);
+// reads in the KppShardOut at ws + kpp_layout(n).out (kpp_layout.h). crow: the
+// newest centroid's [d] row, of X's type.
 int launch_kpp_shard_dist(hipStream_t s, Pts X, int64_t n, int d, int metric, const void* crow, int it, void* ws);
 int launch_kpp_shard_units(hipStream_t s, int64_t n, unsigned long long gmax_bits, double start, void* ws);
 int launch_kpp_shard_chain(hipStream_t s, int64_t n, double s_in, void* ws, unsigned long long* stats);

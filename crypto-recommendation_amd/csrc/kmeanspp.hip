@@ -14,52 +14,35 @@
 // them all up front and the whole seeding runs on the stream with no host
 // round trip.
 //
-// (3) is a strictly sequential fp64 chain s_m = RN(s_{m-1} + q_m) over N rows.
-// It is reproduced exactly, in parallel, from one observation: while s stays
-// in one binade [2^e, 2^(e+1)) every s is a multiple of u = 2^(e-52), so
-// RN(s + q) = s + u * RN_u(q) unless q is a tie (q/u = k + 1/2) — the chain is
-// an integer prefix sum there. Rows are cut into chunks of KPP_CHUNK:
-//   kpp_scan_kernel         the max of the minima; approximate chunk sums (the
-//                           distance pass's sum m^2 per 256 rows / max^2) and
-//                           their exclusive scan: approximate chunk starts
-//   kpp_chunk_units_kernel  guess each chunk's binade from its approximate
-//                           start; R = sum of RN_u(q) in units of u, or
-//                           "dirty" (tie, non-finite, tiny start); chunks
-//                           predicted to cross a binade, or holding a tie,
-//                           also get prefix arrays in binades e and e + 1
-//   kpp_chain_kernel        one wave walks the chunks with the EXACT running
-//                           s: a chunk whose guess is right (s in binade e and
-//                           s/u + R < 2^53) advances s by R*u exactly, 512
-//                           chunks per wave-wide integer scan; a crossing or
-//                           tie chunk is resolved from its prefix arrays with
-//                           one hardware add per crossing / tie row; the rest
-//                           (the first chunk, unresolvable rows) by hardware
-//                           fp64 adds row by row. Then the draw and the
-//                           reference's binary search, the prefix sums formed
-//                           only for the chunk the draw lands in.
+// (3) is a strictly sequential fp64 chain s_m = RN(s_{m-1} + q_m) over N rows,
+// reproduced exactly, in parallel, as an integer prefix sum inside each binade
+// of s: kpp_chain.h states that arithmetic and every rounding decision (checked
+// on the host against the plain chain), kpp_layout.h the workspace. The wave-
+// parallel forms are here. Rows are cut into chunks of KPP_CHUNK:
+//   kpp_scan_kernel         the max of the minima; approximate chunk starts
+//                           (the distance pass's sum m^2 per 256 rows / max^2)
+//   kpp_chunk_units_kernel  each chunk's record in the binade guessed from its
+//                           approximate start, its prefix arrays if it has any
+//   kpp_chain_kernel        one wave walks the chunks with the EXACT running s
+//                           (kpp_walk), 512 chunks per wave-wide integer scan;
+//                           then the draw and the reference's binary search,
+//                           the prefix sums formed only for the draw's chunk.
 //
 // Over contiguous row shards (lshkm_kpp_shard_*) the same device code runs per
 // shard with the host between the steps: a later row needs from the earlier
 // ones only the global max and the exact running s, and the chain's value does
 // not depend on where the chunks are cut. kpp_fold_kernel leaves the shard's max
 // and sum m^2 for the exchange; kpp_starts_kernel takes the global max and the
-// approximate sum before the shard; kpp_chain_shard_kernel is the walk from the
-// previous shard's s (no draw); kpp_pick_shard_kernel is the search for the
-// draw the host forms from the last shard's s.
-#include <climits>
-#include <cstdlib>
-#include <cstring>
-
+// approximate sum before the shard; kpp_chain_shard_kernel walks from the previous
+// shard's s (no draw); kpp_pick_shard_kernel searches for the host's draw.
 #include "common.h"
 #include "kernels.h"
 #include "exact.h"
+#include "kpp_layout.h"
 
 namespace lshkm {
 
-constexpr int KPP_THREADS = 256;
-constexpr int KPP_CHUNK = 512;                 // rows per chunk = 2 per thread
-constexpr int KPP_DIRTY = INT_MIN;
-constexpr int64_t KPP_TWO53 = 1ll << 53;
+constexpr int KPP_THREADS = KPP_GROUP;         // a thread per row of a group; a chunk = 2 rows per thread
 
 // q_m = (min_m / max)^2, as :121-124 (two roundings).
 __device__ inline double kpp_q(double m, double mx) {
@@ -67,23 +50,14 @@ __device__ inline double kpp_q(double m, double mx) {
     return __dmul_rn(t, t);
 }
 
-__device__ inline double kpp_max(const unsigned long long* mx_bits) {
-    return __longlong_as_double((long long)*mx_bits);
-}
-
-// Wave-level helpers of the exact walk (one wave, every lane active): an
-// inclusive int64 scan by DPP row shifts inside each 16-lane row plus the row
-// totals by readlane (no LDS round trips, unlike __shfl_up), and reads of a
-// uniform lane.
-__device__ inline int64_t dpp_shr64(int64_t v, int k) {
+// Wave-level helpers of the exact walk (one wave, every lane active): an inclusive
+// int64 scan by DPP row shifts inside each 16-lane row plus the row totals by
+// readlane (no LDS round trips, unlike __shfl_up), and reads of a uniform lane.
+template <int K>   // row_shr:K (0x110 + K); lanes without a source read 0 (bound_ctrl)
+__device__ inline int64_t dpp_shr64(int64_t v) {
     const int lo = (int)(uint32_t)(uint64_t)v, hi = (int)(uint32_t)((uint64_t)v >> 32);
-    int rl, rh;
-    switch (k) {   // row_shr:k (0x110 + k); lanes without a source read 0 (bound_ctrl)
-        case 1: rl = __builtin_amdgcn_update_dpp(0, lo, 0x111, 0xF, 0xF, true); rh = __builtin_amdgcn_update_dpp(0, hi, 0x111, 0xF, 0xF, true); break;
-        case 2: rl = __builtin_amdgcn_update_dpp(0, lo, 0x112, 0xF, 0xF, true); rh = __builtin_amdgcn_update_dpp(0, hi, 0x112, 0xF, 0xF, true); break;
-        case 4: rl = __builtin_amdgcn_update_dpp(0, lo, 0x114, 0xF, 0xF, true); rh = __builtin_amdgcn_update_dpp(0, hi, 0x114, 0xF, 0xF, true); break;
-        default: rl = __builtin_amdgcn_update_dpp(0, lo, 0x118, 0xF, 0xF, true); rh = __builtin_amdgcn_update_dpp(0, hi, 0x118, 0xF, 0xF, true); break;
-    }
+    const int rl = __builtin_amdgcn_update_dpp(0, lo, 0x110 + K, 0xF, 0xF, true);
+    const int rh = __builtin_amdgcn_update_dpp(0, hi, 0x110 + K, 0xF, 0xF, true);
     return (int64_t)(((uint64_t)(uint32_t)rh << 32) | (uint32_t)rl);
 }
 __device__ inline int64_t readlane64(int64_t v, int l) {
@@ -92,18 +66,13 @@ __device__ inline int64_t readlane64(int64_t v, int l) {
     return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
 }
 __device__ inline int64_t wave_incl_scan64(int64_t v, int lane) {
-    v += dpp_shr64(v, 1);
-    v += dpp_shr64(v, 2);
-    v += dpp_shr64(v, 4);
-    v += dpp_shr64(v, 8);
+    v += dpp_shr64<1>(v);
+    v += dpp_shr64<2>(v);
+    v += dpp_shr64<4>(v);
+    v += dpp_shr64<8>(v);
     const int64_t t0 = readlane64(v, 15), t1 = readlane64(v, 31), t2 = readlane64(v, 47);
     const int row = lane >> 4;
     return v + (row > 0 ? t0 : 0) + (row > 1 ? t1 : 0) + (row > 2 ? t2 : 0);
-}
-
-// Binade exponent of a positive normal double (s in [2^e, 2^(e+1))).
-__device__ inline int kpp_binade(double s) {
-    return (int)((__double_as_longlong(s) >> 52) & 0x7ff) - 1023;
 }
 
 // ------------------------------------------------------------- (1) + (2)
@@ -123,9 +92,8 @@ constexpr int KPP_DJ = 32;
 constexpr int KPP_V4 = KPP_THREADS * KPP_DJ / 4 / KPP_THREADS;   // float4 per thread per slice (8)
 
 // The max of the minima: each block writes its own (positive doubles order as
-// their bit patterns; 0 when it has none) and kpp_max_reduce_kernel folds them
-// -- one global atomic per wave on a single word serialised at ~12 ns each
-// (15,600 waves at N = 1M: ~0.19 ms of the 0.25 ms distance pass).
+// their bit patterns; 0 when it has none) for kpp_fold_max -- one global atomic
+// per wave on a single word serialised at ~12 ns each (~0.19 ms at N = 1M).
 __device__ inline void kpp_block_max(double best, unsigned long long* __restrict__ bmax) {
     __shared__ double wbest[KPP_THREADS / 64];
     for (int off = 32; off >= 1; off >>= 1) {
@@ -157,14 +125,24 @@ __device__ inline void kpp_group_sum(double v, double* __restrict__ gsum, int64_
     __syncthreads();
 }
 
+// Row n's distance dd to the newest centroid -> its running minimum (the
+// earlier value unless dd is strictly smaller) -> mind[n] and the thread's max.
+__device__ inline double kpp_take_min(double dd, int it, double* __restrict__ mind, int64_t n, double& best) {
+    double m = dd;
+    if (it > 1) {
+        const double prev = mind[n];
+        if (!(dd < prev)) m = prev;
+    }
+    mind[n] = m;
+    if (m > best) best = m;
+    return m;
+}
+
 // TX: fp32 or fp64 rows (VEC only for fp32).
 template <int METRIC, bool VEC, typename TX>
-__global__ __launch_bounds__(KPP_THREADS) void kpp_dist_kernel(const TX* __restrict__ X, int64_t N, int d,
-                                                               const int32_t* __restrict__ chosen,
-                                                               const TX* __restrict__ cext, int it,
-                                                               double* __restrict__ mind,
-                                                               unsigned long long* __restrict__ bmax,
-                                                               double* __restrict__ gsum) {
+__global__ __launch_bounds__(KPP_THREADS) void kpp_dist_kernel(
+    const TX* __restrict__ X, int64_t N, int d, const int32_t* __restrict__ chosen, const TX* __restrict__ cext, int it,
+    double* __restrict__ mind, unsigned long long* __restrict__ bmax, double* __restrict__ gsum) {
     static_assert(!VEC || sizeof(TX) == 4, "the float4 form reads fp32 rows");
     constexpr int DJ = sizeof(TX) == 4 ? KPP_DJ : KPP_DJ / 2;     // tile <= 34 KiB either way
     __shared__ TX tile[KPP_THREADS][DJ + 1];
@@ -261,20 +239,8 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_kernel(const TX* __restr
         }
         double m = 0.0;
         if (n < N) {
-        double dd;
-        if (METRIC == 0) {
-            dd = sqrt(acc);
-        } else {
-            const double denom = __dmul_rn(sqrt(a), sqrt(cb));
-            dd = one_minus(x87_quot(ip.value(), denom));
-        }
-        m = dd;
-        if (it > 1) {
-            const double prev = mind[n];
-            if (!(dd < prev)) m = prev;
-        }
-        mind[n] = m;
-        if (m > best) best = m;
+            const double dd = METRIC == 0 ? sqrt(acc) : one_minus(x87_quot(ip.value(), __dmul_rn(sqrt(a), sqrt(cb))));
+            m = kpp_take_min(dd, it, mind, n, best);
         }
         kpp_group_sum(m * m, gsum, row0 / KPP_THREADS);
     }
@@ -288,12 +254,9 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_kernel(const TX* __restr
 // flight; the squares go through gp_sq_wave (glibc's pow batched over the
 // wave). The centroid row is an LDS broadcast. Same exact-order chain as above.
 constexpr int KR_S = 20;                                 // LDS row stride of the transpose (floats)
-__global__ __launch_bounds__(KPP_THREADS) void kpp_dist_reg_kernel(const float* __restrict__ X, int64_t N, int d,
-                                                                   const int32_t* __restrict__ chosen,
-                                                                   const float* __restrict__ cext, int it,
-                                                                   double* __restrict__ mind,
-                                                                   unsigned long long* __restrict__ bmax,
-                                                                   double* __restrict__ gsum) {
+__global__ __launch_bounds__(KPP_THREADS) void kpp_dist_reg_kernel(
+    const float* __restrict__ X, int64_t N, int d, const int32_t* __restrict__ chosen, const float* __restrict__ cext,
+    int it, double* __restrict__ mind, unsigned long long* __restrict__ bmax, double* __restrict__ gsum) {
     extern __shared__ __attribute__((aligned(8))) char kpp_dyn2[];
     float* cs = reinterpret_cast<float*>(kpp_dyn2);     // [d]
     __shared__ double sqs[KPP_THREADS / 64][64 * 16];   // gp_sq_wave: 64 * 16 per wave
@@ -329,9 +292,7 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_reg_kernel(const float* 
             *reinterpret_cast<float4*>(t0 + 16 * KR_S) = c1;
             *reinterpret_cast<float4*>(t0 + 32 * KR_S) = c2;
             *reinterpret_cast<float4*>(t0 + 48 * KR_S) = c3;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             double df[16], p[16];
 #pragma unroll
             for (int h = 0; h < 4; h++) {
@@ -340,24 +301,12 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_reg_kernel(const float* 
 #pragma unroll
                 for (int u = 0; u < 4; u++) df[4 * h + u] = __dsub_rn((double)xv[u], (double)cs[j0 + 4 * h + u]);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             gp_sq_wave<16, false>(df, p, sqb);
 #pragma unroll
             for (int u = 0; u < 16; u++) acc = __dadd_rn(acc, p[u]);
         }
-        double m = 0.0;
-        if (n < N) {
-            const double dd = sqrt(acc);
-            m = dd;
-            if (it > 1) {
-                const double prev = mind[n];
-                if (!(dd < prev)) m = prev;
-            }
-            mind[n] = m;
-            if (m > best) best = m;
-        }
+        const double m = n < N ? kpp_take_min(sqrt(acc), it, mind, n, best) : 0.0;
         kpp_group_sum(m * m, gsum, row0 / KPP_THREADS);
     }
     kpp_block_max(best, bmax);
@@ -369,7 +318,6 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_dist_reg_kernel(const float* 
 // (two 256-row groups per chunk) and their exclusive scan (order irrelevant:
 // guesses only).
 constexpr int KPP_SCAN_THREADS = 1024;
-static_assert(KPP_CHUNK == 2 * KPP_THREADS, "two row groups per chunk");
 
 // The block's fold of the per-block maxima (every thread gets it).
 __device__ inline unsigned long long kpp_fold_max(const unsigned long long* __restrict__ bmax, int nb,
@@ -410,10 +358,9 @@ __device__ inline void kpp_chunk_starts(const double* __restrict__ gsum, int64_t
     }
 }
 
-__global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_scan_kernel(const unsigned long long* __restrict__ bmax, int nb,
-                                                                    const double* __restrict__ gsum, int64_t ngroups,
-                                                                    int64_t nch, unsigned long long* __restrict__ mx_bits,
-                                                                    double* __restrict__ chunk_start) {
+__global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_scan_kernel(
+    const unsigned long long* __restrict__ bmax, int nb, const double* __restrict__ gsum, int64_t ngroups, int64_t nch,
+    unsigned long long* __restrict__ mx_bits, double* __restrict__ chunk_start) {
     __shared__ unsigned long long redm[KPP_SCAN_THREADS];
     __shared__ double part[KPP_SCAN_THREADS];
     const unsigned long long mxb = kpp_fold_max(bmax, nb, redm);
@@ -421,20 +368,11 @@ __global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_scan_kernel(const unsign
     kpp_chunk_starts(gsum, ngroups, nch, __longlong_as_double((long long)mxb), 0.0, chunk_start, part);
 }
 
-// What a shard's steps leave for the host (lshkm_kpp_shard_*), after the max
-// word of the workspace.
-struct KppShardOut {
-    unsigned long long max_bits;   // dist: the shard's max of minima (0 if none)
-    double sum;                    // dist: its approximate sum m^2
-    double s_out;                  // chain: the running sum after its rows
-    long long pick;                // pick: a local row, or -1
-};
-
 // A shard's half of kpp_scan_kernel before the exchange: its own max and its
 // sum m^2 (any order: guesses only), for the host.
-__global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_fold_kernel(const unsigned long long* __restrict__ bmax, int nb,
-                                                                    const double* __restrict__ gsum, int64_t ngroups,
-                                                                    KppShardOut* __restrict__ out) {
+__global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_fold_kernel(
+    const unsigned long long* __restrict__ bmax, int nb, const double* __restrict__ gsum, int64_t ngroups,
+    KppShardOut* __restrict__ out) {
     __shared__ unsigned long long redm[KPP_SCAN_THREADS];
     __shared__ double part[KPP_SCAN_THREADS];
     const unsigned long long mxb = kpp_fold_max(bmax, nb, redm);
@@ -454,63 +392,23 @@ __global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_fold_kernel(const unsign
 
 // ... and after it: the GLOBAL max (mx_bits, for the exact q_m) and the chunk
 // starts from the approximate sum of the rows before this shard.
-__global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_starts_kernel(const double* __restrict__ gsum, int64_t ngroups,
-                                                                      int64_t nch, unsigned long long gmax_bits,
-                                                                      double start0,
-                                                                      unsigned long long* __restrict__ mx_bits,
-                                                                      double* __restrict__ chunk_start) {
+__global__ __launch_bounds__(KPP_SCAN_THREADS) void kpp_starts_kernel(
+    const double* __restrict__ gsum, int64_t ngroups, int64_t nch, unsigned long long gmax_bits, double start0,
+    unsigned long long* __restrict__ mx_bits, double* __restrict__ chunk_start) {
     __shared__ double part[KPP_SCAN_THREADS];
     if (threadIdx.x == 0) *mx_bits = gmax_bits;
     kpp_chunk_starts(gsum, ngroups, nch, __longlong_as_double((long long)gmax_bits), start0, chunk_start, part);
 }
 
-// RN_u(q) in units of u = 2^(e-52), or -1 if q cannot be resolved in binade e
-// (non-finite, q >= 2^(e+1), or an exact tie).
-__device__ inline int64_t kpp_units(double q, int e) {
-    if (!(q >= 0.0) || !(q < __longlong_as_double((long long)(e + 1 + 1023) << 52))) return -1;
-    const double t = ldexp(q, 52 - e);          // exact: t < 2^53
-    const double r = floor(t);
-    const double f = t - r;                     // exact
-    if (f == 0.5) return -1;
-    return (int64_t)r + (f > 0.5 ? 1 : 0);
-}
-
-struct KppChunk {
-    int64_t R;     // sum of the chunk's RN_u(q) in units of 2^(e-52)
-    int32_t e;     // guessed binade, or KPP_DIRTY
-    int32_t dual;  // 0, or 2048 + the guessed binade eg: prefix arrays in eg, eg + 1 in pa / pb
-};
-// prefix-array entries: the inclusive prefix of RN_u(q) (a tie counted as its
-// floor) | KPP_TIE if the row itself is a tie; negative from an unresolvable
-// row (non-finite, q >= 2^(e+1)) on. Prefixes stay below 512 * 2^53 = 2^62.
-constexpr int64_t KPP_TIE = 1ll << 62;
-constexpr int64_t KPP_PMASK = KPP_TIE - 1;
-constexpr int64_t KPP_POISON = INT64_MIN;
-
-// RN_u(q) in units of u = 2^(e-52) with its class: 0 resolved, 1 a tie (the
-// floor returned: the rounding depends on the running sum's parity), 2 not
-// resolvable in binade e (non-finite, q >= 2^(e+1); 0 returned).
-__device__ inline int64_t kpp_units_c(double q, int e, int& cls) {
-    if (!(q >= 0.0) || !(q < __longlong_as_double((long long)(e + 1 + 1023) << 52))) { cls = 2; return 0; }
-    const double t = ldexp(q, 52 - e);
-    const double r = floor(t);
-    const double f = t - r;
-    cls = f == 0.5 ? 1 : 0;
-    return (int64_t)r + (f > 0.5 ? 1 : 0);
-}
-
-// Chunk guesses. A chunk the running sum is predicted to cross (the next
-// chunk's approximate start lies in a higher binade, or its own sum leaves the
-// binade) or that holds a tie also gets its prefix arrays in binades e and
-// e + 1 (pa, pb), so the walk resolves it with one hardware add per crossing
-// or tie row instead of element by element. Thread t owns rows 2t, 2t+1 (row
-// order for the scans).
-__global__ __launch_bounds__(KPP_THREADS) void kpp_chunk_units_kernel(const double* __restrict__ mind, int64_t N,
-                                                                      const unsigned long long* __restrict__ mx_bits,
-                                                                      double* __restrict__ qbuf,
-                                                                      const double* __restrict__ chunk_start, int64_t nch,
-                                                                      KppChunk* __restrict__ meta,
-                                                                      int64_t* __restrict__ pa, int64_t* __restrict__ pb) {
+// Chunk guesses: each chunk's record (kpp_chunk_record) from its rows' units in
+// the binade of its approximate start. A chunk with prefix arrays (a predicted
+// crossing, a tie) gets them in binades e and e + 1 (pa, pb), so the walk
+// resolves it with one hardware add per crossing or tie row instead of element
+// by element. Thread t owns rows 2t, 2t+1 (row order for the scans).
+__global__ __launch_bounds__(KPP_THREADS) void kpp_chunk_units_kernel(
+    const double* __restrict__ mind, int64_t N, const unsigned long long* __restrict__ mx_bits, double* __restrict__ qbuf,
+    const double* __restrict__ chunk_start, int64_t nch, KppChunk* __restrict__ meta, int64_t* __restrict__ pa,
+    int64_t* __restrict__ pb) {
     static_assert(KPP_CHUNK == 2 * KPP_THREADS, "two rows per thread");
     __shared__ long long red[KPP_THREADS / 64];
     __shared__ int redc[KPP_THREADS / 64];
@@ -518,16 +416,15 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_chunk_units_kernel(const doub
     const int64_t c0 = (int64_t)blockIdx.x * KPP_CHUNK;
     const double a = chunk_start[blockIdx.x];
     // a guess only; tiny or non-finite starts are left to the exact walk
-    const bool usable = a >= 0x1p-900 && a < 0x1p62;
-    const int e = usable ? kpp_binade(a) : 0;
+    const int e = kpp_binade0(a);
     const int64_t i0 = c0 + 2 * threadIdx.x;
     // q_m = (min_m / max)^2 (:121-124), stored for the walk
-    const double mx = kpp_max(mx_bits);
+    const double mx = __longlong_as_double((long long)*mx_bits);
     const double q0 = i0 < N ? kpp_q(mind[i0], mx) : 0.0, q1 = i0 + 1 < N ? kpp_q(mind[i0 + 1], mx) : 0.0;
     if (i0 < N) qbuf[i0] = q0;
     if (i0 + 1 < N) qbuf[i0 + 1] = q1;
     int ca0, ca1;
-    const int64_t ra0 = kpp_units_c(q0, e, ca0), ra1 = kpp_units_c(q1, e, ca1);
+    const int64_t ra0 = kpp_units(q0, e, ca0), ra1 = kpp_units(q1, e, ca1);
     long long v = ra0 + ra1;
     int cl = ca0 | ca1;
     for (int off = 32; off >= 1; off >>= 1) {
@@ -540,12 +437,11 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_chunk_units_kernel(const doub
     long long t = 0;
     int any = 0;
     for (int k = 0; k < KPP_THREADS / 64; k++) { t += red[k]; any |= redc[k]; }
-    const bool cross = usable && (t >= KPP_TWO53 || (blockIdx.x + 1 < nch && !(chunk_start[blockIdx.x + 1] <
-                                                                            __longlong_as_double((long long)(e + 1 + 1023) << 52))));
-    const bool arrays = usable && (cross || (any & 1));
-    if (arrays) {                                  // block-uniform
+    const bool has_next = blockIdx.x + 1 < nch;
+    const KppChunk m = kpp_chunk_record(a, has_next, has_next ? chunk_start[blockIdx.x + 1] : 0.0, t, any);
+    if (m.dual != 0) {                             // prefix arrays; block-uniform
         int cb0, cb1;
-        const int64_t rb0 = kpp_units_c(q0, e + 1, cb0), rb1 = kpp_units_c(q1, e + 1, cb1);
+        const int64_t rb0 = kpp_units(q0, e + 1, cb0), rb1 = kpp_units(q1, e + 1, cb1);
         // values and unresolvable-row counts, scanned in row order
         int64_t sa = wave_incl_scan64(ra0 + ra1, lane), sb = wave_incl_scan64(rb0 + rb1, lane);
         int64_t sfa = wave_incl_scan64((ca0 == 2) + (ca1 == 2), lane), sfb = wave_incl_scan64((cb0 == 2) + (cb1 == 2), lane);
@@ -553,254 +449,247 @@ __global__ __launch_bounds__(KPP_THREADS) void kpp_chunk_units_kernel(const doub
         __syncthreads();
         for (int k = 0; k < w; k++) { sa += wtot[0][k]; sb += wtot[1][k]; sfa += wtot[2][k]; sfb += wtot[3][k]; }
         // inclusive prefixes at rows 2t and 2t + 1
-        auto enc = [](int64_t p, int64_t bad, int cls) { return bad ? KPP_POISON : p | (cls == 1 ? KPP_TIE : 0); };
         if (i0 < N) {
-            pa[i0] = enc(sa - ra1, sfa - (ca1 == 2), ca0);
-            pb[i0] = enc(sb - rb1, sfb - (cb1 == 2), cb0);
+            pa[i0] = kpp_entry(sa - ra1, sfa - (ca1 == 2), ca0);
+            pb[i0] = kpp_entry(sb - rb1, sfb - (cb1 == 2), cb0);
         }
         if (i0 + 1 < N) {
-            pa[i0 + 1] = enc(sa, sfa, ca1);
-            pb[i0 + 1] = enc(sb, sfb, cb1);
+            pa[i0 + 1] = kpp_entry(sa, sfa, ca1);
+            pb[i0 + 1] = kpp_entry(sb, sfb, cb1);
         }
     }
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0) meta[blockIdx.x] = m;
+}
+
+// The exact walk (one wave: kpp_walk, after its parts). s is uniform across the
+// wave. A step covers 64 lanes x KPP_CPL consecutive chunks (lane-local prefix,
+// then a wave scan of the lane totals); R < 2^53 per chunk keeps every prefix
+// below 2^62. Starts from s (0 on one device and on the shard of global row 0,
+// else the sum after the earlier shards' rows: a chunk's result depends on the rows
+// before it through s alone), returns s after row N - 1; nseq counts the stop chunks.
+constexpr int KPP_CPL = 8;                         // chunks per lane per step
+constexpr int KPP_STEP = 64 * KPP_CPL;
+constexpr int KPP_WIN = 2 * KPP_STEP;              // chunk records staged in LDS (16 KB)
+constexpr int KPP_EPL = KPP_CHUNK / 64;            // rows of a chunk per lane
+struct KppWalkLds {
+    KppChunk wm[KPP_WIN];                          // the records of chunks win0 .. win0 + WIN - 1
+    double qs[KPP_CHUNK];                          // a stop chunk's q and prefix arrays
+    int64_t pas[KPP_CHUNK], pbs[KPP_CHUNK];
+};
+
+// (Re)fill the window at win0: all loads in flight before the LDS writes
+// (clamped indices: a guarded load per element compiled to one round trip each).
+__device__ __forceinline__ void kpp_fill(KppWalkLds& L, const KppChunk* __restrict__ meta, int64_t nch, int64_t win0,
+                                         int lane) {
+    KppChunk tmp[KPP_WIN / 64];
+#pragma unroll
+    for (int t = 0; t < KPP_WIN / 64; t++) {
+        const int64_t j = win0 + lane + 64 * t;
+        tmp[t] = meta[j < nch ? j : nch - 1];
+    }
+#pragma unroll
+    for (int t = 0; t < KPP_WIN / 64; t++) L.wm[lane + 64 * t] = tmp[t];
+    wave_sync();
+}
+
+// The integer step over chunks base .. base + STEP - 1 (inside the window):
+// those before the first whose guess does not hold (kpp_guess_holds for the s
+// it would start from) get their exact start in chunk_s and mode 0, and s moves
+// past them. Returns that stop chunk (nch: the end), or -1 if all were resolved.
+__device__ __forceinline__ int64_t kpp_step(const KppWalkLds& L, int64_t base, int64_t win0, int64_t nch,
+                                            double* chunk_s, int32_t* chunk_mode, double& s, int lane) {
+    const bool s_ok = kpp_usable(s);
+    const int es = kpp_binade0(s);
+    const int64_t s_units = s_ok ? kpp_to_units(s, es) : 0;
+    const int64_t j0 = base + (int64_t)lane * KPP_CPL;
+    int64_t R[KPP_CPL];
+    int lbad = KPP_CPL;                            // first chunk of the lane with a wrong guess
+    int64_t tot = 0;
+#pragma unroll
+    for (int t = 0; t < KPP_CPL; t++) {
+        const int64_t j = j0 + t;
         KppChunk m;
-        // a tie or unresolvable row makes the chunk dirty (the walk stops
-        // there); R >= 2^53 (it leaves the binade) stops it as well
-        const bool dirty = !usable || any != 0;
-        m.R = dirty ? 0 : t;
-        m.e = dirty ? KPP_DIRTY : e;
-        m.dual = arrays ? 2048 + e : 0;
-        meta[blockIdx.x] = m;
+        m.R = 0; m.e = KPP_DIRTY;
+        if (j < nch) m = L.wm[j - win0];
+        R[t] = m.R;
+        tot += m.R;
+        if (lbad == KPP_CPL && !(j < nch && kpp_guess_binade(s_ok, es, m))) lbad = t;
+    }
+    // exclusive prefix of the lane totals
+    int64_t pre = wave_incl_scan64(tot, lane) - tot;
+    // the lane's first chunk that is wrong or would leave the binade
+    int first = lbad;
+    int64_t run = s_units + pre;
+#pragma unroll
+    for (int t = 0; t < KPP_CPL; t++) {
+        if (t < first && !kpp_fits(run, R[t])) first = t;
+        if (t < first) run += R[t];
+    }
+    const unsigned long long bad = __ballot(first < KPP_CPL);
+    const int fl = bad ? __ffsll((long long)bad) - 1 : 64;       // first lane with a stop
+    // lanes before fl: all KPP_CPL chunks resolved; lane fl: its chunks before
+    // `first` (lanes before fl have first == KPP_CPL)
+    if (lane <= fl) {
+        int64_t r = s_units + pre;
+#pragma unroll
+        for (int t = 0; t < KPP_CPL; t++) {
+            if (t < first) {
+                chunk_s[j0 + t] = kpp_from_units(r, es);
+                chunk_mode[j0 + t] = 0;
+                r += R[t];
+            }
+        }
+    }
+    const int fstop = fl < 64 ? __builtin_amdgcn_readlane(first, fl) : KPP_CPL;
+    const int64_t c = base + (int64_t)(fl < 64 ? fl : 64) * KPP_CPL + (fl < 64 ? fstop : 0);
+    // s after the resolved chunks: `run` of lane fl (or of lane 63 if none stopped)
+    const int64_t adv = readlane64(run, fl < 64 ? fl : 63);
+    if (c > base) s = kpp_from_units(adv, es);
+    return fl == 64 ? -1 : c;
+}
+
+// Stage a stop chunk of n rows (q, pa, pb: at its first row): lane l holds rows
+// 8l..8l+7 of the prefix arrays in registers; q and the arrays also go to LDS for
+// the uniform reads; every load is issued before the first use (clamped indices).
+__device__ __forceinline__ void kpp_stage(KppWalkLds& L, const double* __restrict__ q, const int64_t* __restrict__ pa,
+                                          const int64_t* __restrict__ pb, int n, bool arrays, int64_t (&PA)[KPP_EPL],
+                                          int64_t (&PB)[KPP_EPL], int lane) {
+    double qv[KPP_EPL];
+#pragma unroll
+    for (int t = 0; t < KPP_EPL; t++) {
+        const int i = lane * KPP_EPL + t;
+        qv[t] = q[i < n ? i : n - 1];
+    }
+    if (arrays) {
+#pragma unroll
+        for (int t = 0; t < KPP_EPL; t++) {
+            const int i = lane * KPP_EPL + t;
+            PA[t] = pa[i < n ? i : n - 1];
+            PB[t] = pb[i < n ? i : n - 1];
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < KPP_EPL; t++) L.qs[lane * KPP_EPL + t] = qv[t];
+    if (arrays) {
+#pragma unroll
+        for (int t = 0; t < KPP_EPL; t++) { L.pas[lane * KPP_EPL + t] = PA[t]; L.pbs[lane * KPP_EPL + t] = PB[t]; }
+    }
+    wave_sync();
+}
+
+// Rows [i0, m) of the staged chunk as integers in binade E from the prefix array
+// P (in LDS; PR: this lane's entries; s exact, in binade E): returns m, the first
+// row that stops (kpp_entry_stops); s moves to row m - 1. cum: at the chunk's row 0.
+__device__ __forceinline__ int kpp_resolve(const int64_t* P, const int64_t (&PR)[KPP_EPL], int i0, int n, int E,
+                                           double* cum, double& s, int lane) {
+    const int64_t su = kpp_to_units(s, E);
+    const int64_t base_p = i0 > 0 ? kpp_entry_prefix(P[i0 - 1]) : 0;
+    int lf = KPP_EPL;
+#pragma unroll
+    for (int t = 0; t < KPP_EPL; t++) {
+        const int i = lane * KPP_EPL + t;
+        if (lf == KPP_EPL && i >= i0 && i < n && kpp_entry_stops(PR[t], su, base_p)) lf = t;
+    }
+    const unsigned long long fbits = __ballot(lf < KPP_EPL);
+    const int fl = fbits ? __ffsll((long long)fbits) - 1 : 64;
+    const int m = fl < 64 ? fl * KPP_EPL + __builtin_amdgcn_readlane(lf, fl) : n;
+    double out[KPP_EPL];
+#pragma unroll
+    for (int t = 0; t < KPP_EPL; t++) out[t] = kpp_from_units(su + (kpp_entry_prefix(PR[t]) - base_p), E);
+#pragma unroll
+    for (int t = 0; t < KPP_EPL; t++) {
+        const int i = lane * KPP_EPL + t;
+        if (i >= i0 && i < m) cum[i] = out[t];
+    }
+    if (m > i0) s = kpp_from_units(su + (kpp_entry_prefix(P[m - 1]) - base_p), E);
+    return m;
+}
+
+// The staged chunk through its prefix arrays in binades eg and eg + 1: the rows
+// before a crossing from pa, the crossing (or tie) row by the reference's hardware
+// add, the rows after it from pb. Returns the first row left to the tail (n: none).
+__device__ __forceinline__ int kpp_two_binades(const KppWalkLds& L, const int64_t (&PA)[KPP_EPL],
+                                               const int64_t (&PB)[KPP_EPL], int eg, int n, double* cum, double& s,
+                                               int lane) {
+    int i0 = 0;
+    while (i0 < n) {
+        if (!kpp_usable(s)) break;
+        const int E = kpp_binade(s);
+        if (E != eg && E != eg + 1) break;
+        const int64_t* P = E == eg ? L.pas : L.pbs;
+        i0 = E == eg ? kpp_resolve(L.pas, PA, i0, n, E, cum, s, lane) : kpp_resolve(L.pbs, PB, i0, n, E, cum, s, lane);
+        if (i0 >= n || kpp_entry_poison(P[i0])) break;   // done, or an unresolvable row: one by one from it
+        s = __dadd_rn(L.qs[i0], s);             // a tie or crossing row: the reference's add
+        if (lane == 0) cum[i0] = s;
+        i0++;
+    }
+    return i0;
+}
+
+// Rows i0 .. n - 1 one by one, the reference's adds (:122-125): every lane adds
+// and stores the same value (one line, no exec toggling, ~26 cycles per row),
+// the next 16 values read ahead from LDS with uniform-address (broadcast) reads.
+__device__ __forceinline__ void kpp_tail(const double* qs, int i0, int n, double* cum, double& s) {
+    constexpr int QB = 16;
+    double qn[QB];
+#pragma unroll
+    for (int t = 0; t < QB; t++) qn[t] = qs[i0 + t < n ? i0 + t : n - 1];
+    int i = i0;
+    for (; i + QB <= n; i += QB) {
+        double qv[QB];
+#pragma unroll
+        for (int t = 0; t < QB; t++) qv[t] = qn[t];
+        if (i + 2 * QB <= n) {
+#pragma unroll
+            for (int t = 0; t < QB; t++) qn[t] = qs[i + QB + t];
+        }
+#pragma unroll
+        for (int t = 0; t < QB; t++) {
+            s = __dadd_rn(qv[t], s);           // the reference's add (0 + q_0 = q_0 for row 0)
+            cum[i + t] = s;
+        }
+    }
+    for (; i < n; i++) {
+        s = __dadd_rn(qs[i], s);
+        cum[i] = s;
     }
 }
 
-// The exact walk (one wave). s is uniform across the wave. A step covers
-// 64 lanes x CPL consecutive chunks (lane-local prefix, then a wave scan of
-// the lane totals); R < 2^53 per chunk keeps every prefix below 2^62.
-// Starts from s (0 on one device and on the shard of global row 0, else the
-// running sum after the earlier shards' rows: a chunk's result depends on the
-// rows before it through s alone) and returns s after row N - 1; nseq counts
-// the stop chunks.
-__device__ __forceinline__ double kpp_walk(const double* __restrict__ qbuf, int64_t N,
-                                           const KppChunk* __restrict__ meta, int64_t nch,
-                                           const int64_t* __restrict__ pa, const int64_t* __restrict__ pb,
-                                           double* chunk_s, int32_t* chunk_mode, double* cum, double s,
-                                           unsigned long long& nseq) {
-    constexpr int CPL = 8;                         // chunks per lane per step
-    constexpr int STEP = 64 * CPL;
-    constexpr int WIN = 2 * STEP;                  // chunk metadata staged in LDS (16 KB)
-    __shared__ KppChunk wm[WIN];
-    __shared__ double qs[KPP_CHUNK];
-    __shared__ int64_t pas[KPP_CHUNK], pbs[KPP_CHUNK];
+__device__ __forceinline__ double kpp_walk(
+    const double* __restrict__ qbuf, int64_t N, const KppChunk* __restrict__ meta, int64_t nch,
+    const int64_t* __restrict__ pa, const int64_t* __restrict__ pb, double* chunk_s, int32_t* chunk_mode, double* cum,
+    double s, unsigned long long& nseq) {
+    __shared__ KppWalkLds L;
     const int lane = threadIdx.x;
-    int64_t base = 0, win0 = -2 * WIN;
-#if defined(KPP_PROF)
-    unsigned long long tp[5] = {0, 0, 0, 0, 0}, npass = 0;
-    unsigned long long tq = __builtin_amdgcn_s_memtime();
-#define KPP_T(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tp[i] += t_ - tq; tq = t_; }
-#else
-#define KPP_T(i)
-#endif
+    int64_t base = 0, win0 = -2 * KPP_WIN;
     while (base < nch) {
-        KPP_T(4)
-        if (base < win0 || base + STEP > win0 + WIN) {   // (re)fill the window at base
-            win0 = base;
-            // all loads in flight before the LDS writes (clamped indices: a guarded
-            // load per element compiled to one round trip each)
-            KppChunk tmp[WIN / 64];
-#pragma unroll
-            for (int t = 0; t < WIN / 64; t++) {
-                const int64_t j = win0 + lane + 64 * t;
-                tmp[t] = meta[j < nch ? j : nch - 1];
-            }
-#pragma unroll
-            for (int t = 0; t < WIN / 64; t++) wm[lane + 64 * t] = tmp[t];
-            wave_sync();
-        }
-        KPP_T(0)
-        const bool s_ok = s >= 0x1p-900 && s < 0x1p62;
-        const int es = s_ok ? kpp_binade(s) : 0;
-        const int64_t s_units = s_ok ? (int64_t)ldexp(s, 52 - es) : 0;
-        const int64_t j0 = base + (int64_t)lane * CPL;
-        int64_t R[CPL];
-        int lbad = CPL;                            // first chunk of the lane with a wrong guess
-        int64_t tot = 0;
-#pragma unroll
-        for (int t = 0; t < CPL; t++) {
-            const int64_t j = j0 + t;
-            KppChunk m;
-            m.R = 0; m.e = KPP_DIRTY;
-            if (j < nch) m = wm[j - win0];
-            R[t] = m.R;
-            tot += m.R;
-            if (lbad == CPL && !(j < nch && s_ok && m.e == es)) lbad = t;
-        }
-        // exclusive prefix of the lane totals
-        int64_t pre = wave_incl_scan64(tot, lane) - tot;
-        // the lane's first chunk that is wrong or would leave the binade
-        int first = lbad;
-        int64_t run = s_units + pre;
-#pragma unroll
-        for (int t = 0; t < CPL; t++) {
-            if (t < first && run + R[t] >= KPP_TWO53) first = t;
-            if (t < first) run += R[t];
-        }
-        const unsigned long long bad = __ballot(first < CPL);
-        const int fl = bad ? __ffsll((long long)bad) - 1 : 64;       // first lane with a stop
-        // lanes before fl: all CPL chunks resolved; lane fl: its chunks before
-        // `first` (lanes before fl have first == CPL)
-        if (lane <= fl) {
-            int64_t r = s_units + pre;
-#pragma unroll
-            for (int t = 0; t < CPL; t++) {
-                if (t < first) {
-                    chunk_s[j0 + t] = ldexp((double)r, es - 52);
-                    chunk_mode[j0 + t] = 0;
-                    r += R[t];
-                }
-            }
-        }
-        const int fstop = fl < 64 ? __builtin_amdgcn_readlane(first, fl) : CPL;
-        const int64_t c = base + (int64_t)(fl < 64 ? fl : 64) * CPL + (fl < 64 ? fstop : 0);
-        // s after the resolved chunks: `run` of lane fl (or of lane 63 if none stopped)
-        const int64_t adv = readlane64(run, fl < 64 ? fl : 63);
-        if (c > base) s = ldexp((double)adv, es - 52);
-        if (fl == 64) {
-            base += STEP;
+        if (base < win0 || base + KPP_STEP > win0 + KPP_WIN) kpp_fill(L, meta, nch, win0 = base, lane);
+        // now win0 <= base and base + STEP <= win0 + WIN: a stop chunk lies in the window
+        const int64_t c = kpp_step(L, base, win0, nch, chunk_s, chunk_mode, s, lane);
+        if (c < 0) {
+            base += KPP_STEP;
             continue;
         }
         if (c >= nch) break;
-        if (c >= win0 + WIN) {                     // not a stop, just the window's end
-            base = c;
-            continue;
-        }
-        // Stop chunk c (the first, a binade crossing, a tie, a non-finite value).
-        // With prefix arrays (a predicted crossing): the rows before the crossing
-        // from pa in s's binade, the crossing row by the reference's hardware add,
-        // the rows after it from pb in the next binade, all in parallel. Any rest
-        // (no arrays, a tie, a second crossing): the reference's adds one by one
-        // (:122-125), s uniform in every lane, ~26 cycles per row.
-        KPP_T(1)
+        // Stop chunk c (the first, a binade crossing, a tie, a non-finite value):
+        // through its prefix arrays if it has them, any rest (no arrays, a row
+        // unresolvable in either binade, a third binade) row by row.
         const int64_t r0 = c * KPP_CHUNK;
         const int n = (int)(N - r0 < KPP_CHUNK ? N - r0 : KPP_CHUNK);
         if (lane == 0) {
             chunk_s[c] = s;
             chunk_mode[c] = 1;
         }
-        const KppChunk mc = wm[c - win0];
+        const KppChunk mc = L.wm[c - win0];
         const bool arrays = mc.dual != 0;
-        const int eg = mc.dual - 2048;
-        // lane l holds rows 8l..8l+7 of the prefix arrays in registers; q and the
-        // arrays also go to LDS for the uniform reads; every load is issued
-        // before the first use (clamped indices)
-        constexpr int EPL = KPP_CHUNK / 64;
-        int64_t PA[EPL], PB[EPL];
-        {
-            double qv[EPL];
-#pragma unroll
-            for (int t = 0; t < EPL; t++) {
-                const int i = lane * EPL + t;
-                qv[t] = qbuf[r0 + (i < n ? i : n - 1)];
-            }
-            if (arrays) {
-#pragma unroll
-                for (int t = 0; t < EPL; t++) {
-                    const int i = lane * EPL + t;
-                    PA[t] = pa[r0 + (i < n ? i : n - 1)];
-                    PB[t] = pb[r0 + (i < n ? i : n - 1)];
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < EPL; t++) qs[lane * EPL + t] = qv[t];
-            if (arrays) {
-#pragma unroll
-                for (int t = 0; t < EPL; t++) { pas[lane * EPL + t] = PA[t]; pbs[lane * EPL + t] = PB[t]; }
-            }
-        }
+        int64_t PA[KPP_EPL], PB[KPP_EPL];
+        kpp_stage(L, qbuf + r0, pa + r0, pb + r0, n, arrays, PA, PB, lane);
+        const int i0 = arrays ? kpp_two_binades(L, PA, PB, mc.dual - 2048, n, cum + r0, s, lane) : 0;
+        kpp_tail(L.qs, i0, n, cum + r0, s);
         wave_sync();
-        KPP_T(2)
-        // rows [i0, m) resolved as integers in binade E from the prefix array P
-        // (s exact, in binade E): returns m, the first row that is a tie,
-        // unresolvable or leaves the binade; s advances to row m - 1
-        auto resolve = [&](const int64_t* P, const int64_t (&PR)[EPL], int i0, int E) -> int {
-            const int64_t su = (int64_t)ldexp(s, 52 - E);
-            const int64_t base_p = i0 > 0 ? (P[i0 - 1] & KPP_PMASK) : 0;
-            int lf = EPL;
-#pragma unroll
-            for (int t = 0; t < EPL; t++) {
-                const int i = lane * EPL + t;
-                const int64_t p = PR[t];
-                if (lf == EPL && i >= i0 && i < n &&
-                    (p < 0 || (p & KPP_TIE) || su + ((p & KPP_PMASK) - base_p) >= KPP_TWO53))
-                    lf = t;
-            }
-            const unsigned long long fbits = __ballot(lf < EPL);
-            const int fl = fbits ? __ffsll((long long)fbits) - 1 : 64;
-            const int m = fl < 64 ? fl * EPL + __builtin_amdgcn_readlane(lf, fl) : n;
-            double out[EPL];
-#pragma unroll
-            for (int t = 0; t < EPL; t++) out[t] = ldexp((double)(su + ((PR[t] & KPP_PMASK) - base_p)), E - 52);
-#pragma unroll
-            for (int t = 0; t < EPL; t++) {
-                const int i = lane * EPL + t;
-                if (i >= i0 && i < m) cum[r0 + i] = out[t];
-            }
-            if (m > i0) s = ldexp((double)(su + ((P[m - 1] & KPP_PMASK) - base_p)), E - 52);
-            return m;
-        };
-        int i0 = 0;
-        while (arrays && i0 < n) {
-            if (!(s >= 0x1p-900 && s < 0x1p62)) break;
-            const int E = kpp_binade(s);
-            if (E != eg && E != eg + 1) break;
-            const int64_t* P = E == eg ? pas : pbs;
-            i0 = E == eg ? resolve(pas, PA, i0, E) : resolve(pbs, PB, i0, E);
-            if (i0 >= n || P[i0] < 0) break;         // done, or an unresolvable row: one by one from it
-            s = __dadd_rn(qs[i0], s);               // a tie or crossing row: the reference's add
-            if (lane == 0) cum[r0 + i0] = s;
-            i0++;
-        }
-#if defined(KPP_PROF)
-        npass += n - i0;
-#if defined(KPP_PROF_STOPS)
-        if (lane == 0) printf("KPPSTOP %lld %d %d %d %d %d\n", (long long)c, mc.dual, mc.e, es, (int)s_ok, i0);
-#endif
-#endif
-        // the rest one by one: every lane adds and stores the same value (one
-        // line, no exec toggling), the next 16 values read ahead from LDS with
-        // uniform-address (broadcast) reads
-        constexpr int QB = 16;
-        double qn[QB];
-#pragma unroll
-        for (int t = 0; t < QB; t++) qn[t] = qs[i0 + t < n ? i0 + t : n - 1];
-        int i = i0;
-        for (; i + QB <= n; i += QB) {
-            double qv[QB];
-#pragma unroll
-            for (int t = 0; t < QB; t++) qv[t] = qn[t];
-            if (i + 2 * QB <= n) {
-#pragma unroll
-                for (int t = 0; t < QB; t++) qn[t] = qs[i + QB + t];
-            }
-#pragma unroll
-            for (int t = 0; t < QB; t++) {
-                s = __dadd_rn(qv[t], s);           // the reference's add (0 + q_0 = q_0 for row 0)
-                cum[r0 + i + t] = s;
-            }
-        }
-        for (; i < n; i++) {
-            s = __dadd_rn(qs[i], s);
-            cum[r0 + i] = s;
-        }
-        wave_sync();
-        KPP_T(3)
         base = c + 1;
         nseq++;
     }
-#if defined(KPP_PROF)
-    if (lane == 0) printf("KPPPROF %llu %llu %llu %llu %llu %llu %llu\n", tp[0], tp[1], tp[2], tp[3], tp[4], nseq, npass);
-#endif
     return s;
 }
 
@@ -831,38 +720,38 @@ __device__ __forceinline__ int64_t kpp_search(const double* __restrict__ qbuf, i
     // rows of chunk cs_
     const int64_t r0 = cs_ * KPP_CHUNK;
     const int n = (int)(N - r0 < KPP_CHUNK ? N - r0 : KPP_CHUNK);
-    constexpr int EPL = KPP_CHUNK / 64;
-    double v[EPL];
+    double v[KPP_EPL];
     if (chunk_mode[cs_] != 0) {
 #pragma unroll
-        for (int t = 0; t < EPL; t++) {
-            const int i = lane * EPL + t;
+        for (int t = 0; t < KPP_EPL; t++) {
+            const int i = lane * KPP_EPL + t;
             v[t] = cum[r0 + (i < n ? i : n - 1)];
         }
     } else {
-        const int e = meta[cs_].e;
-        const int64_t su = (int64_t)ldexp(chunk_s[cs_], 52 - e);
-        int64_t r[EPL], own = 0;
+        const int e = meta[cs_].e;          // a mode-0 chunk is clean: every row of class 0
+        const int64_t su = kpp_to_units(chunk_s[cs_], e);
+        int64_t r[KPP_EPL], own = 0;
 #pragma unroll
-        for (int t = 0; t < EPL; t++) {
-            const int i = lane * EPL + t;
-            r[t] = i < n ? kpp_units(qbuf[r0 + i], e) : 0;
+        for (int t = 0; t < KPP_EPL; t++) {
+            const int i = lane * KPP_EPL + t;
+            int cls;
+            r[t] = i < n ? kpp_units(qbuf[r0 + i], e, cls) : 0;
             own += r[t];
         }
         int64_t run = su + wave_incl_scan64(own, lane) - own;
 #pragma unroll
-        for (int t = 0; t < EPL; t++) {
+        for (int t = 0; t < KPP_EPL; t++) {
             run += r[t];
-            v[t] = ldexp((double)run, e - 52);
+            v[t] = kpp_from_units(run, e);
         }
     }
-    int lf = EPL;
+    int lf = KPP_EPL;
 #pragma unroll
-    for (int t = 0; t < EPL; t++)
-        if (lf == EPL && lane * EPL + t < n && v[t] >= rd) lf = t;
-    const unsigned long long b = __ballot(lf < EPL);
+    for (int t = 0; t < KPP_EPL; t++)
+        if (lf == KPP_EPL && lane * KPP_EPL + t < n && v[t] >= rd) lf = t;
+    const unsigned long long b = __ballot(lf < KPP_EPL);
     const int fl = b ? __ffsll((long long)b) - 1 : 63;      // b != 0: the chunk's end reaches rd
-    return r0 + fl * EPL + __builtin_amdgcn_readlane(lf, fl);
+    return r0 + fl * KPP_EPL + __builtin_amdgcn_readlane(lf, fl);
 }
 
 __device__ inline void kpp_walk_stats(unsigned long long* __restrict__ stats, int64_t nch, unsigned long long nseq) {
@@ -875,12 +764,10 @@ __device__ inline void kpp_walk_stats(unsigned long long* __restrict__ stats, in
 // One device: the walk from 0, then (4) the draw (:127-149): rd =
 // uniform_real(0, total) = canon * (total - 0) + 0 and the search (rd <=
 // total; a NaN total from degenerate minima gives rd NaN and row 0).
-__global__ __launch_bounds__(64) void kpp_chain_kernel(const double* __restrict__ qbuf, int64_t N,
-                                                       const KppChunk* __restrict__ meta, int64_t nch,
-                                                       const int64_t* __restrict__ pa, const int64_t* __restrict__ pb,
-                                                       double* chunk_s, int32_t* chunk_mode,
-                                                       double* cum, const double* __restrict__ canon, int it,
-                                                       int32_t* __restrict__ chosen, unsigned long long* __restrict__ stats) {
+__global__ __launch_bounds__(64) void kpp_chain_kernel(
+    const double* __restrict__ qbuf, int64_t N, const KppChunk* __restrict__ meta, int64_t nch,
+    const int64_t* __restrict__ pa, const int64_t* __restrict__ pb, double* chunk_s, int32_t* chunk_mode, double* cum,
+    const double* __restrict__ canon, int it, int32_t* __restrict__ chosen, unsigned long long* __restrict__ stats) {
     unsigned long long nseq = 0;
     const double total = kpp_walk(qbuf, N, meta, nch, pa, pb, chunk_s, chunk_mode, cum, 0.0, nseq);
     __threadfence();                               // this wave's chunk_s / cum stores, visible to its loads
@@ -895,12 +782,10 @@ __global__ __launch_bounds__(64) void kpp_chain_kernel(const double* __restrict_
 // A shard's walk: from s_in (the sum after the earlier shards' rows; with
 // s_in > 0 its first chunk has a binade and takes the integer path like any
 // other) to s_out; the draw waits for the last shard's s_out, the total.
-__global__ __launch_bounds__(64) void kpp_chain_shard_kernel(const double* __restrict__ qbuf, int64_t N,
-                                                             const KppChunk* __restrict__ meta, int64_t nch,
-                                                             const int64_t* __restrict__ pa, const int64_t* __restrict__ pb,
-                                                             double* chunk_s, int32_t* chunk_mode, double* cum,
-                                                             double s_in, KppShardOut* __restrict__ out,
-                                                             unsigned long long* __restrict__ stats) {
+__global__ __launch_bounds__(64) void kpp_chain_shard_kernel(
+    const double* __restrict__ qbuf, int64_t N, const KppChunk* __restrict__ meta, int64_t nch,
+    const int64_t* __restrict__ pa, const int64_t* __restrict__ pb, double* chunk_s, int32_t* chunk_mode, double* cum,
+    double s_in, KppShardOut* __restrict__ out, unsigned long long* __restrict__ stats) {
     unsigned long long nseq = 0;
     const double s = kpp_walk(qbuf, N, meta, nch, pa, pb, chunk_s, chunk_mode, cum, s_in, nseq);
     if (threadIdx.x == 0) out->s_out = s;
@@ -910,11 +795,9 @@ __global__ __launch_bounds__(64) void kpp_chain_shard_kernel(const double* __res
 // A shard's part of the search for the draw rd (formed on the host from the
 // total): its first row whose prefix sum reaches rd, or -1. The shard of
 // global row 0 answers row 0 unless rd > q_0 (:139; a NaN rd as well).
-__global__ __launch_bounds__(64) void kpp_pick_shard_kernel(const double* __restrict__ qbuf, int64_t N,
-                                                            const KppChunk* __restrict__ meta, int64_t nch,
-                                                            const double* chunk_s, const int32_t* chunk_mode,
-                                                            const double* cum, double rd, int owns_row0,
-                                                            KppShardOut* out) {
+__global__ __launch_bounds__(64) void kpp_pick_shard_kernel(
+    const double* __restrict__ qbuf, int64_t N, const KppChunk* __restrict__ meta, int64_t nch, const double* chunk_s,
+    const int32_t* chunk_mode, const double* cum, double rd, int owns_row0, KppShardOut* out) {
     const double total = out->s_out;
     int64_t pick = -1;
     if (owns_row0 && !(rd > qbuf[0])) pick = 0;
@@ -922,15 +805,10 @@ __global__ __launch_bounds__(64) void kpp_pick_shard_kernel(const double* __rest
     if (threadIdx.x == 0) out->pick = pick;
 }
 
-
-// The workspace of one device or one shard (kmeans_pp_ws_bytes(N) bytes):
-// mind[N] f64, cum[N] f64, then per 256-row group sum m^2, per chunk start f64,
-// meta, s_start f64, mode i32, the max word with the shard's host-read values
-// behind it, the per-block maxima, q[N] and the prefix arrays.
+// The workspace's regions as pointers (kpp_layout.h: the map).
 struct KppWs {
     int64_t nch, ngroups;
     unsigned dgrid;
-    size_t out_off;                // of `out` in the workspace
     double *mind, *cum, *gsum, *cstart, *cs, *qbuf;
     KppChunk* meta;
     int32_t* mode;
@@ -938,29 +816,18 @@ struct KppWs {
     KppShardOut* out;
     int64_t *pa, *pb;
 };
-static_assert(8 + sizeof(KppShardOut) <= 64, "the max word's 64 bytes hold the shard's outputs");
-
 static KppWs kpp_carve(void* ws, int64_t N) {
-    KppWs w;
-    w.nch = (N + KPP_CHUNK - 1) / KPP_CHUNK;
-    w.ngroups = (N + KPP_THREADS - 1) / KPP_THREADS;
-    w.dgrid = gsz(N, KPP_THREADS, 4096);
+    const KppLayout l = kpp_layout(N);
     char* p = (char*)ws;
-    w.mind = (double*)p;                 p += sizeof(double) * N;
-    w.cum = (double*)p;                  p += sizeof(double) * N;
-    w.gsum = (double*)p;                 p += sizeof(double) * ((w.ngroups + 1) & ~1ll);   // per 256-row group sum m^2
-    w.cstart = (double*)p;               p += sizeof(double) * w.nch;
-    w.meta = (KppChunk*)p;               p += sizeof(KppChunk) * w.nch;
-    w.cs = (double*)p;                   p += sizeof(double) * w.nch;
-    w.mode = (int32_t*)p;                p += sizeof(int32_t) * ((w.nch + 1) & ~1ll);
-    w.mx = (unsigned long long*)p;
-    w.out = (KppShardOut*)(p + 8);
-    w.out_off = (size_t)(p + 8 - (char*)ws);
-    p += 64;
-    w.bmax = (unsigned long long*)p;     p += 4096 * 8;   // [<= 4096] per-block maxima
-    w.qbuf = (double*)p;                 p += sizeof(double) * N;   // [N] q_m
-    w.pa = (int64_t*)p;                  p += sizeof(int64_t) * N;  // crossing chunks' prefix arrays
-    w.pb = (int64_t*)p;
+    KppWs w;
+    w.nch = l.nch; w.ngroups = l.ngroups; w.dgrid = l.dgrid;
+    w.mind = (double*)(p + l.mind);      w.cum = (double*)(p + l.cum);
+    w.gsum = (double*)(p + l.gsum);      w.cstart = (double*)(p + l.cstart);
+    w.meta = (KppChunk*)(p + l.meta);    w.cs = (double*)(p + l.cs);
+    w.mode = (int32_t*)(p + l.mode);     w.mx = (unsigned long long*)(p + l.mx);
+    w.out = (KppShardOut*)(p + l.out);   w.bmax = (unsigned long long*)(p + l.bmax);
+    w.qbuf = (double*)(p + l.qbuf);      w.pa = (int64_t*)(p + l.pa);
+    w.pb = (int64_t*)(p + l.pb);
     return w;
 }
 
@@ -970,21 +837,13 @@ static KppWs kpp_carve(void* ws, int64_t N) {
 static void kpp_launch_dist(hipStream_t s, Pts X, int64_t N, int d, int metric, const int32_t* chosen, const void* cext,
                             int it, const KppWs& w) {
     const bool vec = d % KPP_DJ == 0 && !X.f64;
-    const dim3 g(w.dgrid), b(KPP_THREADS);
-    const size_t ld32 = (size_t)d * 4, ld64 = (size_t)d * 8;     // the centroid row in LDS
-    const float* cf = (const float*)cext;
-    const double* cd = (const double*)cext;
-    if (X.f64) {
-        if (metric == 0) hipLaunchKernelGGL((kpp_dist_kernel<0, false, double>), g, b, ld64, s, X.d(), N, d, chosen, cd, it, w.mind, w.bmax, w.gsum);
-        else hipLaunchKernelGGL((kpp_dist_kernel<1, false, double>), g, b, ld64, s, X.d(), N, d, chosen, cd, it, w.mind, w.bmax, w.gsum);
-    } else if (metric == 0 && vec)
-        hipLaunchKernelGGL(kpp_dist_reg_kernel, g, b, ld32, s, X.f(), N, d, chosen, cf, it, w.mind, w.bmax, w.gsum);
-    else if (metric == 0)
-        hipLaunchKernelGGL((kpp_dist_kernel<0, false, float>), g, b, ld32, s, X.f(), N, d, chosen, cf, it, w.mind, w.bmax, w.gsum);
-    else if (vec)
-        hipLaunchKernelGGL((kpp_dist_kernel<1, true, float>), g, b, ld32, s, X.f(), N, d, chosen, cf, it, w.mind, w.bmax, w.gsum);
-    else
-        hipLaunchKernelGGL((kpp_dist_kernel<1, false, float>), g, b, ld32, s, X.f(), N, d, chosen, cf, it, w.mind, w.bmax, w.gsum);
+    const auto go = [&](auto kernel, const auto* x) {          // dynamic LDS: the centroid row
+        hipLaunchKernelGGL(kernel, dim3(w.dgrid), dim3(KPP_THREADS), sizeof(*x) * d, s, x, N, d, chosen, (decltype(x))cext, it,
+                           w.mind, w.bmax, w.gsum);
+    };
+    if (X.f64) metric == 0 ? go(kpp_dist_kernel<0, false, double>, X.d()) : go(kpp_dist_kernel<1, false, double>, X.d());
+    else if (metric == 0) vec ? go(kpp_dist_reg_kernel, X.f()) : go(kpp_dist_kernel<0, false, float>, X.f());
+    else vec ? go(kpp_dist_kernel<1, true, float>, X.f()) : go(kpp_dist_kernel<1, false, float>, X.f());
 }
 
 // Runs iterations 1..K-1; chosen[0] and canon[1..K-1] are already on the device.
@@ -999,19 +858,9 @@ int launch_kmeans_pp(hipStream_t s, Pts X, int64_t N, int d, int K, int metric, 
                            w.cstart, w.nch, w.meta, w.pa, w.pb);
         hipLaunchKernelGGL(kpp_chain_kernel, dim3(1), dim3(64), 0, s, w.qbuf, N, w.meta, w.nch, w.pa, w.pb, w.cs, w.mode, w.cum,
                            canon, it, chosen, stats);
-        const int rc = kstatus("kmeanspp.hip");
-        if (rc) return rc;
+        if (const int rc = kstatus("kmeanspp.hip")) return rc;
     }
     return 0;
-}
-
-size_t kmeans_pp_ws_bytes(int64_t N) {
-    const int64_t nch = (N + KPP_CHUNK - 1) / KPP_CHUNK;
-    const int64_t ngroups = (N + KPP_THREADS - 1) / KPP_THREADS;
-    return sizeof(double) * 2 * (size_t)N + sizeof(double) * (size_t)((ngroups + 1) & ~1ll) +
-           (sizeof(double) * 2 + sizeof(KppChunk)) * (size_t)nch +
-           sizeof(int32_t) * (size_t)((nch + 1) & ~1ll) + 64 + 4096 * 8 + sizeof(double) * (size_t)N +
-           2 * sizeof(int64_t) * (size_t)N;
 }
 
 // ------------------------------------------------------------- row shards
@@ -1020,11 +869,7 @@ size_t kmeans_pp_ws_bytes(int64_t N) {
 // shard), with the host between the steps: dist -> (max, sum m^2) of the shard;
 // units with the global max and the approximate sum before the shard; chain
 // from the exact s after the previous shard; pick for the draw. Each step's
-// host-read values lie at kpp_shard_out (ws + kpp_shard_out_offset(n)).
-size_t kpp_shard_out_offset(int64_t n) {
-    return kpp_carve(nullptr, n).out_off;
-}
-
+// host-read values lie in the workspace's KppShardOut (kpp_layout(n).out).
 int launch_kpp_shard_dist(hipStream_t s, Pts X, int64_t n, int d, int metric, const void* crow, int it, void* ws) {
     const KppWs w = kpp_carve(ws, n);
     kpp_launch_dist(s, X, n, d, metric, nullptr, crow, it, w);
