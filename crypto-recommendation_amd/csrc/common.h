@@ -103,7 +103,10 @@ enum Stat {
     STAT_LSHPC_KEPT = 14,    // ... candidates the screen kept for the exact pass
     STAT_LSHPC_SEEN = 15,    // ... candidates it saw
     STAT_PAIR_ROWS = 16,     // rows of STAT_ASSIGN_AMBIG the refinement named both candidates of and decided itself
-    STAT_COUNT = 17
+    STAT_NEAREST_SETTLED = 17, // lshkm_min_vector_dist: queries the MFMA screen settled
+    STAT_NEAREST_SCAN = 18,  // ... queries sent to the exact scan over all rows (poison, overflow; or the whole call)
+    STAT_NEAREST_EXACT = 19, // ... exact distances the settle computed (the lists form's too)
+    STAT_COUNT = 20
 };
 
 constexpr int WAVE = 64;

@@ -108,6 +108,9 @@ struct lshkm_ctx_s {
     // image, the users' image, the chunk, the handed-back list, the lists path's
     // users and its two lists (the cube's: its list, and its masks and sizes)
     lshkm::Buf ws_lshpc[7];
+    // lshkm_min_vector_dist (nearest_layout.h): the rows' image, the queries'
+    // image, the call's state
+    lshkm::Buf ws_nearest[3];
     uint64_t ws_epoch = 0;       // bumped by every user of the ws[] slots (api_index.cpp reserve)
     // optional HIP-event timing of the dominant kernel launch (lshkm_last_kernel_ms)
     bool timing = false;

@@ -470,6 +470,52 @@ int launch_lshpc_scatter(hipStream_t s, const int32_t* list, int64_t m, int P, c
                          const int32_t* gcnt, const int64_t* eptr, int32_t* out_idx, double* out_sim, int32_t* out_cnt,
                          int64_t* ncand);
 
+// lshkm_min_vector_dist (nearest.hip; nearest_layout.h states the routing rule
+// and the workspace). One side's f32 image: x^ [n][dp], a (|x^|^2 euclidean,
+// 1 / |x^| cosine; negative: poison), the bound's conversion term.
+struct NearestSide {
+    const float* xh;
+    const float* a;
+    const float* rel;
+    int64_t n;
+};
+// The screen's state per query: the smallest hi's key, the count of rows with
+// lo <= it, the first cap of them.
+struct NearestKept {
+    uint32_t* minkey;
+    int32_t *cnt, *krow;
+    int64_t seg_rows;
+    int cap;
+};
+// pois / npois (rows; NULL for the queries): the poison rows' list and count.
+int launch_nearest_prep(hipStream_t s, Pts X, int64_t n, int d, int dp, int metric, const NearestSide& out, int32_t* pois,
+                        unsigned int* npois);
+// Both passes over a grid of tiles x segs blocks.
+int launch_nearest_screen(hipStream_t s, int dp, int metric, const NearestSide& rows, const NearestSide& qs,
+                          const NearestKept& kept, int64_t tiles, int segs);
+// ptr != NULL: the lists form over idx[ptr[q] .. ptr[q+1]) (first in list wins
+// ties); else the kept rows and the poison rows of the queries the screen did
+// not flag. stats 19 += the distances computed.
+int launch_nearest_settle(hipStream_t s, Pts X, Pts Q, int64_t nq, int d, int metric, const int64_t* ptr,
+                          const int32_t* idx, const NearestKept& kept, const float* qa, const int32_t* pois,
+                          const unsigned int* npois, const double* xn2, const double* qn2, double* dist, int32_t* row,
+                          unsigned long long* stats);
+// list += the flagged queries (a poison query, more than cap rows); stats 17 / 18.
+int launch_nearest_collect(hipStream_t s, const NearestKept& kept, const float* qa, int64_t nq, int32_t* list,
+                           unsigned int* count, unsigned long long* stats);
+// All N rows for the queries of list[0 .. *count) (list NULL: all nq, stats 18 += nq).
+int launch_nearest_scan(hipStream_t s, Pts X, int64_t N, Pts Q, int64_t nq, int d, int metric, const int32_t* list,
+                        const unsigned int* count, const double* xn2, const double* qn2, double* dist, int32_t* row,
+                        unsigned long long* stats);
+// xn2 / qn2 of the two launchers above: the rows' / queries' sequential sums of
+// squares (launch_rc_norms), read for cosine on fp64 values only.
+bool nearest_needs_norms(Pts X, int metric);
+int launch_nearest_norms(hipStream_t s, Pts X, int64_t n, int d, int metric, double* xa);
+int launch_nearest_empty(hipStream_t s, int64_t nq, double* dist, int32_t* row);
+// *bad = 1 on a ptr that does not start at 0 or decreases, or an idx outside [0, N).
+int launch_nearest_check(hipStream_t s, const int64_t* ptr, int64_t nq, const int32_t* idx, int64_t total, int64_t N,
+                         unsigned int* bad);
+
 // User vectors from scored tweets (uservec.hip). The visit list and the tweet
 // table of one lshkm_user_sums call: visit v = tweet tw[v] onto group grp[v]
 // (-1: skipped), tweet t's score and its coins ci_idx[ci_ptr[t] .. ci_ptr[t+1]).

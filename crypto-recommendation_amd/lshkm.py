@@ -26,6 +26,7 @@ STAT_KM_SEQ = 9
 STAT_PAM_SCREENED, STAT_PAM_EXACT = 10, 11
 STAT_LSHPC_SETTLED, STAT_LSHPC_LISTS, STAT_LSHPC_KEPT, STAT_LSHPC_SEEN = 12, 13, 14, 15
 STAT_PAIR_ROWS = 16
+STAT_NEAREST_SETTLED, STAT_NEAREST_SCAN, STAT_NEAREST_EXACT = 17, 18, 19
 _METRIC = {"euclidean": EUCLIDEAN, "cosine": COSINE, EUCLIDEAN: EUCLIDEAN, COSINE: COSINE}
 DIST_CERTIFIED, DIST_EXACT = 0, 1
 _DIST = {"certified": DIST_CERTIFIED, "default": DIST_CERTIFIED, "exact": DIST_EXACT,
@@ -149,6 +150,8 @@ def lib():
             "lshkm_p_closest": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, i32, vp, vp, vp]),
             "lshkm_lsh_p_closest": (i32, [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp]),
             "lshkm_cube_p_closest": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
+            "lshkm_min_vector_dist": (i32, [vp, vp, i64, i32, vp, i64, i32, vp, vp]),
+            "lshkm_min_vector_dist_lists": (i32, [vp, vp, i64, i32, vp, i64, i32, vp, vp, vp, vp]),
             "lshkm_top_n_recom": (i32, [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i32, i32, vp]),
             "lshkm_cluster_top_n": (i32, [vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, i32, vp]),
             "lshkm_cluster_sims": (i32, [vp, vp, i64, i32, vp, vp, i32, vp, i64, vp, vp, vp, vp, i64,
@@ -1049,6 +1052,69 @@ def cube_recommend(ctx, cube, X, x_mean, U, u_mean, unk_ptr, unk_idx, probes, P,
     does; cnt == 0 marks the users to skip (no neighbours)."""
     idx, sim, cnt = cube_p_closest(ctx, cube, X, U, probes, P)
     return top_n_recom(ctx, X, x_mean, u_mean, unk_ptr, unk_idx, idx, sim, cnt, n_top), cnt
+
+
+# ---------------------------------------------------------- exact nearest row
+def min_vector_dist(ctx, X, Q, metric, rows=True):
+    """min_vector_euclidean_dist / min_vector_cosine_dist (utils.hpp:107-140)
+    for every query of Q over the rows X (lshkm_min_vector_dist): the exact
+    nearest row. X [N][d], Q [nq][d] device tensors of one dtype (float32 or
+    float64). Returns (dist float64 [nq], row int32 [nq]); with rows=False the
+    distances alone. N == 0 gives 0.0 and -1."""
+    torch = ctx.torch
+    assert X.dtype == Q.dtype, "X and Q share the element type"
+    N, nq, d = X.shape[0], Q.shape[0], Q.shape[1]
+    dist = ctx.empty((nq,), torch.float64)
+    row = ctx.empty((nq,), torch.int32) if rows else None
+    _ck(_fn("lshkm_min_vector_dist", Q)(ctx.h, _t_ptr(X) if N else None, N, d, _t_ptr(Q), nq, _METRIC[metric],
+                                        _t_ptr(dist), _t_ptr(row)))
+    return (dist, row) if rows else dist
+
+
+def min_vector_dist_lists(ctx, X, Q, metric, ptr, idx):
+    """The same over each query's own candidate rows X[idx[ptr[q] .. ptr[q+1])]
+    in list order (lshkm_min_vector_dist_lists): the reference's helper on a
+    combined bucket. ptr [nq+1] int64 / idx int32 device tensors (LSH.query /
+    Cube.query with device=True). Returns (dist float64 [nq], row int32 [nq]);
+    an empty list gives 0.0 and -1, the first in a list wins ties."""
+    torch = ctx.torch
+    assert X.dtype == Q.dtype, "X and Q share the element type"
+    N, nq, d = X.shape[0], Q.shape[0], Q.shape[1]
+    dist = ctx.empty((nq,), torch.float64)
+    row = ctx.empty((nq,), torch.int32)
+    _ck(_fn("lshkm_min_vector_dist_lists", Q)(ctx.h, _t_ptr(X) if N else None, N, d, _t_ptr(Q), nq, _METRIC[metric],
+                                              _t_ptr(ptr), _t_ptr(idx) if idx.numel() else None, _t_ptr(dist),
+                                              _t_ptr(row)))
+    return dist, row
+
+
+def index_quality(ctx, index, X, Q, metric, probes=None, filtered=True):
+    """How good the answers of a built LSH or Cube over X are for the queries
+    Q: index.query(..., device=True), then the bucket's nearest row
+    (min_vector_dist_lists), then the true nearest row (min_vector_dist).
+    Returns a dict: found (share of queries with a non-empty bucket),
+    recall_at_1 (share whose bucket minimum equals the true minimum distance),
+    ratio_mean / ratio_max (bucket distance over true distance, over the found
+    queries whose true distance is > 0; nan if there is none), and the four
+    per-query device tensors bucket_dist, bucket_row, true_dist, true_row."""
+    torch = ctx.torch
+    if isinstance(index, Cube):
+        ptr, idx = index.query(Q, probes, device=True)
+    else:
+        ptr, idx = index.query(Q, filtered=filtered, device=True)
+    bd, br = min_vector_dist_lists(ctx, X, Q, metric, ptr, idx)
+    td, tr = min_vector_dist(ctx, X, Q, metric)
+    nq = Q.shape[0]
+    has = br >= 0
+    hit = has & (bd == td)
+    pos = has & (td > 0)
+    ratio = bd[pos] / td[pos]
+    nan = float("nan")
+    return {"found": float(has.sum().item()) / nq if nq else nan,
+            "recall_at_1": float(hit.sum().item()) / nq if nq else nan,
+            "ratio_mean": float(ratio.mean().item()) if ratio.numel() else nan,
+            "ratio_max": float(ratio.max().item()) if ratio.numel() else nan,
+            "bucket_dist": bd, "bucket_row": br, "true_dist": td, "true_row": tr}
 
 
 def cluster_top_n(ctx, X, x_mean, crow, crows, U, u_mean, ucl, unk_ptr, unk_idx, n_top):

@@ -140,7 +140,12 @@ int lshkm_memcpy_d2h(lshkm_ctx ctx, void* dst_host, const void* src_dev, int64_t
  * 14 = ... candidates the screen kept for the exact pass,
  * 15 = ... candidates the screen saw,
  * 16 = of counter 1's points, those the fused pass's refinement named the only
- *      two possible nearest centroids of (decided between the two alone). */
+ *      two possible nearest centroids of (decided between the two alone),
+ * 17 = lshkm_min_vector_dist: queries the MFMA screen settled,
+ * 18 = ... queries sent to the exact scan over all rows (a poison query, a
+ *      kept-list overflow; every query of a call the screen does not take),
+ * 19 = ... exact distances the settle computed (kept and poison rows; the lists
+ *      form's list entries). */
 int lshkm_get_stat(lshkm_ctx ctx, int which, int64_t* value_host);
 int lshkm_reset_stats(lshkm_ctx ctx);
 /* HIP-event timing of the dominant kernel launch (the fused hash+assign kernel)
@@ -572,6 +577,46 @@ int lshkm_lsh_p_closest(lshkm_lsh lsh, const double* X_dev, const double* U_dev,
  * Returns after its workspace is free for the next call. */
 int lshkm_cube_p_closest(lshkm_cube cube, const double* X_dev, const double* U_dev, int64_t nq, int probes, int P,
                          int32_t* out_idx_dev, double* out_sim_dev, int32_t* out_cnt_dev, int64_t* ncand_dev);
+/* min_vector_euclidean_dist / min_vector_cosine_dist (lib/utils.hpp:107-140)
+ * for nq queries at once: the exact nearest row of every query. dist_dev[q] is
+ * bit for bit what the reference's helper returns for query Q[q] over the vector
+ * of rows X: query.euclideanDistance(row) / query.cosineDistance(row)
+ * (cust_vector.hpp:124-155: glibc's pow(x, 2) per square, the x87 inner product,
+ * 1 - double(ip / denom)), the minimum taken by the reference's loop: start from
+ * row 0, replace only on strict <. row_dev[q] (or NULL) is the row that holds it
+ * (ours: the reference returns the value alone): of equal minima the lowest row.
+ * If row 0's distance is a NaN the result is that NaN (x86's bits) and row 0,
+ * since nothing is < NaN; a NaN at a later row is never taken. inf - inf, zero
+ * rows under cosine and 1e+-200 entries are reproduced, not refused. N == 0:
+ * dist = 0.0, row = -1 (utils.hpp:109-110); nq == 0 does no device work.
+ * X_dev [N][d] and Q_dev [nq][d] share the element type (fp32, or fp64 with
+ * _f64). The distances are the exact chain in both distance modes of the
+ * context: one value per query leaves LSHKM_DIST_CERTIFIED nothing to save.
+ * d <= 128 goes through an f32 MFMA screen over (query tile x row segment)
+ * blocks with a rigorous bound that leaves only the rows that can
+ * still hold the minimum to the exact chain; d > 128, and every query the screen
+ * cannot decide (a poison query, more kept rows than the capacity), takes the
+ * exact scan over all rows. N < 2^31, nq < 2^31, d >= 1, metric euclidean or
+ * cosine, dist_dev not NULL: else LSHKM_ERR_ARG, before any device work.
+ * Returns after its workspace is free for the next call. */
+int lshkm_min_vector_dist(lshkm_ctx ctx, const float* X_dev, int64_t N, int d, const float* Q_dev, int64_t nq,
+                          int metric, double* dist_dev /*[nq]*/, int32_t* row_dev /*[nq] or NULL*/);
+int lshkm_min_vector_dist_f64(lshkm_ctx ctx, const double* X_dev, int64_t N, int d, const double* Q_dev, int64_t nq,
+                              int metric, double* dist_dev, int32_t* row_dev);
+/* The same function over each query's own candidate vector
+ * X[cand_idx_dev[cand_ptr_dev[q] .. cand_ptr_dev[q+1])], in list order: the
+ * reference's helper applied to a combined bucket (the LSH / hypercube nearest
+ * neighbour; lshkm_lsh_query's and lshkm_cube_query's CSR). Of equal minima the
+ * first in the list wins; the NaN rule applies to the list's first element; an
+ * empty list gives 0.0 and -1. row_dev[q] is the dataset row (cand_idx's value).
+ * A cand_ptr that does not start at 0 or decreases, or an index outside [0, N),
+ * is LSHKM_ERR_ARG (checked on the device before anything is written). */
+int lshkm_min_vector_dist_lists(lshkm_ctx ctx, const float* X_dev, int64_t N, int d, const float* Q_dev, int64_t nq,
+                                int metric, const int64_t* cand_ptr_dev /*[nq+1]*/, const int32_t* cand_idx_dev,
+                                double* dist_dev, int32_t* row_dev);
+int lshkm_min_vector_dist_lists_f64(lshkm_ctx ctx, const double* X_dev, int64_t N, int d, const double* Q_dev,
+                                    int64_t nq, int metric, const int64_t* cand_ptr_dev, const int32_t* cand_idx_dev,
+                                    double* dist_dev, int32_t* row_dev);
 /* get_top_N_recom (crypto_rec.hpp:305-325) over lshkm_p_closest's lists:
  * predicted scores of each user's unknown indexes (get_predicted_user_sim,
  * :280-302; unk_* = CSR of the ascending unknown indexes, std::set order),

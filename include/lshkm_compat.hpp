@@ -21,6 +21,7 @@
  *   rand_selection          lib/clustering_phases/initialization.hpp:39-69
  *   get_P_closest           lib/crypto_rec.hpp:213-231
  *   get_top_N_recom (both overloads)  lib/crypto_rec.hpp:309-345
+ *   min_vector_euclidean_dist, min_vector_cosine_dist  lib/utils.hpp:107-140
  *
  * Same signatures, same return values and the same ownership as the
  * reference: the hashtables are real CustHashtable objects (the caller deletes
@@ -575,6 +576,43 @@ std::vector<CustVector<T>*> rand_selection(std::vector<CustVector<T>>& input_vec
 template <typename T>
 std::vector<CustVector<T>*> rand_selection(std::vector<CustVector<T>>& input_vectors, int cluster_num) {
     return rand_selection(input_vectors, cluster_num, clock_seed());
+}
+
+// ------------------------------------------------------ brute-force helpers
+// min_vector_euclidean_dist / min_vector_cosine_dist (utils.hpp:107-140): the
+// smallest distance from the query to the vectors (0 for none), one
+// lshkm_min_vector_dist call of one query. fp64 vectors (the reference's other
+// instantiations do their arithmetic in the narrower type). These two are
+// checked for compilation only: oracle/compat_check.cpp does not call them;
+// tests/test_gpu_nearest.py checks the C entry point they marshal to against
+// the reference's own results.
+template <typename q_type, typename dim_type>
+double min_vector_dist(CustVector<q_type>* queryVector, std::vector<CustVector<dim_type>>* vectors, int metric) {
+    static_assert(std::is_same<q_type, double>::value && std::is_same<dim_type, double>::value,
+                  "lshkm_compat: min_vector_*_dist takes fp64 vectors");
+    if (vectors->size() == 0) return 0;
+    const size_t d = queryVector->getDimensions()->size();
+    for (CustVector<dim_type>& v : *vectors) dims_of(v, d);
+    std::vector<double> X(vectors->size() * d);
+    for (size_t i = 0; i < vectors->size(); i++)
+        for (size_t j = 0; j < d; j++) X[i * d + j] = (*(*vectors)[i].getDimensions())[j];
+    const DevMem Xd = upload(X.data(), X.size()), Qd = upload(queryVector->getDimensions()->data(), d);
+    DevMem out(sizeof(double));
+    check(lshkm_min_vector_dist_f64(context(), Xd.as<double>(), (int64_t)vectors->size(), (int)d, Qd.as<double>(), 1,
+                                    metric, out.as<double>(), nullptr));
+    double dist = 0;
+    download(&dist, out, 1);
+    return dist;
+}
+
+template <typename q_type, typename dim_type>
+double min_vector_euclidean_dist(CustVector<q_type>* queryVector, std::vector<CustVector<dim_type>>* vectors) {
+    return min_vector_dist(queryVector, vectors, LSHKM_METRIC_EUCLIDEAN);
+}
+
+template <typename q_type, typename dim_type>
+double min_vector_cosine_dist(CustVector<q_type>* queryVector, std::vector<CustVector<dim_type>>* vectors) {
+    return min_vector_dist(queryVector, vectors, LSHKM_METRIC_COSINE);
 }
 
 // ------------------------------------------------------------ recommendation

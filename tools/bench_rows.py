@@ -6,7 +6,7 @@ syncs (host launch and sync latency included) -- next to the CPU restatement (or
 thread, OMP_NUM_THREADS=1, kind "port") on a bounded sample of the same
 workload, scaled to the row's unit. Prints one JSON line per row.
 
-    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64,cv,lshpc,cubepc] [--no-cpu]
+    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64,cv,lshpc,cubepc,nearest] [--no-cpu]
     python tools/bench_rows.py --rows main_program --main-dir DIR [--main-ref-seconds S]
 """
 import argparse
@@ -138,6 +138,8 @@ def main():
     ap.add_argument("--cv-sizes", default="20000,1000000", help="user counts of the cv row")
     ap.add_argument("--lshpc-sizes", default="20000,200000", help="user counts of the lshpc row")
     ap.add_argument("--pam-shapes", default="100000x16,1000000x256", help="NxK list of the pam row (d = 128)")
+    ap.add_argument("--nearest-part", default="all", choices=["all", "new", "lloyd"], help="what the nearest row measures")
+    ap.add_argument("--nearest-lloyd-n", type=int, default=0, help="nearest row: rows of the Lloyd route (0: all)")
     ap.add_argument("--main-dir", default="", help="main_program row: the directory gen_main_golden --time wrote")
     ap.add_argument("--main-ref-seconds", type=float, default=0.0, help="main_program row: the reference's seconds")
     a = ap.parse_args()
@@ -562,6 +564,71 @@ def main():
                 "note": "cube.query + p_closest against lshkm_cube_p_closest on the same handle; HIP events, "
                         "median of 10 after 3 warm-ups; stats per call"}), flush=True)
             del W, Q, cube, out
+
+    if "nearest" in rows:    # min_vector_*_dist (utils.hpp:107-140) for all queries: lshkm_min_vector_dist
+        # --nearest-part new: the call, its counters and the CPU port; lloyd: the only route without it,
+        # lshkm_lloyd_assign (exact mode) with the rows as fp64 centroids, over the first --nearest-lloyd-n rows
+        shapes = [("grid fp32", 1_000_000, 128, 4096, "euclidean"), ("grid fp32", 1_000_000, 128, 4096, "cosine"),
+                  ("cv_users fp64", 200_000, 20, 20_000, "cosine")]
+        S = (lshkm.STAT_NEAREST_SETTLED, lshkm.STAT_NEAREST_SCAN, lshkm.STAT_NEAREST_EXACT)
+        for kind, N, d, nq, metric in shapes:
+            if kind == "grid fp32":
+                X, Q = ctx.synth(0x5EED + 21, N, d), ctx.synth(0x5EED + 22, nq, d)
+            else:
+                X = torch.from_numpy(cv_users(N, d)[0]).to(ctx.dev)
+                Q = torch.from_numpy(cv_users(nq, d, seed=0xBE7C5)[0]).to(ctx.dev)
+            line = {"row": "nearest", "rows": kind, "N": N, "d": d, "nq": nq, "metric": metric}
+            if a.nearest_part in ("new", "all"):
+                out = {}
+
+                def call():
+                    out["new"] = lshkm.min_vector_dist(ctx, X, Q, metric)
+                ctx.reset_stats()
+                t_new = event_ms(call, warm=2, reps=5)
+                st = [ctx.stat(i) // 7 for i in S]
+                line.update({"min_vector_dist_ms": {"median": t_new[0], "min": t_new[1], "max": t_new[2]},
+                             "pairs_per_s": N * nq / (t_new[0] / 1e3), "stat_settled": st[0], "stat_scan": st[1],
+                             "stat_exact": st[2], "exact_per_query": st[2] / nq})
+                if cpu:
+                    m = 256
+                    Xh, Qh = X.cpu().numpy(), Q[:m].cpu().numpy()
+                    t0 = time.perf_counter()
+                    wa, wd = oracle.lloyd_assign(Qh, Xh, metric)
+                    tc = time.perf_counter() - t0
+                    line.update({"cpu_port": {"queries": m, "seconds": tc, "cores": int(os.environ["OMP_NUM_THREADS"]),
+                                              "pairs_per_s": N * m / tc},
+                                 "gpu_over_cpu": (N * nq / (t_new[0] / 1e3)) / (N * m / tc),
+                                 "identical_to_port": bool(np.array_equal(out["new"][0][:m].cpu().numpy().view(np.uint64),
+                                                                          wd.view(np.uint64)) and
+                                                           np.array_equal(out["new"][1][:m].cpu().numpy(), wa))})
+            if a.nearest_part in ("lloyd", "all"):
+                Nl = min(N, a.nearest_lloyd_n or N)
+                Xl = X[:Nl]
+                Cc = Xl.double()
+                ctx.set_dist_mode("exact")
+                try:
+                    ctx.reset_stats()
+                    got = {}
+
+                    def lloyd():
+                        got["a"], got["d"] = lshkm.lloyd_assign(ctx, Q, Cc, metric)
+                    t_l = event_ms(lloyd, warm=1, reps=3)
+                    amb = ctx.stat(lshkm.STAT_ASSIGN_AMBIG) // 4
+                finally:
+                    ctx.set_dist_mode("certified")
+                t_s = event_ms(lambda: got.update(n=lshkm.min_vector_dist(ctx, Xl, Q, metric)), warm=1, reps=3)
+                line.update({"lloyd_route": {"N": Nl, "ms": {"median": t_l[0], "min": t_l[1], "max": t_l[2]},
+                                             "queries_to_its_exact_pass": amb,
+                                             "min_vector_dist_ms_same_N": {"median": t_s[0], "min": t_s[1], "max": t_s[2]},
+                                             "speedup_median": t_l[0] / t_s[0],
+                                             "identical": bool(torch.equal(got["d"].view(torch.int64),
+                                                                           got["n"][0].view(torch.int64)) and
+                                                               torch.equal(got["a"], got["n"][1]))}})
+                del Cc
+            line["note"] = ("HIP events around single calls, median / min / max after warm-ups (5 reps the call, 3 the "
+                            "Lloyd route); stats per call; cpu_port: oracle.lloyd_assign over 256 of the queries")
+            print(json.dumps(line), flush=True)
+            del X, Q
 
     if "main_program" in rows:   # the whole program (main.cpp:36-390) on the files of gen_main_golden --time FACTOR DIR
         sys.path.insert(0, os.path.join(ROOT, "crypto-recommendation_amd"))
