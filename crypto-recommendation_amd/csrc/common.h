@@ -106,7 +106,10 @@ enum Stat {
     STAT_NEAREST_SETTLED = 17, // lshkm_min_vector_dist: queries the MFMA screen settled
     STAT_NEAREST_SCAN = 18,  // ... queries sent to the exact scan over all rows (poison, overflow; or the whole call)
     STAT_NEAREST_EXACT = 19, // ... exact distances the settle computed (the lists form's too)
-    STAT_COUNT = 20
+    STAT_KNN_SETTLED = 20,   // lshkm_knn: queries the MFMA screen settled
+    STAT_KNN_SCAN = 21,      // ... queries sent to the exact scan over all rows (poison, no threshold, overflow; or the whole call)
+    STAT_KNN_EXACT = 22,     // ... exact distances the settle computed (the lists form's too)
+    STAT_COUNT = 23
 };
 
 constexpr int WAVE = 64;

@@ -111,6 +111,8 @@ struct lshkm_ctx_s {
     // lshkm_min_vector_dist (nearest_layout.h): the rows' image, the queries'
     // image, the call's state
     lshkm::Buf ws_nearest[3];
+    // lshkm_knn (knn_layout.h): the call's state; its images are ws_nearest's
+    lshkm::Buf ws_knn;
     uint64_t ws_epoch = 0;       // bumped by every user of the ws[] slots (api_index.cpp reserve)
     // optional HIP-event timing of the dominant kernel launch (lshkm_last_kernel_ms)
     bool timing = false;

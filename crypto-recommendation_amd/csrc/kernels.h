@@ -516,6 +516,35 @@ int launch_nearest_empty(hipStream_t s, int64_t nq, double* dist, int32_t* row);
 int launch_nearest_check(hipStream_t s, const int64_t* ptr, int64_t nq, const int32_t* idx, int64_t total, int64_t N,
                          unsigned int* bad);
 
+// lshkm_knn (knn.hip; knn_layout.h states the routing rule and the workspace).
+// The screen's state per query: its (query, group) keys, the k-th smallest of
+// them, the count of rows with lo <= it, the first cap of them. The images,
+// the prep, the norms and the lists check are lshkm_min_vector_dist's.
+struct KnnKept {
+    uint32_t *gkey, *tau;
+    int32_t *cnt, *krow;
+    int64_t seg_rows;
+    int groups, grp_shift, cap, k;
+};
+// Pass 1, the select and pass 2 over a grid of tiles x segs blocks.
+int launch_knn_screen(hipStream_t s, int dp, int metric, const NearestSide& rows, const NearestSide& qs,
+                      const KnnKept& kept, int64_t tiles, int segs);
+// ptr != NULL: the lists form over idx[ptr[q] .. ptr[q+1]) (key = the position);
+// else the kept rows and the poison rows of the queries the screen did not
+// hand over. row / dist [nq][k], cnt [nq] or NULL. stats 22 += the distances computed.
+int launch_knn_settle(hipStream_t s, Pts X, Pts Q, int64_t nq, int d, int metric, int k, const int64_t* ptr,
+                      const int32_t* idx, const KnnKept& kept, const float* qa, const int32_t* pois,
+                      const unsigned int* npois, const double* xn2, const double* qn2, int32_t* row, double* dist,
+                      int32_t* cnt, unsigned long long* stats);
+// list += the handed queries (a poison query, no threshold, more than cap rows); stats 20 / 21.
+int launch_knn_collect(hipStream_t s, const KnnKept& kept, const float* qa, int64_t nq, int32_t* list,
+                       unsigned int* count, unsigned long long* stats);
+// All N rows for the queries of list[0 .. *count) (list NULL: all nq, stats 21 += nq).
+int launch_knn_scan(hipStream_t s, Pts X, int64_t N, Pts Q, int64_t nq, int d, int metric, int k, const int32_t* list,
+                    const unsigned int* count, const double* xn2, const double* qn2, int32_t* row, double* dist,
+                    int32_t* cnt, unsigned long long* stats);
+int launch_knn_empty(hipStream_t s, int64_t nq, int k, int32_t* row, double* dist, int32_t* cnt);
+
 // User vectors from scored tweets (uservec.hip). The visit list and the tweet
 // table of one lshkm_user_sums call: visit v = tweet tw[v] onto group grp[v]
 // (-1: skipped), tweet t's score and its coins ci_idx[ci_ptr[t] .. ci_ptr[t+1]).

@@ -27,6 +27,8 @@ STAT_PAM_SCREENED, STAT_PAM_EXACT = 10, 11
 STAT_LSHPC_SETTLED, STAT_LSHPC_LISTS, STAT_LSHPC_KEPT, STAT_LSHPC_SEEN = 12, 13, 14, 15
 STAT_PAIR_ROWS = 16
 STAT_NEAREST_SETTLED, STAT_NEAREST_SCAN, STAT_NEAREST_EXACT = 17, 18, 19
+STAT_KNN_SETTLED, STAT_KNN_SCAN, STAT_KNN_EXACT = 20, 21, 22
+KNN_KMAX = 64                   # LSHKM_KNN_KMAX (include/lshkm.h)
 _METRIC = {"euclidean": EUCLIDEAN, "cosine": COSINE, EUCLIDEAN: EUCLIDEAN, COSINE: COSINE}
 DIST_CERTIFIED, DIST_EXACT = 0, 1
 _DIST = {"certified": DIST_CERTIFIED, "default": DIST_CERTIFIED, "exact": DIST_EXACT,
@@ -152,6 +154,8 @@ def lib():
             "lshkm_cube_p_closest": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
             "lshkm_min_vector_dist": (i32, [vp, vp, i64, i32, vp, i64, i32, vp, vp]),
             "lshkm_min_vector_dist_lists": (i32, [vp, vp, i64, i32, vp, i64, i32, vp, vp, vp, vp]),
+            "lshkm_knn": (i32, [vp, vp, i64, i32, vp, i64, i32, i32, vp, vp, vp]),
+            "lshkm_knn_lists": (i32, [vp, vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
             "lshkm_top_n_recom": (i32, [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i32, i32, vp]),
             "lshkm_cluster_top_n": (i32, [vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, i32, vp]),
             "lshkm_cluster_sims": (i32, [vp, vp, i64, i32, vp, vp, i32, vp, i64, vp, vp, vp, vp, i64,
@@ -1088,7 +1092,57 @@ def min_vector_dist_lists(ctx, X, Q, metric, ptr, idx):
     return dist, row
 
 
-def index_quality(ctx, index, X, Q, metric, probes=None, filtered=True):
+def knn(ctx, X, Q, k, metric):
+    """The k exact nearest rows of every query of Q over the rows X (lshkm_knn):
+    min_vector_dist's distances, ordered by (distance, row), NaN distances
+    last. X [N][d], Q [nq][d] device tensors of one dtype (float32 or float64),
+    1 <= k <= KNN_KMAX. Returns (rows int32 [nq][k], dist float64 [nq][k], cnt
+    int32 [nq]): cnt = min(k, N), the slots past it hold -1 and 0.0."""
+    torch = ctx.torch
+    assert X.dtype == Q.dtype, "X and Q share the element type"
+    N, nq, d = X.shape[0], Q.shape[0], Q.shape[1]
+    kk = max(int(k), 0)
+    rows = ctx.empty((nq, kk), torch.int32)
+    dist = ctx.empty((nq, kk), torch.float64)
+    cnt = ctx.empty((nq,), torch.int32)
+    _ck(_fn("lshkm_knn", Q)(ctx.h, _t_ptr(X) if N else None, N, d, _t_ptr(Q), nq, _METRIC[metric], int(k),
+                            _t_ptr(rows), _t_ptr(dist), _t_ptr(cnt)))
+    return rows, dist, cnt
+
+
+def knn_lists(ctx, X, Q, k, metric, ptr, idx):
+    """The same over each query's own candidate rows X[idx[ptr[q] .. ptr[q+1])]
+    (lshkm_knn_lists): ties go to the earlier position in the list, cnt =
+    min(k, the list's length), rows holds dataset rows. ptr [nq+1] int64 / idx
+    int32 device tensors (LSH.query / Cube.query with device=True)."""
+    torch = ctx.torch
+    assert X.dtype == Q.dtype, "X and Q share the element type"
+    N, nq, d = X.shape[0], Q.shape[0], Q.shape[1]
+    kk = max(int(k), 0)
+    rows = ctx.empty((nq, kk), torch.int32)
+    dist = ctx.empty((nq, kk), torch.float64)
+    cnt = ctx.empty((nq,), torch.int32)
+    _ck(_fn("lshkm_knn_lists", Q)(ctx.h, _t_ptr(X) if N else None, N, d, _t_ptr(Q), nq, _METRIC[metric], int(k),
+                                  _t_ptr(ptr), _t_ptr(idx) if idx.numel() else None, _t_ptr(rows), _t_ptr(dist),
+                                  _t_ptr(cnt)))
+    return rows, dist, cnt
+
+
+def recall_at_k(ctx, X, Q, metric, ptr, idx, k):
+    """Mean over the queries of |exact k nearest rows ∩ the lists' k nearest
+    rows| / min(k, N); a query with an empty list counts as 0."""
+    N, nq = X.shape[0], Q.shape[0]
+    if nq == 0 or N == 0:
+        return float("nan")
+    tr, _, tc = knn(ctx, X, Q, k, metric)
+    br, _, bc = knn_lists(ctx, X, Q, k, metric, ptr, idx)
+    # an exact row counts once however often the list holds it
+    same = (tr[:, :, None] == br[:, None, :]) & (tr[:, :, None] >= 0)
+    hits = same.any(dim=2).sum(dim=1).double()
+    return float((hits / float(min(int(k), N))).mean().item())
+
+
+def index_quality(ctx, index, X, Q, metric, probes=None, filtered=True, k=None):
     """How good the answers of a built LSH or Cube over X are for the queries
     Q: index.query(..., device=True), then the bucket's nearest row
     (min_vector_dist_lists), then the true nearest row (min_vector_dist).
@@ -1096,7 +1150,10 @@ def index_quality(ctx, index, X, Q, metric, probes=None, filtered=True):
     recall_at_1 (share whose bucket minimum equals the true minimum distance),
     ratio_mean / ratio_max (bucket distance over true distance, over the found
     queries whose true distance is > 0; nan if there is none), and the four
-    per-query device tensors bucket_dist, bucket_row, true_dist, true_row."""
+    per-query device tensors bucket_dist, bucket_row, true_dist, true_row.
+    With k given also recall_at_k: the mean over the queries of |exact k
+    nearest rows (knn) ∩ the bucket's k nearest rows (knn_lists)| / min(k, N),
+    a query with an empty bucket counting as 0."""
     torch = ctx.torch
     if isinstance(index, Cube):
         ptr, idx = index.query(Q, probes, device=True)
@@ -1110,11 +1167,14 @@ def index_quality(ctx, index, X, Q, metric, probes=None, filtered=True):
     pos = has & (td > 0)
     ratio = bd[pos] / td[pos]
     nan = float("nan")
-    return {"found": float(has.sum().item()) / nq if nq else nan,
-            "recall_at_1": float(hit.sum().item()) / nq if nq else nan,
-            "ratio_mean": float(ratio.mean().item()) if ratio.numel() else nan,
-            "ratio_max": float(ratio.max().item()) if ratio.numel() else nan,
-            "bucket_dist": bd, "bucket_row": br, "true_dist": td, "true_row": tr}
+    out = {"found": float(has.sum().item()) / nq if nq else nan,
+           "recall_at_1": float(hit.sum().item()) / nq if nq else nan,
+           "ratio_mean": float(ratio.mean().item()) if ratio.numel() else nan,
+           "ratio_max": float(ratio.max().item()) if ratio.numel() else nan,
+           "bucket_dist": bd, "bucket_row": br, "true_dist": td, "true_row": tr}
+    if k is not None:
+        out["recall_at_k"] = recall_at_k(ctx, X, Q, metric, ptr, idx, k)
+    return out
 
 
 def cluster_top_n(ctx, X, x_mean, crow, crows, U, u_mean, ucl, unk_ptr, unk_idx, n_top):

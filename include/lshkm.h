@@ -145,6 +145,12 @@ int lshkm_memcpy_d2h(lshkm_ctx ctx, void* dst_host, const void* src_dev, int64_t
  * 18 = ... queries sent to the exact scan over all rows (a poison query, a
  *      kept-list overflow; every query of a call the screen does not take),
  * 19 = ... exact distances the settle computed (kept and poison rows; the lists
+ *      form's list entries),
+ * 20 = lshkm_knn: queries the MFMA screen settled,
+ * 21 = ... queries sent to the exact scan over all rows (a poison query, fewer
+ *      than k row groups with a real row, a kept-list overflow; every query of
+ *      a call the screen does not take),
+ * 22 = ... exact distances the settle computed (kept and poison rows; the lists
  *      form's list entries). */
 int lshkm_get_stat(lshkm_ctx ctx, int which, int64_t* value_host);
 int lshkm_reset_stats(lshkm_ctx ctx);
@@ -617,6 +623,46 @@ int lshkm_min_vector_dist_lists(lshkm_ctx ctx, const float* X_dev, int64_t N, in
 int lshkm_min_vector_dist_lists_f64(lshkm_ctx ctx, const double* X_dev, int64_t N, int d, const double* Q_dev,
                                     int64_t nq, int metric, const int64_t* cand_ptr_dev, const int32_t* cand_idx_dev,
                                     double* dist_dev, int32_t* row_dev);
+/* The k exact nearest rows of every query: lshkm_min_vector_dist's distances,
+ * the k smallest of them. The distance of (query, row) is bit for bit
+ * query.euclideanDistance(row) / query.cosineDistance(row) (cust_vector.hpp:
+ * 124-155: glibc's pow(x, 2) per square, the x87 inner product, 1 - double(ip /
+ * denom)), the exact chain in both distance modes of the context. The reference
+ * has no top-k by distance, so the order is ours: the distances that are
+ * numbers first, ascending by value (-0.0 == 0.0), equal values by ascending
+ * row; then the rows whose distance is a NaN, by ascending row (x86's NaN
+ * bits). cnt_dev[q] (or NULL) = min(k, N); the slots past it hold row -1 and
+ * distance 0.0. For k = 1 the result is lshkm_min_vector_dist's on every query
+ * whose row 0 distance is not a NaN: that function's "NaN at row 0 wins" is the
+ * reference loop's rule and is not reproduced here (a NaN comes last).
+ * 1 <= k <= LSHKM_KNN_KMAX (one wave settles a query, a result slot per lane).
+ * d <= 128 goes through the f32 MFMA screen of lshkm_min_vector_dist with its
+ * bound: the rows are cut into disjoint groups, the
+ * threshold of a query is the k-th smallest of its groups' smallest upper
+ * bounds, and only the rows whose lower bound does not exceed it go to the
+ * exact chain; d > 128, calls with fewer than k groups or real rows, and every
+ * query the screen cannot decide (a poison query, more kept rows than the
+ * capacity) take the exact scan over all rows. N < 2^31, nq < 2^31, d >= 1,
+ * metric euclidean or cosine, row_dev and dist_dev not NULL, k in range: else
+ * LSHKM_ERR_ARG, before any device work. N == 0: every slot empty; nq == 0 does
+ * no device work. Returns after its workspace is free for the next call. */
+#define LSHKM_KNN_KMAX 64
+int lshkm_knn(lshkm_ctx ctx, const float* X_dev, int64_t N, int d, const float* Q_dev, int64_t nq, int metric, int k,
+              int32_t* row_dev /*[nq][k]*/, double* dist_dev /*[nq][k]*/, int32_t* cnt_dev /*[nq] or NULL*/);
+int lshkm_knn_f64(lshkm_ctx ctx, const double* X_dev, int64_t N, int d, const double* Q_dev, int64_t nq, int metric,
+                  int k, int32_t* row_dev, double* dist_dev, int32_t* cnt_dev);
+/* The same over each query's own candidate vector X[cand_idx_dev[cand_ptr_dev[q]
+ * .. cand_ptr_dev[q+1])] (lshkm_lsh_query's and lshkm_cube_query's CSR): the
+ * tie-breaking key is the position in the list, cnt_dev[q] = min(k, the list's
+ * length), row_dev holds dataset rows (cand_idx's values). A cand_ptr that
+ * does not start at 0 or decreases, or an index outside [0, N), is
+ * LSHKM_ERR_ARG (checked on the device before anything is written). */
+int lshkm_knn_lists(lshkm_ctx ctx, const float* X_dev, int64_t N, int d, const float* Q_dev, int64_t nq, int metric,
+                    int k, const int64_t* cand_ptr_dev /*[nq+1]*/, const int32_t* cand_idx_dev, int32_t* row_dev,
+                    double* dist_dev, int32_t* cnt_dev);
+int lshkm_knn_lists_f64(lshkm_ctx ctx, const double* X_dev, int64_t N, int d, const double* Q_dev, int64_t nq,
+                        int metric, int k, const int64_t* cand_ptr_dev, const int32_t* cand_idx_dev, int32_t* row_dev,
+                        double* dist_dev, int32_t* cnt_dev);
 /* get_top_N_recom (crypto_rec.hpp:305-325) over lshkm_p_closest's lists:
  * predicted scores of each user's unknown indexes (get_predicted_user_sim,
  * :280-302; unk_* = CSR of the ascending unknown indexes, std::set order),

@@ -6,7 +6,7 @@ syncs (host launch and sync latency included) -- next to the CPU restatement (or
 thread, OMP_NUM_THREADS=1, kind "port") on a bounded sample of the same
 workload, scaled to the row's unit. Prints one JSON line per row.
 
-    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64,cv,lshpc,cubepc,nearest] [--no-cpu]
+    python tools/bench_rows.py [--rows cosine,kpp,range,sil,pam,update,lsh,cube,recom,csv,f64,cv,lshpc,cubepc,nearest,knn] [--no-cpu]
     python tools/bench_rows.py --rows main_program --main-dir DIR [--main-ref-seconds S]
 """
 import argparse
@@ -629,6 +629,49 @@ def main():
                             "Lloyd route); stats per call; cpu_port: oracle.lloyd_assign over 256 of the queries")
             print(json.dumps(line), flush=True)
             del X, Q
+
+    if "knn" in rows:        # lshkm_knn for k = 1, 10, 64 on the nearest row's shapes, next to lshkm_min_vector_dist
+        shapes = [("grid fp32", 1_000_000, 128, 4096, "euclidean"), ("grid fp32", 1_000_000, 128, 4096, "cosine"),
+                  ("cv_users fp64", 200_000, 20, 20_000, "cosine")]
+        S = (lshkm.STAT_KNN_SETTLED, lshkm.STAT_KNN_SCAN, lshkm.STAT_KNN_EXACT)
+        for kind, N, d, nq, metric in shapes:
+            if kind == "grid fp32":
+                X, Q = ctx.synth(0x5EED + 21, N, d), ctx.synth(0x5EED + 22, nq, d)
+            else:
+                X = torch.from_numpy(cv_users(N, d)[0]).to(ctx.dev)
+                Q = torch.from_numpy(cv_users(nq, d, seed=0xBE7C5)[0]).to(ctx.dev)
+            out = {}
+            t_min = event_ms(lambda: out.update(min=lshkm.min_vector_dist(ctx, X, Q, metric)), warm=2, reps=5)
+            m, D = 16, None
+            if cpu and N <= 200_000:     # the oracle's exact distance of every (query, row) pair, one row at a time
+                Xh, Qh = X.cpu().numpy(), np.ascontiguousarray(Q[:m].cpu().numpy(), np.float64)
+                D = np.stack([oracle.lloyd_assign(Qh, Xh[j:j + 1], metric)[1] for j in range(N)], axis=1)
+            for k in (1, 10, 64):
+                ctx.reset_stats()
+                t = event_ms(lambda: out.update(knn=lshkm.knn(ctx, X, Q, k, metric)), warm=2, reps=5)
+                st = [ctx.stat(i) // 7 for i in S]
+                line = {"row": "knn", "rows": kind, "N": N, "d": d, "nq": nq, "metric": metric, "k": k,
+                        "knn_ms": {"median": t[0], "min": t[1], "max": t[2]},
+                        "min_vector_dist_ms": {"median": t_min[0], "min": t_min[1], "max": t_min[2]},
+                        "over_min_vector_dist": t[0] / t_min[0], "stat_settled": st[0], "stat_scan": st[1],
+                        "stat_exact": st[2], "exact_per_query": st[2] / nq}
+                if k == 1:
+                    nan0 = torch.isnan(out["min"][0])
+                    line["identical_to_min_vector_dist"] = bool(
+                        torch.equal(out["knn"][0][:, 0][~nan0], out["min"][1][~nan0]) and
+                        torch.equal(out["knn"][1][:, 0][~nan0].view(torch.int64), out["min"][0][~nan0].view(torch.int64)))
+                if D is not None:
+                    order = np.stack([np.lexsort((np.arange(N), np.where(np.isnan(r), 0.0, r), np.isnan(r)))[:k] for r in D])
+                    line["identical_to_port"] = bool(
+                        np.array_equal(out["knn"][0][:m].cpu().numpy(), order.astype(np.int32)) and
+                        np.array_equal(out["knn"][1][:m].cpu().numpy().view(np.uint64),
+                                       np.take_along_axis(D, order, 1).view(np.uint64)))
+                line["note"] = ("HIP events around single calls, median / min / max of 5 after 2 warm-ups, "
+                                "lshkm_min_vector_dist timed the same way in the same process; stats per call; "
+                                "identical_to_port: the oracle's per-row distance matrix over 16 of the queries "
+                                "(N <= 200,000)")
+                print(json.dumps(line), flush=True)
+            del X, Q, out
 
     if "main_program" in rows:   # the whole program (main.cpp:36-390) on the files of gen_main_golden --time FACTOR DIR
         sys.path.insert(0, os.path.join(ROOT, "crypto-recommendation_amd"))
