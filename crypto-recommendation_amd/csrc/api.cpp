@@ -659,6 +659,7 @@ static int assign_f32_mfma(lshkm_ctx ctx, const AssignJob& q) {
         (rc = ctx->ws_counter.reserve(64)))
         return rc;
     unsigned long long* cnt = (unsigned long long*)ctx->ws_counter.p;
+    ctx->ws_dirty();              // ws_counter / ws_cconst: not as fused_assign left them
     LSHKM_HIP(hipMemsetAsync(cnt, 0, 16, s));
     if ((rc = launch_centroid_prep(s, q.C, q.K, Kpad, q.d, DP, q.metric, q.X.f64, (float*)ctx->ws_c32.p, (float*)ctx->ws_cconst.p))) return rc;
     if ((rc = launch_assign_mfma(s, q.X, N, q.d, DP, q.C, q.K, Kpad, q.metric, (const float*)ctx->ws_c32.p, (const float*)ctx->ws_cconst.p,
@@ -671,6 +672,31 @@ static int assign_f32_mfma(lshkm_ctx ctx, const AssignJob& q) {
          (rc = launch_add_counter(s, (unsigned long long*)ctx->stats.p + STAT_COS_FIX, cnt + 1)))) return rc;
     // ambiguous-count statistic
     return launch_add_counter(s, (unsigned long long*)ctx->stats.p + STAT_ASSIGN_AMBIG, cnt);
+}
+
+// The centroid override's source rows into ws_src on the context's stream.
+static int stage_override(lshkm_ctx ctx, const int32_t* src_rows_host, int K) {
+    hipStream_t s = ctx->stream;
+    int rc;
+    if ((rc = ctx->ws_src.reserve((size_t)K * 4))) return rc;
+    // The same rows as the previous override already sit in ws_src (Lloyd
+    // iterations and the bench pass one array repeatedly): no copy. A small
+    // host->device copy blocked the host until the stream drained, so every
+    // call waited for the previous one's tail: 2.05 ms of host enqueue per call vs 0.05).
+    const bool same = ctx->src_cache_dev == ctx->ws_src.p && ctx->src_cache_cap == ctx->ws_src.cap &&
+                      ctx->src_cache.size() == (size_t)K &&
+                      std::memcmp(ctx->src_cache.data(), src_rows_host, (size_t)K * 4) == 0;
+    if (same) return 0;
+    // Stage through a pinned buffer so the caller's array may be freed at
+    // once and no stream sync is needed (a ring of buffers, index.h).
+    if ((rc = ctx->pin_stage((size_t)K * 4))) return rc;
+    std::memcpy(ctx->pinned, src_rows_host, (size_t)K * 4);
+    LSHKM_HIP(hipMemcpyAsync(ctx->ws_src.p, ctx->pinned, (size_t)K * 4, hipMemcpyHostToDevice, s));
+    LSHKM_HIP(hipEventRecord(ctx->pinned_ev, s));
+    ctx->src_cache.assign(src_rows_host, src_rows_host + K);
+    ctx->src_cache_dev = ctx->ws_src.p;
+    ctx->src_cache_cap = ctx->ws_src.cap;
+    return 0;
 }
 
 // force_exact: exact distances whatever the context's mode (range
@@ -689,8 +715,14 @@ static int assign_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const double* C, 
                                          X, N, lsh->proj, lsh->nb,
                                          lsh->metric == LSHKM_METRIC_EUCLIDEAN ? tuples : nullptr, phi, bucket,
                                          nullptr))) { LSHKM_LAUNCH_CHECK(); return rc; }
-    if (path == 0 || path == 3) rc = fused_assign(ctx, q);
-    else if (path == 1) rc = assign_f32_mfma(ctx, q);
+    const bool fused = path == 0 || path == 3;
+    // the centroid override: staged ahead of a fused pass, whose last kernel
+    // applies it; a launch of its own after the other paths
+    if (src_rows_host && (rc = stage_override(ctx, src_rows_host, K))) return rc;
+    if (fused) {
+        if (src_rows_host) q.src_dev = (const int32_t*)ctx->ws_src.p;
+        rc = fused_assign(ctx, q);
+    } else if (path == 1) rc = assign_f32_mfma(ctx, q);
     else {
         // Exact reference-order pass over every centroid (cosine metric, or d > 256).
         RowList all;
@@ -698,28 +730,8 @@ static int assign_impl(lshkm_ctx ctx, Pts X, int64_t N, int d, const double* C, 
         rc = launch_exact_pass(s, q, all, ExactForm::every, nullptr, true, nullptr, nullptr);
     }
     if (rc) { LSHKM_LAUNCH_CHECK(); return rc; }
-    if (src_rows_host) {
-        if ((rc = ctx->ws_src.reserve((size_t)K * 4))) return rc;
-        // The same rows as the previous override already sit in ws_src (Lloyd
-        // iterations and the bench pass one array repeatedly): no copy. A small
-        // host->device copy blocked the host until the stream drained, so every
-        // call waited for the previous one's tail: 2.05 ms of host enqueue per call vs 0.05).
-        const bool same = ctx->src_cache_dev == ctx->ws_src.p && ctx->src_cache_cap == ctx->ws_src.cap &&
-                          ctx->src_cache.size() == (size_t)K &&
-                          std::memcmp(ctx->src_cache.data(), src_rows_host, (size_t)K * 4) == 0;
-        if (!same) {
-            // Stage through a pinned buffer so the caller's array may be freed at
-            // once and no stream sync is needed (a ring of buffers, index.h).
-            if ((rc = ctx->pin_stage((size_t)K * 4))) return rc;
-            std::memcpy(ctx->pinned, src_rows_host, (size_t)K * 4);
-            LSHKM_HIP(hipMemcpyAsync(ctx->ws_src.p, ctx->pinned, (size_t)K * 4, hipMemcpyHostToDevice, s));
-            LSHKM_HIP(hipEventRecord(ctx->pinned_ev, s));
-            ctx->src_cache.assign(src_rows_host, src_rows_host + K);
-            ctx->src_cache_dev = ctx->ws_src.p;
-            ctx->src_cache_cap = ctx->ws_src.cap;
-        }
-        if ((rc = launch_assign_override(s, (const int32_t*)ctx->ws_src.p, K, N, assign, dist))) { LSHKM_LAUNCH_CHECK(); return rc; }
-    }
+    if (src_rows_host && !fused &&
+        (rc = launch_assign_override(s, (const int32_t*)ctx->ws_src.p, K, N, assign, dist))) { LSHKM_LAUNCH_CHECK(); return rc; }
     return 0;
 }
 

@@ -368,10 +368,9 @@ __global__ void assign_override_kernel(const int32_t* __restrict__ src, int K, i
 // scans the later entries 4 at a time (ds_read_b128, 4 independent reads in
 // flight) instead of K^2/2 dependent global loads.
 constexpr int OV_LDS_MAX = 8192;
-__global__ __launch_bounds__(1024) void assign_override_lds_kernel(const int32_t* __restrict__ src, int K, int64_t N,
-                                                                  int32_t* __restrict__ assign,
-                                                                  double* __restrict__ dist) {
-    __shared__ __attribute__((aligned(16))) int32_t ls[OV_LDS_MAX + 16];
+// ls: the block's (K + 15 & ~15) + 16 words
+__device__ inline void override_lds(const int32_t* __restrict__ src, int K, int64_t N, int32_t* __restrict__ assign,
+                                    double* __restrict__ dist, int32_t* ls) {
     const int Kp = (K + 15) & ~15;
     for (int c = threadIdx.x; c < Kp + 16; c += blockDim.x) ls[c] = c < K ? src[c] : -1;
     __syncthreads();
@@ -394,6 +393,12 @@ __global__ __launch_bounds__(1024) void assign_override_lds_kernel(const int32_t
             dist[r] = 0.0;
         }
     }
+}
+__global__ __launch_bounds__(1024) void assign_override_lds_kernel(const int32_t* __restrict__ src, int K, int64_t N,
+                                                                  int32_t* __restrict__ assign,
+                                                                  double* __restrict__ dist) {
+    __shared__ __attribute__((aligned(16))) int32_t ls[OV_LDS_MAX + 16];
+    override_lds(src, K, N, assign, dist, ls);
 }
 
 int launch_assign_override(hipStream_t s, const int32_t* src_rows, int K, int64_t N, int32_t* assign,
@@ -437,6 +442,54 @@ int launch_add_counters(hipStream_t s, unsigned long long* stats, int n, const i
     for (int i = 0; i < n; i++) { c.dst[i] = dst_idx[i]; c.src[i] = src[i]; }
     hipLaunchKernelGGL(add_counters_kernel, dim3(1), dim3(64), 0, s, stats, c);
     return kstatus("assign.hip");
+}
+
+// The fused assignment's epilogue, one small block (it is placed beside the
+// hash fix-up's blocks as soon as one of them ends): the call's counters added
+// into the context's, the counters and the centroid prep's bound words then
+// zeroed for the next call (fused.hip: a clean workspace needs no clears), and
+// the centroid override where the call has one (src != NULL, K <= OV_LDS_MAX).
+// EPI_THREADS threads without an override or with few centroids; with more
+// centroids as many as the override's own kernel, up to EPI_THREADS_MAX (its
+// scan of the later entries is quadratic in K).
+constexpr int EPI_THREADS = 256, EPI_THREADS_MAX = 1024;
+__global__ __launch_bounds__(EPI_THREADS_MAX) void fused_epilogue_kernel(unsigned long long* stats, CounterAdds c,
+                                                                     unsigned long long* cnt, int ncnt,
+                                                                     unsigned int* cb, int ncb,
+                                                                     const int32_t* __restrict__ src, int K, int64_t N,
+                                                                     int32_t* __restrict__ assign,
+                                                                     double* __restrict__ dist) {
+    extern __shared__ __attribute__((aligned(16))) int32_t epi_ls[];
+    if ((int)threadIdx.x < c.n) atomicAdd(stats + c.dst[threadIdx.x], *c.src[threadIdx.x]);
+    __syncthreads();                      // every counter read before any is zeroed
+    if ((int)threadIdx.x < ncnt) cnt[threadIdx.x] = 0ull;
+    if ((int)threadIdx.x < ncb) cb[threadIdx.x] = 0u;
+    if (src) override_lds(src, K, N, assign, dist, epi_ls);
+}
+
+int launch_fused_epilogue(hipStream_t s, unsigned long long* stats, int n, const int* dst_idx,
+                          const unsigned long long* const* srcs, unsigned long long* cnt, int ncnt, unsigned int* cb,
+                          int ncb, const int32_t* src_rows, int K, int64_t N, int32_t* assign, double* dist) {
+    if (n > 8 || ncnt > EPI_THREADS || ncb > EPI_THREADS) {
+        set_error("launch_fused_epilogue: at most 8 counters and 256 words to zero");
+        return -1;
+    }
+    CounterAdds c;
+    c.n = n;
+    for (int i = 0; i < n; i++) { c.dst[i] = dst_idx[i]; c.src[i] = srcs[i]; }
+    // more centroids than the LDS form holds: the override's global-memory
+    // kernel after the epilogue (it touches assign / dist alone)
+    const bool own_launch = src_rows && K > OV_LDS_MAX;
+    const int32_t* src = own_launch ? nullptr : src_rows;
+    const size_t lds = src ? ((size_t)((K + 15) & ~15) + 16) * 4 : 0;
+    const int threads = src ? std::min(EPI_THREADS_MAX, std::max(EPI_THREADS, (K + 63) / 64 * 64)) : EPI_THREADS;
+    hipLaunchKernelGGL(fused_epilogue_kernel, dim3(1), dim3(threads), lds, s, stats, c, cnt, ncnt, cb, ncb, src, K, N,
+                       assign, dist);
+    if (own_launch) {
+        const int rc = kstatus("fused_epilogue_kernel");
+        return rc ? rc : launch_assign_override(s, src_rows, K, N, assign, dist);
+    }
+    return kstatus("fused_epilogue_kernel");
 }
 
 }  // namespace lshkm

@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "exact.h"
 #include "pick.h"
+#include "settle.h"
 
 namespace lshkm {
 
@@ -86,18 +87,6 @@ __device__ inline void stage_rows(const TX* __restrict__ X, int d, const int32_t
     wave_sync();
 }
 
-// The every-centroid loop of one row over the wave's lanes, dd(c) the
-// reference's distance. assignment.hpp:66: the -1 sentinel takes centroid 0's
-// distance even if NaN (a zero vector under cosine), which then blocks every
-// later '<'; any other NaN is never taken.
-template <typename F>
-__device__ inline void every_centroid(int K, F&& dd, double& best, int& bi) {
-    for (int c = threadIdx.x & 63; c < K; c += 64) {
-        const double v = dd(c);
-        if (bi < 0 ? (v == v || c == 0) : v < best) { best = v; bi = c; }
-    }
-}
-
 // Cosine, a row with an inf or NaN entry: every product with it is inf or NaN
 // and the row's norm is, so every distance is the default NaN (inf / inf) and
 // the sentinel keeps centroid 0. The soft-x87 chains take finite products only
@@ -110,18 +99,6 @@ __device__ inline bool cosine_nonfinite_row(const TX* x, int d, double& best, in
     best = __longlong_as_double((long long)0xFFF8000000000000ull);
     bi = 0;
     return true;
-}
-
-// The wave's (best, bi) of one row to its outputs: the smallest value, then the
-// smallest index (= the first strict minimum in c order); no lane took any:
-// the reference's sentinel.
-__device__ inline void wave_store(double best, int bi, int64_t row, int32_t* __restrict__ assign,
-                                  double* __restrict__ dist) {
-    group_argmin<64>(best, bi);
-    if ((threadIdx.x & 63) == 0) {
-        assign[row] = bi < 0 ? 0 : bi;
-        dist[row] = bi < 0 ? -1.0 : best;
-    }
 }
 
 // -------------------------------------------------------------------- every
@@ -413,23 +390,6 @@ __device__ inline bool row_candidates(float xn2p, const float (&acc)[NCH], const
         ncand += __popcll(cm[i]);
     }
     return __all(finite) && ncand >= 1;
-}
-
-// The k-th candidate of the ballots (increasing c), or -1 past the last.
-template <int NCH>
-__device__ inline int kth_candidate(const unsigned long long (&cm)[NCH], int k) {
-    int c = -1, seen = 0;
-#pragma unroll
-    for (int i = 0; i < NCH; i++) {
-        const int n = __popcll(cm[i]);
-        if (c < 0 && k >= seen && k < seen + n) {
-            unsigned long long m = cm[i];
-            for (int t = k - seen; t > 0; t--) m &= m - 1;
-            c = 64 * i + __builtin_ctzll(m);
-        }
-        seen += n;
-    }
-    return c;
 }
 
 // The whole wave decides one row: lane k takes the k-th of its (at most 64)

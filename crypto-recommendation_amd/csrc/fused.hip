@@ -240,6 +240,10 @@ struct PhaseReport {
 
 int fused_assign(lshkm_ctx ctx, const AssignRequest& q) {
     hipStream_t s = ctx->stream;
+    // what the previous call's epilogue left zeroed; the record is dropped until
+    // this call's own epilogue is enqueued, so no error return leaves one
+    const lshkm_ctx_s::WsClean was_clean = ctx->ws_clean;
+    ctx->ws_dirty();
     const bool cosine = q.metric != LSHKM_METRIC_EUCLIDEAN;
     const ProjTable* pj = q.lsh ? &q.lsh->proj : nullptr;
     const FusedRoute route = fused_route(cosine, q.X.f64, q.d, q.K, pj != nullptr, pj ? pj->k : 0, pj ? pj->LK : 0,
@@ -263,14 +267,24 @@ int fused_assign(lshkm_ctx ctx, const AssignRequest& q) {
     int rc;
     FusedWorkspace w;
     if ((rc = fused_workspace(ctx, sh, w))) return rc;
-    LSHKM_HIP(hipMemsetAsync(w.cnt, 0, FUSED_COUNTER_CLEAR, s));
+    // the counters and the prep's bound words: zero as the last call's epilogue
+    // left them, or cleared here (a first call, new allocations, another user since)
+    const bool clean = was_clean.cnt == w.cnt && was_clean.cnt_cap == ctx->ws_counter.cap && was_clean.cb == w.cbound &&
+                       was_clean.cb_cap == ctx->ws_cconst.cap;
+    if (!clean) {
+        LSHKM_HIP(hipMemsetAsync(w.cnt, 0, FUSED_COUNTER_CLEAR, s));
+        LSHKM_HIP(hipMemsetAsync(w.cbound, 0, FUSED_CBOUND_BYTES, s));
+    }
     // the timed fused pass starts before the centroid prep
     if (ctx->timing) LSHKM_HIP(hipEventRecord(ctx->tev[0], s));
     ctx->tev_side = false;
     if ((rc = launch_fused_prep(s, q.C, q.K, q.d, cosine ? 1 : 0, w))) return rc;
     // the listed pass's centroid prep ahead of the passes: it then starts as
     // soon as the refinement ends
-    const bool xprep = exact_is_pruned(exact_form(q));
+    // (not where the refinement settles its leftover rows itself: no listed pass)
+    const bool pair_pass = q.N > 0 && route.form != FusedForm::chunked && sh.pairs() && !test_switch("LSHKM_PAIR_PASS", "0");
+    const bool settle = pair_pass && !test_switch("LSHKM_SETTLE", "0");
+    const bool xprep = !settle && exact_is_pruned(exact_form(q));
     if (xprep && (rc = exact_listed_prep(ctx, q))) return rc;
     if (w.xn2 && (rc = launch_row_sumsq(s, q.X.d(), q.N, q.d, w.xn2))) return rc;
 
@@ -331,23 +345,38 @@ int fused_assign(lshkm_ctx ctx, const AssignRequest& q) {
         // euclidean, one refinement pass: the rows it names both candidates of go
         // to the pair list (counts beside list2's), which each block decides itself
         // before it ends; LSHKM_PAIR_PASS=0: all to list2
-        if (sh.pairs() && !test_switch("LSHKM_PAIR_PASS", "0")) {
+        // and with them every other uncertified row is settled by the wave that
+        // meets it (counted in list2's slots, not listed); LSHKM_SETTLE=0: to list2
+        if (pair_pass) {
             pair_rows = segmented(w.pairs, w.cnt + CNT_PAIR, w.seg2, q, p);
             rf.pairs = pair_rows.p; rf.pair_count = pair_rows.count;
+            rf.settle = settle ? 1 : 0;
         }
         if ((rc = fused_refine_passes(s, rf, p))) return rc;
         if (cosine && (rc = side.join())) return rc;
         if ((rc = kstatus("fused_hi_kernel"))) return rc;
+        // (with settle, l2's counts -- CNT_AMBIG and the segments' slot 0 -- count rows
+        // the refinement decided itself and list2 does not hold: no listed pass on them)
         exact_rows = l2;        if (cosine || pwfix) dist_fix[ndist_fix++] = segmented(w.cfix, w.cnt + CNT_CFIX, w.seg3, q, p);
         if (cosine) dist_fix[ndist_fix++] = segmented(w.hfix2, w.cnt + CNT_CFIX, w.seg2, q, p);
     }
     if (ctx->timing) LSHKM_HIP(hipEventRecord(ctx->tev[1], s));
-    if ((rc = exact_listed(ctx, q, exact_rows, !sh.fast, xprep, cosine ? w.xn2 : nullptr, cosine ? w.nbv : nullptr)))
+    if (!settle &&
+        (rc = exact_listed(ctx, q, exact_rows, !sh.fast, xprep, cosine ? w.xn2 : nullptr, cosine ? w.nbv : nullptr)))
         return rc;
-    if ((rc = side.join())) return rc;
+    // The call's epilogue, one kernel: its counters into the context's, the
+    // workspace words zeroed for the next call, the centroid override. It reads
+    // and writes nothing the hash fix-up touches, so it runs beside it, before
+    // the join; a call with distance fix-up lists joins first and ends with it.
+    const bool dist_lists = cosine || pwfix;
+    if (dist_lists) {
+        if ((rc = side.join())) return rc;
+        if ((rc = launch_cos_fix_seg(s, q, ndist_fix, dist_fix, cosine ? w.xn2 : nullptr, cosine ? w.nbv : nullptr)))
+            return rc;
+    }
     {
-        int di[5], n = 0;
-        const unsigned long long* sp[5];
+        int di[6], n = 0;
+        const unsigned long long* sp[6];
         di[n] = STAT_REFINED; sp[n++] = w.cnt + CNT_REFINED;
         if (sh.hash) { di[n] = STAT_HASH_FIX; sp[n++] = w.cnt + CNT_HFIX; }
         di[n] = STAT_ASSIGN_AMBIG; sp[n++] = w.cnt + CNT_AMBIG;
@@ -356,15 +385,15 @@ int fused_assign(lshkm_ctx ctx, const AssignRequest& q) {
             di[n] = STAT_ASSIGN_AMBIG; sp[n++] = w.cnt + CNT_PAIR;
             di[n] = STAT_PAIR_ROWS; sp[n++] = w.cnt + CNT_PAIR;
         }
-        if ((rc = launch_add_counters(s, ctx->stats.as<unsigned long long>(), n, di, sp))) return rc;
-    }
-    if (cosine || pwfix) {
-        if ((rc = launch_cos_fix_seg(s, q, ndist_fix, dist_fix, cosine ? w.xn2 : nullptr, cosine ? w.nbv : nullptr)))
-            return rc;
-        if ((rc = launch_add_counter(s, ctx->stats.as<unsigned long long>() + (cosine ? STAT_COS_FIX : STAT_POW_FIX),
-                                     w.cnt + CNT_CFIX)))
+        if (dist_lists) { di[n] = cosine ? STAT_COS_FIX : STAT_POW_FIX; sp[n++] = w.cnt + CNT_CFIX; }
+        if ((rc = launch_fused_epilogue(s, ctx->stats.as<unsigned long long>(), n, di, sp, w.cnt,
+                                        (int)(FUSED_COUNTER_CLEAR / 8), reinterpret_cast<unsigned int*>(w.cbound),
+                                        (int)(FUSED_CBOUND_BYTES / 4), q.src_dev, q.K, q.N, q.assign, q.dist)))
             return rc;
     }
+    ctx->ws_clean.cnt = w.cnt; ctx->ws_clean.cnt_cap = ctx->ws_counter.cap;
+    ctx->ws_clean.cb = w.cbound; ctx->ws_clean.cb_cap = ctx->ws_cconst.cap;
+    if ((rc = side.join())) { ctx->ws_dirty(); return rc; }
     return 0;
 }
 

@@ -86,6 +86,8 @@ struct FusedArgs {
     unsigned long long* pairs;
     unsigned long long* pair_count;
     int K;                           // real centroids of the call (a pair names none past them)
+    int settle;                      // with pairs: the refinement decides every other uncertified row too
+                                     // (settle_rows, fused_refine.hip): counted in ambig's slots, not listed
 };
 
 }  // namespace lshkm

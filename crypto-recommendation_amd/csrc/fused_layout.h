@@ -92,6 +92,7 @@ constexpr int CNT_REFINED = 2;       // rows the hi-only passes left to the refi
 constexpr int CNT_CFIX = 3;          // cosine declines / pow fix-ups
 constexpr int CNT_PAIR = 4;          // uncertified rows the refinement named both candidates of and decided itself
 constexpr size_t FUSED_COUNTER_BYTES = 64, FUSED_COUNTER_CLEAR = 40;
+constexpr size_t FUSED_CBOUND_BYTES = 32;      // FusedArgs::cbound: the centroid prep's maxima start from zero
 
 // ---- the workspace of one fused assignment
 struct FusedShape {

@@ -2,6 +2,7 @@
 // the rows a hi-only pass (fused_hi.hip) could not certify, scored again with
 // the full split x = xh + xl, c = ch + cl.
 #include "fused_impl.h"
+#include "settle.h"
 
 namespace lshkm {
 
@@ -36,6 +37,7 @@ __device__ inline void tile_scores(const floatx16& acc_hi, const floatx16& acc_l
 
 __host__ __device__ constexpr int fp_lds_bytes(int Kpad) { return 16 + 2 * Kpad * FU_RS * 2 + Kpad * 4; }
 static_assert(fp_lds_bytes(FP_KMAX) <= 160 * 1024, "refinement LDS image exceeds 160 KiB");
+static_assert(FP_KMAX <= 32 * ST_TILES, "a settled row's candidate mask covers one refinement pass");
 
 // ---- the pair rows' finish. A block decides its own pair rows before it ends,
 // in the LDS its centroid image leaves behind: a wave takes FP_PAIR_REC records
@@ -98,6 +100,53 @@ __device__ inline void pair_finish(const FusedArgs& a, const unsigned long long*
             a.dist[row] = best;
         }
         wave_sync();
+    }
+}
+
+// ---- the rows that are neither certified nor pair rows, settled by the wave
+// that meets them (a.settle), so the call launches no listed pass. The tile's
+// centroid tiles run once more and every lane keeps, per score, whether it
+// reaches the certificate's own threshold M1 - 2E (settle.h's mask; the row's
+// two lanes hold its set).
+// The set contains the reference's nearest centroid, by the certificate's
+// argument: E bounds |s - t| for every computed score s of the row against its
+// true score t = x.c - |c|^2/2, for the plain f32 value tile_scores returns as
+// for the value with the in-tile index packed into its low mantissa bits (the
+// packing's 16 ulp are one of E's terms), and it covers the reference's own
+// rounding of its distances (the 2^-41 |x|^2 term). M1 is the packed score of
+// I1, so t_I1 >= M1 - E; a centroid whose plain score lies below M1 - 2E has
+// t < M1 - E <= t_I1 by more than the reference can round away: it is neither
+// the reference's nearest nor tied with it. The collecting pass compares the
+// plain scores (the certificate compares packed ones; either is within E).
+// Padding centroids (>= K) are dropped from the set.
+// The rows are then taken one at a time by the whole wave, as the listed pruned
+// pass's wave_decide takes them: at most 64 candidates, lane k runs the chain
+// of the k-th (pruned_pick_euclid, the row read from global memory); more, or a
+// row or centroid set outside the f16 range guard (no certificate: ok false),
+// every centroid with the reference's chain. Any superset of the reference's
+// near-ties gives the same pick: the chains are exact and the lowest index wins.
+template <int ROWS>
+__device__ inline void settle_rows(const FusedArgs& a, unsigned long long amask, const LaneMask& cand, int64_t row,
+                                   bool ok, int lane) {
+    using TX = std::conditional_t<ROWS == 2, double, float>;
+    const TX* X;
+    if constexpr (ROWS == 2) X = a.X64; else X = a.X;
+    const int d = ROWS == 0 ? FU_D : a.d;
+    for (unsigned long long m = amask; m; m &= m - 1) {      // wave-uniform: the rows' upper lanes
+        const int up = __builtin_ctzll(m), lw = up - 32;
+        const int64_t r = __shfl(row, up);
+        const LaneMask m0 = {__shfl(cand.lo, lw), __shfl(cand.hi, lw)}, m1 = {__shfl(cand.lo, up), __shfl(cand.hi, up)};
+        const bool rok = __shfl(ok ? 1 : 0, up) != 0;
+        unsigned long long cm[ST_CHUNKS];
+        const int n = settle_set(m0, m1, a.K, cm);
+        const TX* xr = X + r * d;
+        double best = 0.0;
+        int bi = -1;
+        if (rok && n >= 1 && n <= 64)
+            pruned_pick_euclid<64>(xr, a.Cd, d, kth_candidate(cm, lane), !a.fast_dist, best, bi);
+        else
+            every_centroid(a.K, [&](int c) { return exact_euclid_rolled(xr, a.Cd + (size_t)c * d, d); }, best, bi);
+        wave_store(best, bi, r, a.assign, a.dist);
     }
 }
 
@@ -279,6 +328,32 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
                    (double)pm.M3 < (double)M1 - 2.0 * (double)E;
         }
 
+        // A row nobody else decides: with a.settle the wave decides it below, from
+        // the candidates a second run of the tile's centroid tiles collects here,
+        // while the split operand is still in registers (wave-uniform branch)
+        const bool amb = valid && !cert && !pair;
+        LaneMask cand = {0ull, 0ull};
+        bool settle = false;
+        if constexpr (PAIR) {
+            settle = a.settle && __ballot(amb) != 0ull;
+            if (settle) {
+                const double thr = (double)M1 - 2.0 * (double)E;
+                __builtin_amdgcn_s_setprio(MFMA_PRIO);
+#pragma unroll 1
+                for (int t = 0; t < ntile32; t++) {
+                    float sv[16];
+                    floatx16 acc_hi, acc_lo;
+                    tile_mfma(my_h + t * 32 * FU_RS, my_l + t * 32 * FU_RS, bh, bl, acc_hi, acc_lo);
+                    tile_scores(acc_hi, acc_lo, lcn + t * 32 + 4 * h, sv);
+                    uint32_t bits = 0u;
+#pragma unroll
+                    for (int i = 0; i < 16; i++) bits |= (double)sv[i] >= thr ? 1u << i : 0u;
+                    settle_mark(cand, t, bits);
+                }
+                __builtin_amdgcn_s_setprio(0);
+            }
+        }
+
         // ---- winner distance in reference order: the squares are independent,
         // only the sum is a chain; dims 8seg..8seg+7 belong to lane half seg & 1,
         // and the halves hand the sum on after every 8 dims.
@@ -365,7 +440,6 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
         PT_MARK(3)
         if constexpr (PAIR)
             seg_append(valid && pair && h == 1, pair_record(row, I1, I2), lcount + 1, pair_seg, lane);
-        const bool amb = valid && !cert && !pair;
         const unsigned long long amask = __ballot(amb && h == 1);
         if (h == 1 && valid) {
             if (amb) {
@@ -374,8 +448,11 @@ __global__ __launch_bounds__(FP_THREADS, 1) void fused_persistent_kernel(FusedAr
                 if (lane == leader) base = atomicAdd(lcount, __popcll(amask));
                 base = __shfl(base, leader);
                 const int rank = __popcll(amask & ((1ull << lane) - 1ull));
-                ambig_seg[base + rank] = (int32_t)row;
+                if (!(PAIR && a.settle)) ambig_seg[base + rank] = (int32_t)row;     // settled here: counted only
             }
+        }
+        if constexpr (PAIR) {
+            if (settle) settle_rows<ROWS>(a, amask, cand, row, x_ok && c_ok, lane);
         }
         PT_MARK(4)
     }

@@ -393,7 +393,7 @@ __global__ void fused_centroid_prep(const double* __restrict__ C, int K, int Kpa
 int launch_fused_prep(hipStream_t s, const double* C, int K, int d, int metric, const FusedWorkspace& w) {
     const int Kpad = (K + 63) / 64 * 64;
     static_assert(64 % FP_PREP_WAVES == 0, "Kpad is a multiple of 64");
-    (void)hipMemsetAsync(w.cbound, 0, 32, s);
+    // (w.cbound's FUSED_CBOUND_BYTES are zero here: fused_assign's clear, or the last call's epilogue)
     hipLaunchKernelGGL(fused_centroid_prep, dim3((unsigned)(Kpad / FP_PREP_WAVES)), dim3(64 * FP_PREP_WAVES), 0, s, C, K, Kpad, w.Ch, w.Cl, w.cnh,
                        reinterpret_cast<unsigned int*>(w.cbound), metric, w.nbv, w.C32, w.rn32, d, w.C64p);
     return kstatus("fused_centroid_prep");

@@ -71,6 +71,9 @@ struct AssignRequest : AssignJob {
     const ::lshkm_lsh_s* lsh = nullptr;          // hash in this pass (NULL: assignment alone)
     int32_t *tuples = nullptr, *phi = nullptr, *bucket = nullptr;
     bool force_exact = false;                    // exact distances whatever the context's mode
+    // the centroid override's source rows, staged on the device ([K] int32; NULL:
+    // none): fused_assign's last kernel applies it
+    const int32_t* src_dev = nullptr;
 };
 int fused_assign(lshkm_ctx_s* ctx, const AssignRequest& q);
 
@@ -114,6 +117,16 @@ struct lshkm_ctx_s {
     // lshkm_knn (knn_layout.h): the call's state; its images are ws_nearest's
     lshkm::Buf ws_knn;
     uint64_t ws_epoch = 0;       // bumped by every user of the ws[] slots (api_index.cpp reserve)
+    // The fused assignment's last kernel leaves its counters (ws_counter) and
+    // the centroid prep's bound words (ws_cconst) zeroed, so the next call on
+    // the same allocations clears nothing. fused_assign takes the record at its
+    // start (any return before its last kernel leaves none) and every other
+    // user of the two buffers drops it (ws_dirty).
+    struct WsClean {
+        const void *cnt = nullptr, *cb = nullptr;
+        size_t cnt_cap = 0, cb_cap = 0;
+    } ws_clean;
+    void ws_dirty() { ws_clean = WsClean{}; }
     // optional HIP-event timing of the dominant kernel launch (lshkm_last_kernel_ms)
     bool timing = false;
     hipEvent_t tev[3] = {nullptr, nullptr, nullptr};   // [2]: the side stream's end (hash fix-up)

@@ -145,6 +145,13 @@ int launch_add_counter(hipStream_t s, unsigned long long* dst, const unsigned lo
 // stats[dst_idx[i]] += *src[i], i < n <= 8, in one launch
 int launch_add_counters(hipStream_t s, unsigned long long* stats, int n, const int* dst_idx,
                         const unsigned long long* const* src);
+// The fused assignment's last kernel: stats[dst_idx[i]] += *srcs[i] (i < n <= 8),
+// then cnt[0, ncnt) and cb[0, ncb) zeroed, and the centroid override of
+// src_rows (device) where it is not NULL (K > 8192: by launch_assign_override
+// after it).
+int launch_fused_epilogue(hipStream_t s, unsigned long long* stats, int n, const int* dst_idx,
+                          const unsigned long long* const* srcs, unsigned long long* cnt, int ncnt, unsigned int* cb,
+                          int ncb, const int32_t* src_rows, int K, int64_t N, int32_t* assign, double* dist);
 
 // Stable bucket scatter (scatter.hip).
 size_t sort_scratch_bytes(int64_t N, int64_t range, int T = 1);

@@ -99,4 +99,28 @@ __device__ inline void pruned_pick_euclid(const TX* __restrict__ xr, const doubl
     best = group_min<G>(v);
 }
 
+// The every-centroid loop of one row over the wave's lanes, dd(c) the
+// reference's distance. assignment.hpp:66: the -1 sentinel takes centroid 0's
+// distance even if NaN (a zero vector under cosine), which then blocks every
+// later '<'; any other NaN is never taken.
+template <typename F>
+__device__ inline void every_centroid(int K, F&& dd, double& best, int& bi) {
+    for (int c = threadIdx.x & 63; c < K; c += 64) {
+        const double v = dd(c);
+        if (bi < 0 ? (v == v || c == 0) : v < best) { best = v; bi = c; }
+    }
+}
+
+// The wave's (best, bi) of one row to its outputs: the smallest value, then the
+// smallest index (= the first strict minimum in c order); no lane took any:
+// the reference's sentinel.
+__device__ inline void wave_store(double best, int bi, int64_t row, int32_t* __restrict__ assign,
+                                  double* __restrict__ dist) {
+    group_argmin<64>(best, bi);
+    if ((threadIdx.x & 63) == 0) {
+        assign[row] = bi < 0 ? 0 : bi;
+        dist[row] = bi < 0 ? -1.0 : best;
+    }
+}
+
 }  // namespace lshkm

@@ -25,11 +25,14 @@ bucket = torch.empty((N, L), dtype=torch.int32, device=dev)
 assign = torch.empty((N,), dtype=torch.int32, device=dev)
 dist = torch.empty((N,), dtype=torch.float64, device=dev)
 p = lambda x: C.c_void_p(x.data_ptr())
+# TF_SRC=1: the centroid override of a Lloyd step (the rows the centroids were taken from), as bench.py passes it
+src32 = rows.astype(np.int32)
+src = src32.ctypes.data_as(C.c_void_p) if os.environ.get("TF_SRC") == "1" else None
 lshkm._ck(lib.lshkm_ctx_enable_timing(ctx.h, 1))
 ms = C.c_float()
 ts = []
 for it in range(8):
-    lshkm._ck(lib.lshkm_hash_assign(lsh.h, p(X), N, p(Cc), K, None, p(tuples), None, p(bucket), p(assign), p(dist)))
+    lshkm._ck(lib.lshkm_hash_assign(lsh.h, p(X), N, p(Cc), K, src, p(tuples), None, p(bucket), p(assign), p(dist)))
     lshkm._ck(lib.lshkm_last_kernel_ms(ctx.h, C.byref(ms)))
     if it >= 2:
         ts.append(ms.value)
@@ -40,7 +43,7 @@ t1 = torch.cuda.Event(enable_timing=True)
 torch.cuda.synchronize()
 t0.record()
 for _ in range(5):
-    lshkm._ck(lib.lshkm_hash_assign(lsh.h, p(X), N, p(Cc), K, None, p(tuples), None, p(bucket), p(assign), p(dist)))
+    lshkm._ck(lib.lshkm_hash_assign(lsh.h, p(X), N, p(Cc), K, src, p(tuples), None, p(bucket), p(assign), p(dist)))
 t1.record()
 torch.cuda.synchronize()
 print(f"{os.path.basename(os.environ.get('LSHKM_LIB', 'liblshkm.so'))}: fused pass {np.median(ts):.3f} ms, "
