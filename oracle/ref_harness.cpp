@@ -842,6 +842,69 @@ static int mode_crec(int argc, char** argv) {
     return 0;
 }
 
+// ------------------------------------------------------------------ sil mode
+// sil IN N d K metric ASSIGN CENTERS OUT — silhouette_cluster (silhouette.hpp:31-80)
+// of a given clustering: ASSIGN holds N int32 cluster ids, CENTERS K*d doubles
+// (external centroids, ids "c<i>", as mode_lloyd's). Writes sil.npy [K+1] from
+// silhouette_cluster(separate_clusters_from_input(...)) and s.npy [N], each
+// member's silhouette_of_i called as silhouette_cluster calls it: clusters in
+// index order, members in cluster order, one distance map for the whole run.
+// The nearest-centroid loop (:35-58) is local to silhouette_cluster, so it is
+// repeated here on the reference's own distances; the sums of s.npy, formed as
+// :68-78 forms them, must give sil.npy's bits, or the mode fails.
+static int mode_sil(int argc, char** argv) {
+    if (argc < 9) { fprintf(stderr, "usage: sil IN N d K metric ASSIGN CENTERS OUT\n"); return 2; }
+    std::string in = argv[1]; int N = atoi(argv[2]); int d = atoi(argv[3]); int K = atoi(argv[4]);
+    std::string metric = argv[5], out = argv[8];
+    std::vector<double> x = read_rows(in, (size_t)N * d);
+    std::vector<int32_t> assign = read_raw<int32_t>(argv[6], N);
+    std::vector<double> c = read_f64(argv[7], (size_t)K * d);
+    std::vector<Vec> vecs = make_vectors(x, N, d, "");
+    for (int n = 0; n < N; n++) vecs[n].setCluster(assign[n], 0.0);
+    std::vector<Vec> ext;
+    ext.reserve(K);
+    for (int i = 0; i < K; i++) ext.emplace_back("c" + std::to_string(i), std::vector<double>(c.begin() + (size_t)i * d, c.begin() + (size_t)(i + 1) * d));
+    std::vector<Vec*> centroids(K);
+    for (int i = 0; i < K; i++) centroids[i] = &ext[i];
+    std::vector<double> sil = silhouette_cluster(separate_clusters_from_input(vecs, K), centroids, metric);
+    write_npy(out + "/sil.npy", sil, {sil.size()});
+
+    std::vector<int> near(K);
+    for (int ci = 0; ci < K; ci++) {
+        double mn = -1; int arg = 0;
+        for (int i = 0; i < K; i++) {
+            if (i == ci) continue;
+            double dist = metric == "euclidean" ? centroids[ci]->euclideanDistance(centroids[i])
+                                                : centroids[ci]->cosineDistance(centroids[i]);
+            if (mn == -1 || dist < mn) { mn = dist; arg = i; }
+        }
+        near[ci] = arg;
+    }
+    std::vector<std::vector<Vec*>> clusters = separate_clusters_from_input(vecs, K);
+    std::unordered_map<std::string, double> distanceMap;
+    std::vector<double> s(N), sums(K + 1);
+    sums[K] = 0;
+    int vector_num = 0;
+    for (int ci = 0; ci < K; ci++) {
+        sums[ci] = 0;
+        for (int vi = 0; vi < (int)clusters[ci].size(); vi++) {
+            double si = silhouette_of_i(clusters[ci], vi, clusters[near[ci]], metric, distanceMap);
+            s[clusters[ci][vi] - vecs.data()] = si;
+            sums[ci] = sums[ci] + si;
+        }
+        sums[K] = sums[K] + sums[ci];
+        sums[ci] = sums[ci] / clusters[ci].size();
+        vector_num = vector_num + clusters[ci].size();
+    }
+    sums[K] = sums[K] / vector_num;
+    if (memcmp(sums.data(), sil.data(), sizeof(double) * (K + 1)) != 0) {
+        fprintf(stderr, "sil: the per-member run does not reproduce silhouette_cluster\n");
+        return 3;
+    }
+    write_npy(out + "/s.npy", s, {(size_t)N});
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) { fprintf(stderr, "usage: ref_harness {lsh|cube|lloyd|kmeanspp|bench} ...\n"); return 2; }
     if (std::string(argv[1]) == "crec") return mode_crec(argc - 1, argv + 1);
@@ -857,6 +920,7 @@ int main(int argc, char** argv) {
     if (m == "conf") return mode_conf(argc - 1, argv + 1);
     if (m == "c1") return mode_c1(argc - 1, argv + 1);
     if (m == "chain") return mode_chain(argc - 1, argv + 1);
+    if (m == "sil") return mode_sil(argc - 1, argv + 1);
     fprintf(stderr, "unknown mode %s\n", m.c_str());
     return 2;
 }

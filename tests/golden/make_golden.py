@@ -14,7 +14,7 @@ fp64 cases (kind f64_*, chain, c1 with "f64": true) run on general doubles shape
 like the recommender's user vectors (user_vectors below); their inputs ARE
 stored (x64 / q64 / pool ... arrays), as fixtures.
 
-Usage: python tests/golden/make_golden.py [--only lsh,cube,lloyd,kmeanspp,range,csv,conf,c1,recom,f64,chain,crec]
+Usage: python tests/golden/make_golden.py [--only lsh,cube,lloyd,kmeanspp,range,csv,conf,c1,recom,f64,chain,crec,sil]
 (--only regenerates those kinds and keeps the other cases' entries.)
 """
 import json
@@ -29,7 +29,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle  # noqa: E402
+import sil_cases  # noqa: E402
 
 HARNESS = os.path.join(ROOT, "oracle", "_ref", "ref_harness")
 
@@ -491,6 +493,22 @@ def main(only=None):
             np.savez_compressed(os.path.join(HERE, name + ".npz"), **res)
             meta[name] = dict(kind="crec", N=N, F=F, d=d, K=K, iters=iters, min_dist=md, seedA=sa, seedB=sb,
                               NTA=nta, NTB=ntb, data_seed=dseed, fake_dup=dup)
+        # the silhouette at the edges the oracle only restates (K = 1, a singleton, an
+        # empty nearest cluster, tied and NaN centroid distances, inf rows): inputs
+        # from tests/sil_cases.py, stored; fixtures under tests/golden/sil/
+        for name in (sil_cases.FIXTURE_NAMES if want("sil") else []):
+            out = os.path.join(tmp, name); os.makedirs(out)
+            x, assign, c, metric = sil_cases.fixture_inputs(name)
+            N, d = x.shape
+            for arr, fn in ((x, "x.f64"), (assign, "assign.i32"), (c, "c.f64")):
+                arr.tofile(os.path.join(out, fn))
+            run(["sil", os.path.join(out, "x.f64"), N, d, len(c), metric, os.path.join(out, "assign.i32"),
+                 os.path.join(out, "c.f64"), out])
+            res = load_dir(out)
+            res.update(x=x, assign=assign, centers=c, metric=np.array([int(metric == "cosine")], np.int32))
+            os.makedirs(os.path.join(HERE, "sil"), exist_ok=True)
+            np.savez_compressed(os.path.join(HERE, "sil", name + ".npz"), **res)
+            meta[name] = dict(kind="sil", N=N, d=d, K=len(c), metric=metric, file="sil/" + name + ".npz")
         for name, text in (CONF_CASES.items() if want("conf") else []):
             path = os.path.join(iodir, name + ".conf")
             with open(path, "w", newline="") as f:

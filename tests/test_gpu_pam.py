@@ -148,6 +148,14 @@ def case_expect(key, Xh, assign, K, metric, prev):
     (600, "grid", np.float32, "euclidean", 0),            # above the exact kernel's LDS row limit (512)
     (8, "grid", np.float32, "cosine", 101),               # zero rows; row 0 is a zero first member
     (100, "normal", np.float64, "cosine", 101),
+    # d % 4 != 0: the scalar tail of sil_euclid (pairsum.h) and the screen's
+    # element-wise staging loop (clusters of >= 64 members take the screen)
+    (1, "grid", np.float32, "euclidean", 0),
+    (3, "normal", np.float32, "euclidean", 0),
+    (7, "normal", np.float64, "euclidean", 0),            # general doubles
+    (33, "wide", np.float32, "euclidean", 0),
+    (513, "grid", np.float32, "euclidean", 0),
+    (5, "grid", np.float32, "cosine", 101),
 ])
 def test_pam_generated(ctx, sw, sctx, monkeypatch, d, kind, dtype, metric, zero_every):
     K = len(SIZES)

@@ -209,6 +209,26 @@ def test_range_silhouette(name):
         assert np.array_equal(out.view(np.uint64), g[f"sil{it}"].view(np.uint64)), it
 
 
+@pytest.mark.parametrize("name", cases("sil"))
+def test_sil_edges(name):
+    # silhouette_cluster and each member's silhouette_of_i at the edges the
+    # oracle restates without a workload ever reaching them (tests/golden/sil:
+    # K = 1 and 2, a singleton, an empty nearest cluster, tied and NaN centroid
+    # distances, zero rows, inf rows), NaN bits included
+    import sil_cases
+    assert META[name]["file"] == "sil/" + name + ".npz"
+    x, assign, centers, metric, sil, s = sil_cases.fixture(name)
+    assert metric == META[name]["metric"] and x.shape == (META[name]["N"], META[name]["d"])
+    out, so = oracle.silhouette(x, assign, centers, metric)
+    assert np.array_equal(out.view(np.uint64), sil.view(np.uint64)), (out, sil)
+    assert np.array_equal(so.view(np.uint64), s.view(np.uint64)), np.nonzero(so.view(np.uint64) != s.view(np.uint64))[0]
+
+
+def test_sil_edges_present():
+    import sil_cases
+    assert cases("sil") == sorted(sil_cases.FIXTURE_NAMES) == sil_cases.fixtures()
+
+
 @pytest.mark.parametrize("name", cases("chain"))
 def test_recommender_chain(name):
     # main.cpp:149-222: cosine LSH over user vectors (general doubles), filtered
