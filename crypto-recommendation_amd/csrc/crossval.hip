@@ -175,7 +175,9 @@ __global__ __launch_bounds__(256) void cv_predict_kernel(const double* __restric
             pred[e] = 0.0;
             continue;
         }
-        pred[e] = x86_nan(rc_predict_at(X, x_mean, d, nb_idx + q * P, nb_sim + q * P, nb_cnt[q], index, u_mean[q]));
+        double v = rc_predict_at(X, x_mean, d, nb_idx + q * P, nb_sim + q * P, nb_cnt[q], index, u_mean[q]);
+        if (v != v) v = rc_predict_nan(X, x_mean, d, nb_idx + q * P, nb_sim + q * P, nb_cnt[q], index, u_mean[q]);
+        pred[e] = v;
     }
 }
 

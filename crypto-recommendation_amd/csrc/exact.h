@@ -455,3 +455,17 @@ __device__ inline void ld4d(const double* p, double (&o)[4]) {
 __device__ inline double x86_nan(double v) {
     return v != v ? __longlong_as_double((long long)0xFFF8000000000000ull) : v;
 }
+
+// A NaN that was an input is no such product: x86 hands it on, quieted, with
+// its own sign and payload. Of two NaN operands the x87 (FADD, FDIV) keeps the
+// one with the larger significand and, of two equal ones, the positive.
+__device__ inline double quiet_nan(double v) {
+    return __longlong_as_double(__double_as_longlong(v) | 0x0008000000000000ll);
+}
+__device__ inline double x87_nan_pick(double a, double b) {
+    const unsigned long long ba = (unsigned long long)__double_as_longlong(quiet_nan(a));
+    const unsigned long long bb = (unsigned long long)__double_as_longlong(quiet_nan(b));
+    const unsigned long long ma = ba & 0x000FFFFFFFFFFFFFull, mb = bb & 0x000FFFFFFFFFFFFFull;
+    if (ma != mb) return __longlong_as_double((long long)(ma > mb ? ba : bb));
+    return __longlong_as_double((long long)((ba >> 63) ? bb : ba));
+}

@@ -38,14 +38,45 @@ constexpr int RC_MAXV = 8;       // candidates per lane held in registers (n <= 
 // CustVector::cosineSimilarity (cust_vector.hpp:158-174), this = neighbour x,
 // in = user u: long-double inner product of double products, fp64 norms
 // (xa, ub: sum of squares in dim order), long-double division, then double.
+// The NaN cosineSimilarity returns when the inner product (ip_nan: a NaN
+// product, or inf - inf), the denominator (dn_nan) or both are NaN. A NaN the
+// operations made (inf * 0, inf - inf, 0 * inf of the norms) is the "real
+// indefinite", sign set; a NaN entry of x or u comes through quieted with its
+// own sign and payload: as the product's (SSE: x[j]'s if both are NaN), and
+// through pow, the fp64 sums and the square root as the denominator's (the
+// first NaN entry of x, else of u). The x87 adds and the division then choose
+// by x87_nan_pick. Exact for rows whose NaN entries are all one NaN; with
+// several different ones the fp64 sums' choice depends on the reference's
+// operand order, which is not restated. Out of line: the branch is cold.
+__device__ __noinline__ double rc_cos_sim_nan(const double* __restrict__ x, const double* __restrict__ u, int d,
+                                              bool ip_nan, bool dn_nan) {
+    const double indefinite = __longlong_as_double((long long)0xFFF8000000000000ull);
+    double ipn = indefinite, dn = indefinite;
+    bool dx = false, du = false;
+    double ux = 0.0;
+    for (int j = 0; j < d; j++) {
+        const double xj = x[j], uj = u[j];
+        if (xj != xj) {
+            ipn = x87_nan_pick(ipn, xj);
+            if (!dx) { dn = quiet_nan(xj); dx = true; }
+        } else if (uj != uj) {
+            ipn = x87_nan_pick(ipn, uj);
+            if (!du) { ux = quiet_nan(uj); du = true; }
+        }
+    }
+    if (!dx && du) dn = ux;
+    if (ip_nan && dn_nan) return x87_nan_pick(ipn, dn);
+    return ip_nan ? ipn : dn;
+}
+
 __device__ inline double rc_cos_sim(const double* __restrict__ x, const double* __restrict__ u, int d, double xa,
                                     double ub) {
     X87acc ip;
     ip.init();
     const double denom = __dmul_rn(sqrt(xa), sqrt(ub));
     // Infinite products or norms (an inf entry, a row whose squares overflow)
-    // are outside the soft chain: the x87's results for special operands, the
-    // default NaN being its "real indefinite" (sign set). inf: 1 = +, 2 = -.
+    // are outside the soft chain: the x87's results for special operands
+    // (rc_cos_sim_nan for the NaN ones). inf: 1 = +, 2 = -.
     int inf = 0;
     bool nan = false;
     for (int j = 0; j < d; j++) {
@@ -56,7 +87,7 @@ __device__ inline double rc_cos_sim(const double* __restrict__ x, const double* 
     }
     if (inf || nan || !(denom < __builtin_inf())) {
         const double indefinite = __longlong_as_double((long long)0xFFF8000000000000ull);
-        if (nan || inf == 3 || denom != denom) return indefinite;
+        if (nan || inf == 3 || denom != denom) return rc_cos_sim_nan(x, u, d, nan || inf == 3, denom != denom);
         if (inf) return denom == __builtin_inf() ? indefinite : inf == 1 ? __builtin_inf() : -__builtin_inf();
         return ip.value().s ? -0.0 : 0.0;                  // finite / inf
     }

@@ -823,7 +823,8 @@ int lshkm_cv_exclude(lshkm_ctx ctx, const int64_t* in_ptr_dev, const int32_t* in
  * (unk_ptr_dev [nq+1] with unk_ptr[0] = 0, unk_idx_dev) = main_sum / abs_sum +
  * u_mean, both sums over the user's kept neighbours in their sorted order
  * (:289-297) -- the sums lshkm_top_n_recom sorts by. No neighbour or all
- * similarities 0 gives 0 / 0: NaNs are x86's default NaN. */
+ * similarities 0 gives 0 / 0: NaNs are x86's default NaN; a NaN similarity
+ * comes through with its own sign, as x86 hands an operand NaN on. */
 int lshkm_predicted_scores(lshkm_ctx ctx, const double* X_dev, const double* x_mean_dev, int64_t N, int d,
                            const double* u_mean_dev, int64_t nq, const int64_t* unk_ptr_dev, const int32_t* unk_idx_dev,
                            const int32_t* nb_idx_dev, const double* nb_sim_dev, const int32_t* nb_cnt_dev, int P,

@@ -14,7 +14,7 @@ fp64 cases (kind f64_*, chain, c1 with "f64": true) run on general doubles shape
 like the recommender's user vectors (user_vectors below); their inputs ARE
 stored (x64 / q64 / pool ... arrays), as fixtures.
 
-Usage: python tests/golden/make_golden.py [--only lsh,cube,lloyd,kmeanspp,range,csv,conf,c1,recom,f64,chain,crec,sil]
+Usage: python tests/golden/make_golden.py [--only lsh,cube,lloyd,kmeanspp,range,csv,conf,c1,recom,recomedge,f64,chain,crec,sil]
 (--only regenerates those kinds and keeps the other cases' entries.)
 """
 import json
@@ -31,6 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle  # noqa: E402
+import recom_cases  # noqa: E402
 import sil_cases  # noqa: E402
 
 HARNESS = os.path.join(ROOT, "oracle", "_ref", "ref_harness")
@@ -529,6 +530,26 @@ def main(only=None):
             res = load_dir(out); res.update(inp)
             np.savez_compressed(os.path.join(HERE, name + ".npz"), **res)
             meta[name] = dict(kind="recom", N=N, d=d, Q=Q, P=P, NTOP=NT, seed=seed, values=values)
+        # the recommend step at its structural edges (a planted tie, a near tie,
+        # special operands, every list length): inputs from tests/recom_cases.py,
+        # stored; fixtures under tests/golden/recom/. A kind of its own: the
+        # "recom" cases' parametrisations stay as they are.
+        for name in (recom_cases.FIXTURES if want("recomedge") else []):
+            out = os.path.join(tmp, name); os.makedirs(out)
+            c = recom_cases.fixture_inputs(name)
+            inp = dict(zip(recom_cases.INPUT_KEYS, c[:8]))
+            P, NT = c[8], c[9]
+            (N, d), Q = inp["x"].shape, len(inp["u"])
+            ext = dict(x="f64", xmean="f64", u="f64", umean="f64", unk_ptr="i64", unk_idx="i32",
+                       cand_ptr="i64", cand_idx="i32")
+            for k, e in ext.items():
+                inp[k].tofile(os.path.join(out, f"{k}.{e}"))
+            run(["recom", out, N, d, Q, P, NT])
+            res = load_dir(out); res.update(inp)
+            os.makedirs(os.path.join(HERE, "recom"), exist_ok=True)
+            np.savez_compressed(os.path.join(HERE, "recom", name + ".npz"), **res)
+            meta[name] = dict(kind="recomedge", N=N, d=d, Q=Q, P=P, NTOP=NT, case=recom_cases.FIXTURES[name],
+                              file="recom/" + name + ".npz")
     finally:
         shutil.rmtree(tmp)
     with open(os.path.join(HERE, "cases.json"), "w") as f:

@@ -154,6 +154,32 @@ def test_recommend_step(name):
     assert np.array_equal(top[has], g["top"][has])
 
 
+@pytest.mark.parametrize("name", cases("recomedge"))
+def test_recommend_edges(name):
+    # get_P_closest and get_top_N_recom at the edges the oracle otherwise only
+    # restates (tests/golden/recom: a planted tie, a near tie, inf / NaN /
+    # overflowing / underflowing operands, every list length around P = 20):
+    # the reference's own results, similarity bits included. For the special
+    # operands the reference decides which NaN comes out.
+    import recom_cases
+    m = META[name]
+    assert m["file"] == "recom/" + name + ".npz"
+    g = recom_cases.fixture(name)
+    idx, sim, cnt = oracle.p_closest(g["x"], g["u"], g["cand_ptr"], g["cand_idx"], m["P"])
+    assert np.array_equal(cnt, g["pc_cnt"])
+    assert np.array_equal(idx, g["pc_idx"])
+    assert np.array_equal(sim.view(np.uint64), g["pc_sim"].view(np.uint64))
+    top = oracle.top_n_recom(g["x"], g["xmean"], g["u"], g["umean"], g["unk_ptr"], g["unk_idx"], idx, sim, cnt,
+                             m["NTOP"])
+    has = cnt > 0                     # main.cpp:161 skips users without neighbours
+    assert np.array_equal(top[has], g["top"][has])
+
+
+def test_recommend_edges_present():
+    import recom_cases
+    assert cases("recomedge") == sorted(recom_cases.FIXTURES) == recom_cases.fixtures()
+
+
 def test_probe_sequence_rules():
     # lsh_cube.hpp:148-150 quirk: probes == 1 skips Hamming distance 1.
     assert list(oracle.cube_probe_seq(0, 1, 4)) == [0, 0b11]
